@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — forward+backward images/s of UNet(3,12) on synthetic 3x360x480 batches (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]            (N=1)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (N=1)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W                   (N>1: one rank per GPU, RCCL)
 
@@ -9,7 +9,15 @@ One "step" = zero_grad(set_to_none) -> net(x) -> CrossEntropy -> backward (-> gr
 on a per-GPU batch of 8 (SURVEY.md §8d timed region; the optimizer step is excluded and reported separately).
 Inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs (--dump-outputs DIR: loss, logits,
+parameter gradients, BatchNorm running statistics as DIR/<name>.npy, under 64 MB) and prints the line: metric, value,
+unit, higher_is_better, dtype, ms_per_step (one timed step).  Inputs and initial weights are seeded: the same arguments
+give the same inputs in every run, so two builds can be compared output for output.
+
+Extra objects on the line, measured with --full only (--no-kernel-profile, --no-cpu-baseline, --no-dp-overhead and
+--no-extra-configs switch single ones off again):
+  dp_overhead   — (N=1, headline configuration; --dp-overhead asks for it in any run) see dp_overhead_leg.
+  config.w2d_tile.logits_vs_reference — the headline logits against the dense reference fixture (logits_accuracy).
   roofline      — the dominant kernel (largest share of step time).  `achieved` / `frac` are the FLOPs the matrix pipe
                   EXECUTES per second over the dense MFMA peak (a hardware fraction, <= 1): algorithmic FLOPs per launch x
                   the kernel's executed share (Winograd F(4,3) runs 9 of 18) / average launch duration, measured live with
@@ -21,6 +29,7 @@ Extra objects on the line:
   extra_configs — (N=1, headline configuration only) short legs of the other single-GPU configurations of BASELINE.json in the
                   same process, after the headline measurement: configs[3] (UNet 4x3x720x960, bf16 storage + bf16 MFMA) and
                   configs[4] (SegNet 8x3x360x480 fp32): images/s, ms/step, dominant kernel, its executed fraction of peak.
+In every run at N>1:
   dp            — (N>1) what took part and how much of the exchange was exposed: device UUID / PCI bus id of every rank,
                   distinct GPUs, gradient buckets, the compute stream's wait for the all-reduces per step (HIP events around
                   GradSync.finish), per-rank step time min/max, the RCCL environment knobs in effect.
@@ -45,11 +54,18 @@ PER_GPU_BATCH = 8
 H, W = 360, 480
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the instrumented kernel profile (roofline, "
+                         "conv_kernels, hbm_kernels), the logits against tests/golden, the dp_overhead leg, the CPU baseline and the "
+                         "extra_configs legs (each still switched off by its --no-* option); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): loss, logits, "
+                         "grad.<parameter>, bn.<buffer>; an array larger than its cap is a fixed, seeded sample of its flattened elements")
     ap.add_argument("--model", default="unet", choices=["unet", "segnet"])
     ap.add_argument("--batch", type=int, default=PER_GPU_BATCH)
     ap.add_argument("--height", type=int, default=H)
@@ -62,7 +78,7 @@ def parse():
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph (N=1; reported under `graph_replay`, never `value`)")
     ap.add_argument("--with-optimizer", action="store_true", help="also time AdamW steps (reported separately)")
     ap.add_argument("--dp-overhead", action="store_true",
-                    help="(kept for compatibility: since round 5 the leg runs by default at N=1 on the headline configuration) the DP step on a "
+                    help="(with --full the leg runs at N=1 on the headline configuration; this flag asks for it in any run) the DP step on a "
                          "world-size-1 RCCL group (real all-reduce launches, CVK_DP_RESERVE_CUS CUs left free), eager and as one captured "
                          "graph; reported under `dp_overhead`, never `value`")
     ap.add_argument("--no-dp-overhead", action="store_true", help="skip the `dp_overhead` leg")
@@ -74,7 +90,7 @@ def parse():
     ap.add_argument("--with-input-pipeline", action="store_true",
                     help="also time the steps fed from HOST uint8 frames through DevicePrefetcher (pinned staging, 1-byte upload one "
                          "batch ahead, device-side normalisation): the PCIe-inclusive rate, reported separately, never `value`")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def config_label(model, batch, h, w, precision, world):
@@ -235,8 +251,50 @@ def logits_accuracy(net, x):
             "tolerance_max_abs": tol, "source": "measured in this run against tests/golden/unet_s0_8x360x480_dense.npz (reference-generated)"}
 
 
-def run_leg(A, dev, model, batch, h, w, precision, steps, warmup, profile, world=1, rank=0, rehearsal=False, want_model=False, split3=False):
-    """Build the network, time `steps` steps after `warmup`, optionally profile the kernels.  Returns a dict."""
+DUMP_MAX_BYTES = 64 * 10 ** 6       # --dump-outputs writes at most this much in all
+DUMP_CAP_LOGITS = 1 << 21           # elements kept of the logits (8 x 12 x 360 x 480 = 16.6 M: a sample)
+DUMP_CAP_PARAM = 1 << 19            # elements kept of one parameter's gradient (the 9 largest UNet weights are sampled)
+
+
+def sample_output(t, cap, name):
+    """`t` as float32 numpy, whole while it has at most `cap` elements; else `cap` of its elements in logical (flattened) order at
+    indices drawn without replacement from a generator seeded by the name: the same positions in every run and every build."""
+    import zlib
+    import numpy as np
+    t = t.detach()
+    if t.numel() <= cap:
+        return t.float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), cap, replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+
+def capture_outputs(net, loss, logits):
+    """What a caller of the timed step holds after it: the loss, the logits, every parameter's gradient, the BatchNorm running
+    statistics the forward passes updated."""
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy(), "logits": sample_output(logits, DUMP_CAP_LOGITS, "logits")}
+    for n, p in net.named_parameters():
+        out["grad." + n] = sample_output(p.grad, DUMP_CAP_PARAM, "grad." + n)
+    for n, b in net.named_buffers():
+        if b.is_floating_point():
+            out["bn." + n] = sample_output(b, DUMP_CAP_PARAM, "bn." + n)
+    return out
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"bench.py: wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {path}", file=sys.stderr)
+
+
+def run_leg(A, dev, model, batch, h, w, precision, steps, warmup, profile, world=1, rank=0, rehearsal=False, want_model=False, split3=False,
+            dump=False):
+    """Build the network, time `steps` steps after `warmup`, optionally profile the kernels.  Returns a dict; with `dump`, its
+    "outputs" are what the last timed step computed (capture_outputs)."""
     from pytorch_camvid_amd import ddp
     torch.manual_seed(0)                                    # identical init on every rank (also broadcast by DataParallel)
     net = A.get_model(model, 3, 12).to(dev).train()
@@ -249,6 +307,7 @@ def run_leg(A, dev, model, batch, h, w, precision, steps, warmup, profile, world
     x = torch.randn(batch, 3, h, w, generator=g).to(dev)
     t = torch.randint(0, 12, (batch, h, w), generator=g).to(dev)
     params = list(net.parameters())
+    kept = [None] if dump else None                         # the last step's logits, held only when they are to be written
 
     def step():
         for p in params:
@@ -257,7 +316,11 @@ def run_leg(A, dev, model, batch, h, w, precision, steps, warmup, profile, world
         # (Winograd-domain filters, data-grad packs, bf16 copies) are REBUILT inside every timed step, never served from the
         # executor's cache — the cache only helps eval and repeated passes over unchanged weights
         A.mark_weights_dirty(net)
-        loss = lossf(wrapped(x), t)
+        if kept is None:
+            loss = lossf(wrapped(x), t)
+        else:
+            kept[0] = wrapped(x)
+            loss = lossf(kept[0], t)
         loss.backward()
         return loss
 
@@ -295,6 +358,9 @@ def run_leg(A, dev, model, batch, h, w, precision, steps, warmup, profile, world
                            "buckets": [{"floats": hi - lo, "MB": round((hi - lo) * 4 / 2 ** 20, 1)} for lo, hi in sync.launched]}
     out.update({"value": world * batch * steps / dt, "ms": dt / steps * 1e3, "loss": float(loss.item()), "step": step, "fence": fence,
                 "net": net, "wrapped": wrapped, "lossf": lossf, "params": params, "x": x, "t": t})
+    if dump:
+        out["outputs"] = capture_outputs(net, loss, kept[0])
+        kept[0] = None
     if profile:
         out["roof"], out["kernels"], out["hbm_kernels"] = kernel_profile(step, dev)
     if not want_model:
@@ -485,9 +551,11 @@ def main():
             _ddp.init_process_group("nccl", device_id=dev)     # RCCL
 
     headline = (a.model, a.batch, a.height, a.width, a.precision) == ("unet", PER_GPU_BATCH, H, W, "fp32") and not a.w2d_split
-    leg = run_leg(A, dev, a.model, a.batch, a.height, a.width, a.precision, a.steps, a.warmup, not a.no_kernel_profile,
-                  world=world, rank=rank, rehearsal=rehearsal, want_model=True, split3=a.w2d_split)
+    leg = run_leg(A, dev, a.model, a.batch, a.height, a.width, a.precision, a.steps, a.warmup, a.full and not a.no_kernel_profile,
+                  world=world, rank=rank, rehearsal=rehearsal, want_model=True, split3=a.w2d_split, dump=bool(a.dump_outputs) and rank == 0)
     step, params, net, wrapped, lossf = leg["step"], leg["params"], leg["net"], leg["wrapped"], leg["lossf"]
+    if "outputs" in leg:
+        write_outputs(a.dump_outputs, leg.pop("outputs"))
 
     # The optional extra loops run on EVERY rank: at N>1 each backward issues the bucketed all-reduces, which all ranks must post.
     opt_ms = None
@@ -557,9 +625,9 @@ def main():
         tf, td = (cfg, cfg) if cfg in (4, 6) else ((4, 6) if a.model == "segnet" else (6, 6))
         w2d_tile = {"tiles": f"channel-heavy layers: 2-D Winograd F({tf}x{tf},3x3) forward / weight-grad, F({td}x{td},3x3) data-grad "
                              "(CVK_W2D_TILE=4 selects the finer-rounding F(4x4,3x3) everywhere: about -8 % images/s)",
-                    "logits_vs_reference": logits_accuracy(net, leg["x"]) if (headline and rank == 0) else None}
+                    "logits_vs_reference": logits_accuracy(net, leg["x"]) if (a.full and headline and rank == 0) else None}
     dp_over, dp_fail = None, False
-    if world == 1 and (a.dp_overhead or headline) and not a.no_dp_overhead and not rehearsal:
+    if world == 1 and (a.dp_overhead or (a.full and headline)) and not a.no_dp_overhead and not rehearsal:
         torch.cuda.synchronize(dev)
         dp_over = dp_overhead_in_child(a)          # its own process: RCCL + graph capture cannot take the headline down
         if "error" in dp_over:
@@ -579,7 +647,7 @@ def main():
             print("bench.py: " + dp["warning"], file=sys.stderr)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.model, a.height, a.width)
 
     # free the headline network before the extra legs
@@ -589,7 +657,7 @@ def main():
     torch.cuda.empty_cache()
 
     extra = None
-    if world == 1 and headline and not a.no_extra_configs:
+    if world == 1 and headline and a.full and not a.no_extra_configs:
         extra = []
         es, ew = max(3, min(a.steps, 30)), max(2, min(a.warmup, 5))       # (round 6: 30 / 5 instead of 10 / 3 — the short legs read 0.5-0.9 % below a run of their own)
         for (m, b, hh, ww, prec, sp3) in (("unet", 4, 720, 960, "bf16", 0), ("segnet", 8, 360, 480, "fp32", 0),

@@ -158,12 +158,12 @@ def test_unet_fullsize_batch2_all_three_losses():
 
 
 def test_bench_json_contract_single_gpu():
-    """`python bench.py` prints ONE JSON line with the driver's fields; the roofline fraction is a hardware fraction (executed
+    """`python bench.py --full` prints ONE JSON line with the driver's fields; the roofline fraction is a hardware fraction (executed
     MFMA FLOPs of the dominant kernel over the dense peak, <= 1) with the algorithmic rate beside it, and the memory-bound
     kernels (incl. the weight transforms and the 2-D Winograd transform passes) are listed with their share of 8 TB/s."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]

@@ -4,6 +4,7 @@ set -euo pipefail
 : "${GRAFT_REPO_ROOT:?}"
 cd "$GRAFT_REPO_ROOT"
 VAR=$1; A=$2; B=$3; shift 3
+set -- --full "$@"      # the lines below read the kernel profile (roofline, conv_kernels, hbm_kernels): only a --full run measures it
 # The product libcvk.so reads no environment (cvk_knob() is its default there): C-side knobs only exist in the experiments build.
 # Python-side knobs (read by engine.py / ddp.py) work with either library.
 PY_KNOBS=$(grep -oh 'environ\(\.get\)\?[(\[]"CVK_[A-Z0-9_]*' pytorch-camvid_amd/*.py | grep -o 'CVK_[A-Z0-9_]*' | sort -u)

@@ -4,6 +4,7 @@ set -euo pipefail
 : "${GRAFT_REPO_ROOT:?}"
 cd "$GRAFT_REPO_ROOT"
 A=$1; B=$2; shift 2
+set -- --full "$@"      # the lines below read the kernel profile (roofline, conv_kernels, hbm_kernels): only a --full run measures it
 for rep in 1 2 3; do
   for v in "$A" "$B"; do
     CVK_LIB_PATH="$GRAFT_REPO_ROOT/$v" python3 bench.py --no-extra-configs --no-cpu-baseline --no-dp-overhead "$@" > gpurun_out/ab_tmp.json 2> gpurun_out/ab_tmp.err

@@ -7,6 +7,7 @@ REPS=$1; PAT=$2; shift 2
 LIBS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do LIBS+=("$1"); shift; done
 [ $# -gt 0 ] && shift
+set -- --full "$@"      # the lines below read the kernel profile (roofline, conv_kernels, hbm_kernels): only a --full run measures it
 for rep in $(seq 1 "$REPS"); do
   for v in "${LIBS[@]}"; do
     CVK_LIB_PATH="$GRAFT_REPO_ROOT/$v" python3 bench.py --no-extra-configs --no-cpu-baseline --no-dp-overhead "$@" > gpurun_out/ab_tmp.json 2> gpurun_out/ab_tmp.err

@@ -17,7 +17,7 @@ stats_pass() {   # $1 suffix, $2... bench args
     local sfx=$1; shift
     local dir="$O/${TAG}_stats_${sfx}"
     rm -rf "$dir"
-    rocprofv3 --kernel-trace --stats --output-format csv -d "$dir" -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra-configs --no-dp-overhead "$@" \
+    rocprofv3 --kernel-trace --stats --output-format csv -d "$dir" -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra-configs --no-dp-overhead "$@" \
         > "$O/${TAG}_bench_${sfx}_under_rocprof.json" 2> "$O/${TAG}_stats_${sfx}.err"
     local csv
     csv=$(ls "$dir"/*/*kernel_stats.csv | head -1)
@@ -39,20 +39,20 @@ pmc_pass() {     # $1 suffix, $2 bench args (one string)
 }
 
 if [ "$LEG" = fp32 ] || [ "$LEG" = all ]; then
-    python3 bench.py > "$O/${TAG}_bench_fp32.json" 2> "$O/${TAG}_bench_fp32.err"
+    python3 bench.py --full > "$O/${TAG}_bench_fp32.json" 2> "$O/${TAG}_bench_fp32.err"
     echo "bench done: $(python3 -c "import json;d=json.load(open('$O/${TAG}_bench_fp32.json'));print(d['value'], d['ms_per_step'])")"
     stats_pass fp32
     pmc_pass fp32 ""
-    python3 bench.py --model segnet --no-cpu-baseline > "$O/${TAG}_bench_segnet.json" 2> "$O/${TAG}_bench_segnet.err"
+    python3 bench.py --full --model segnet --no-cpu-baseline > "$O/${TAG}_bench_segnet.json" 2> "$O/${TAG}_bench_segnet.err"
 fi
 if [ "$LEG" = bf16 ] || [ "$LEG" = all ]; then
-    python3 bench.py $BF16_ARGS --no-cpu-baseline > "$O/${TAG}_bench_bf16_720.json" 2> "$O/${TAG}_bench_bf16_720.err"
+    python3 bench.py --full $BF16_ARGS --no-cpu-baseline > "$O/${TAG}_bench_bf16_720.json" 2> "$O/${TAG}_bench_bf16_720.err"
     echo "bf16 bench done: $(python3 -c "import json;d=json.load(open('$O/${TAG}_bench_bf16_720.json'));print(d['value'], d['ms_per_step'])")"
     stats_pass bf16 $BF16_ARGS
     pmc_pass bf16 "$BF16_ARGS"
 fi
 if [ "$LEG" = split2 ]; then      # the opt-in fp16 split-operand mode on the headline workload (never part of "all": it is not the product default)
-    python3 bench.py --w2d-split=2 --no-cpu-baseline --no-extra-configs > "$O/${TAG}_bench_fp32_split2.json" 2> "$O/${TAG}_bench_fp32_split2.err"
+    python3 bench.py --full --w2d-split=2 --no-cpu-baseline --no-extra-configs > "$O/${TAG}_bench_fp32_split2.json" 2> "$O/${TAG}_bench_fp32_split2.err"
     echo "split2 bench done: $(python3 -c "import json;d=json.load(open('$O/${TAG}_bench_fp32_split2.json'));print(d['value'], d['ms_per_step'])")"
     stats_pass fp32_split2 --w2d-split=2
     pmc_pass fp32_split2 "--w2d-split=2"
