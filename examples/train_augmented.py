@@ -1,0 +1,68 @@
+#!/usr/bin/env python3
+"""The reference's training loop (train.py:100-134) fed the way the reference feeds it: 960x720 uint8 BGR frames and uint8 label
+maps through train.py's augmentation (Resize -> RandomRotation(15) -> RandomGaussianBlur -> RandomHorizontalFlip ->
+ColorJitter(0.4, 0.4) -> ToTensor -> Normalize), here on the device in one launch per batch (`DevicePrefetcher(transforms=...)`),
+and validation through train.py's valid transforms.  Synthetic frames stand in for CamVid (decoding PNGs is not part of this
+package); random.seed makes the augmentation decisions of the reference's Compose under the same seed.
+
+  python examples/train_augmented.py --epochs 2 --iters 20 -b 8
+"""
+import argparse
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import pytorch_camvid_amd as cvk  # noqa: E402
+from pytorch_camvid_amd import transforms  # noqa: E402
+
+
+def synthetic_camvid(n, b, seed):
+    """n batches of (uint8 frames [b,720,960,3] BGR, uint8 masks [b,720,960]): smooth 12-class blobs plus noise, learnable"""
+    g = np.random.default_rng(seed)
+    for _ in range(n):
+        blobs = g.integers(0, 12, (b, 45, 60), dtype=np.uint8)
+        masks = blobs.repeat(16, axis=1).repeat(16, axis=2)
+        frames = (masks[..., None].astype(np.int32) * np.array([20, 15, 10]) % 256 + g.integers(0, 30, masks.shape + (3,)))
+        yield np.clip(frames, 0, 255).astype(np.uint8), masks
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("-net", "--net", default="unet")
+    ap.add_argument("-b", type=int, default=8)
+    ap.add_argument("-lr", type=float, default=5e-4)
+    ap.add_argument("--epochs", type=int, default=2)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    random.seed(a.seed)
+    net = cvk.get_model(a.net, 3, 12).to(dev)
+    opt = torch.optim.AdamW(net.parameters(), lr=a.lr)
+    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=a.iters, epochs=a.epochs)
+    loss_fn = cvk.CrossEntropyLoss()
+    train_tf, valid_tf = transforms.train_transforms(), transforms.valid_transforms()
+    for epoch in range(1, a.epochs + 1):
+        net.train()
+        t0 = time.time()
+        for images, masks in cvk.DevicePrefetcher(synthetic_camvid(a.iters, a.b, epoch), transforms=train_tf):
+            opt.zero_grad()
+            loss = loss_fn(net(images), masks)
+            loss.backward()
+            opt.step(); sched.step()
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        print(f"epoch {epoch}: loss {loss.item():.4f}  {a.b * a.iters / dt:.1f} img/s (incl. host data synthesis)")
+        val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
+        acc, iou, miou = cvk.evaluate(net, val, num_classes=12, ignore_index=11)
+        print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}")
+
+
+if __name__ == "__main__":
+    main()

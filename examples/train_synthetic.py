@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The training loop of the reference (train.py:100-134 + validation :169-206) on synthetic CamVid-shaped data,
-driving the MI355X-native network.  Real CamVid needs the reference's cv2/torchvision data pipeline, which is out
-of scope here; everything from the tensors onward is the product path.
+driving the MI355X-native network.  Frames are synthesised at the network's input size; for the reference's own
+augmentation of 960x720 frames on the device see examples/train_augmented.py.  Everything from the tensors onward is the product path.
 
   python examples/train_synthetic.py --net unet --epochs 2 --iters 20 -b 8
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_synthetic.py   # data parallel

@@ -450,6 +450,28 @@ int cvk_confusion_accumulate(const int64_t* pred, const int64_t* label, int64_t*
  * dst[c] = (src[c]/255 - mean3[c]) / std3[c].  mean3 / std3 are HOST pointers to 3 floats. */
 int cvk_preprocess_u8(const uint8_t* src, float* dst, int N, int H, int W, const float* mean3, const float* std3, void* stream);
 
+/* ---- training / validation transforms on device (transforms.py Resize -> RandomGaussianBlur -> RandomHorizontalFlip ->
+ * ColorJitter -> ToTensor -> Normalize, composed in train.py:61-75), one launch per batch.
+ * frames uint8 [N,Hs,Ws,3] (cv2 BGR), masks [N,Hs,Ws] of mask_bytes = 1 (uint8) or 8 (int64) per value -> out float32 NHWC
+ * ld = 4 [N,H,W,4] (cvk_preprocess_u8's expression and layout), out_masks int64 [N,H,W], out_u8 (nullable) uint8 [N,H,W,3]: the
+ * augmented frame before normalisation.  Per sample, in order: bilinear resize (cv2 INTER_LINEAR mapping (d + 0.5) * in / out
+ * - 0.5, clamped at the edges, rounded half-up), separable Gaussian of ksize taps (fp32, REFLECT_101 in resized coordinates,
+ * rounded half-up), the 256-entry LUT, the horizontal flip; masks: nearest resize (source floor(d * in / out)) and the flip.
+ * records: DEVICE array of N cvk_augment_record; ksize outside {3,5,7,9} means no blur.  mean3 / std3 are HOST pointers to 3
+ * floats.  No allocation and no synchronisation: the call can be captured in a graph. */
+typedef struct cvk_augment_record {
+    int32_t flip;                /* != 0: mirror left-right */
+    int32_t ksize;               /* Gaussian taps: 3, 5, 7 or 9; anything else: no blur */
+    int32_t use_lut;             /* != 0: apply lut (else it is the identity and is not read) */
+    int32_t reserved;
+    float   taps[12];            /* taps[0 .. ksize-1] */
+    uint8_t lut[256];
+} cvk_augment_record;
+int cvk_augment_record_bytes(void);
+int cvk_augment_u8(const uint8_t* frames, const void* masks, int mask_bytes, int N, int Hs, int Ws, int H, int W,
+                   const cvk_augment_record* records, const float* mean3, const float* std3, float* out, int64_t* out_masks,
+                   uint8_t* out_u8, void* stream);
+
 /* ---- fused AdamW over a flat fp32 buffer (torch.optim.AdamW: train.py:100,133) -------------------------------- */
 int cvk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);

@@ -180,6 +180,9 @@ SIGNATURES = {
     "cvk_argmax_channels": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp]),
     "cvk_confusion_accumulate": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "cvk_preprocess_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_vp]),
+    "cvk_augment_record_bytes": (c_int, []),
+    "cvk_augment_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(ctypes.c_float),
+                               ctypes.POINTER(ctypes.c_float), c_vp, c_vp, c_vp, c_vp]),
     "cvk_bf16s_rows_pad": (c_int, [c_int]),
     "cvk_bf16s_stat_partials": (c_int, [c_int, c_int, c_int]),
     "cvk_bf16s_stat_partials_c": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -219,6 +222,11 @@ SIGNATURES = {
 
 _lib = None
 _lock = threading.Lock()
+
+
+class AugmentRecord(ctypes.Structure):  # include/cvk.h cvk_augment_record (its size: cvk_augment_record_bytes())
+    _fields_ = [("flip", ctypes.c_int32), ("ksize", ctypes.c_int32), ("use_lut", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("taps", ctypes.c_float * 12), ("lut", ctypes.c_uint8 * 256)]
 
 
 class PackJob(ctypes.Structure):        # include/cvk.h cvk_pack_job

@@ -250,14 +250,19 @@ class DevicePrefetcher:
     [N,H,W,3] BGR, int64 masks [N,H,W]) batches from any host iterable (numpy arrays or CPU tensors), stages them in
     pinned buffers and uploads 1 byte per value on a side stream one batch ahead of the consumer; normalisation to the
     network's float NHWC layout happens on the device (`preprocess_uint8`).  Yields (images float32 [N,3,H,W] view, masks).
-    The yielded tensors are safe to use on the current stream (the side stream's work is awaited before they are handed out)."""
+    The yielded tensors are safe to use on the current stream (the side stream's work is awaited before they are handed out).
+    With `transforms` (a `transforms.Compose`, e.g. `transforms.train_transforms()`) each batch's augmentation parameters are
+    drawn while it is staged, in batch order, and go up with its frames (pinned records, same side stream); the frames then pass
+    through `cvk_augment_u8` instead of `preprocess_uint8` (masks uint8 or int64; uint8 ones travel at 1 byte per pixel) and the
+    masks come back int64 at the transforms' output size.  `transforms` supplies its own Normalize mean / std."""
 
-    def __init__(self, batches, device="cuda", mean=CAMVID_MEAN, std=CAMVID_STD):
+    def __init__(self, batches, device="cuda", mean=CAMVID_MEAN, std=CAMVID_STD, transforms=None):
         self.it = iter(batches)
         self.dev = torch.device(device)
         self.mean, self.std = mean, std
+        self.transforms = transforms
         self.stream = torch.cuda.Stream(self.dev)
-        self._pin = [None, None]        # two pinned staging slots (frames, masks), reused when shapes repeat
+        self._pin = [None, None]        # two pinned staging slots (frames, masks[, records]), reused when shapes repeat
         self._busy = [None, None]       # per slot: event recorded after the H2D copies that READ its pinned buffers
         self._slot = 0
         self._next = None
@@ -269,7 +274,7 @@ class DevicePrefetcher:
         if buf is None or buf.shape != like.shape or buf.dtype != like.dtype:
             buf = torch.empty(like.shape, dtype=like.dtype, pin_memory=True)
             if cur is None:
-                self._pin[slot] = [None, None]
+                self._pin[slot] = [None, None, None]
             self._pin[slot][which] = buf
         return buf
 
@@ -288,13 +293,20 @@ class DevicePrefetcher:
             self._busy[slot].synchronize()              # the upload that last read this slot must be done before the host overwrites it
         pf = self._pinned(slot, 0, frames); pf.copy_(frames)
         pm = self._pinned(slot, 1, masks); pm.copy_(masks)
+        pr = None
+        if self.transforms is not None:
+            from .transforms import RECORD
+            N = frames.shape[0]
+            pr = self._pinned(slot, 2, torch.empty(N * RECORD.itemsize, dtype=torch.uint8))
+            self.transforms.pack([self.transforms.draw() for _ in range(N)], out=pr.numpy().view(RECORD))
         with torch.cuda.stream(self.stream):
             gf = pf.to(self.dev, non_blocking=True)
             gm = pm.to(self.dev, non_blocking=True)
+            gr = pr.to(self.dev, non_blocking=True) if pr is not None else None
             ev = torch.cuda.Event()
             ev.record(self.stream)
         self._busy[slot] = ev
-        self._next = (gf, gm, ev)
+        self._next = (gf, gm, gr, ev)
 
     def __iter__(self):
         return self
@@ -302,9 +314,14 @@ class DevicePrefetcher:
     def __next__(self):
         if self._next is None:
             raise StopIteration
-        gf, gm, ev = self._next
+        gf, gm, gr, ev = self._next
         cur = torch.cuda.current_stream(self.dev)
         cur.wait_event(ev)
         gf.record_stream(cur); gm.record_stream(cur)
         self._stage()                                   # upload of the following batch overlaps the consumer's step
+        if self.transforms is not None:
+            from .transforms import augment_u8
+            gr.record_stream(cur)
+            t = self.transforms
+            return augment_u8(gf, gm, gr, t.out_hw(gf.shape[1], gf.shape[2]), t.mean, t.std)
         return preprocess_uint8(gf, self.mean, self.std), gm
