@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--class-weights", default="none", choices=["none", "median_frequency", "enet"],
+                    help="class-weighted loss, weights from one pass over the training masks (cvk.class_weights)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -46,7 +49,10 @@ def main():
     net = cvk.get_model(a.net, 3, 12).to(dev)
     opt = torch.optim.AdamW(net.parameters(), lr=a.lr)
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=a.iters, epochs=a.epochs)
-    loss_fn = cvk.CrossEntropyLoss()
+    weight = None
+    if a.class_weights != "none":
+        weight = cvk.class_weights((m for _, m in synthetic_camvid(a.iters, a.b, 1)), 12, method=a.class_weights, device=dev)
+    loss_fn = cvk.CrossEntropyLoss(weight=weight, label_smoothing=a.label_smoothing)
     train_tf, valid_tf = transforms.train_transforms(), transforms.valid_transforms()
     for epoch in range(1, a.epochs + 1):
         net.train()

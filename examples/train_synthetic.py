@@ -28,6 +28,9 @@ def main():
     ap.add_argument("-wd", type=float, default=0.0)            # train.py:25
     ap.add_argument("--flat-adamw", action="store_true", help="one fused optimizer kernel (cvk.FlatAdamW)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--class-weights", default="none", choices=["none", "median_frequency", "enet"],
+                    help="class-weighted loss, weights from the training masks (cvk.class_weights)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
     ap.add_argument("--split-operands", type=int, default=0, choices=[0, 2, 3],
                     help="opt-in for fp32: matrix products on the 16-bit matrix pipe with split fp32 operands (cvk.set_split_operands; 2 = fp16 x 2)")
     a = ap.parse_args()
@@ -47,12 +50,12 @@ def main():
     opt = cvk.FlatAdamW(net, lr=a.lr, weight_decay=a.wd) if a.flat_adamw else \
         torch.optim.AdamW(net.parameters(), lr=a.lr, weight_decay=a.wd)     # train.py:100
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=a.iters, epochs=a.epochs)  # :103-104
-    loss_fn = cvk.CrossEntropyLoss()                                        # train.py:105
-
     g = torch.Generator().manual_seed(1234 + rank)
     # a fixed synthetic "dataset": uint8 HWC frames like cv2 delivers + 12-class masks; smooth blobs so it is learnable
     base = torch.rand(a.iters, a.b, 45, 60, generator=g)
     masks = torch.nn.functional.interpolate((base * 12).floor().clamp(0, 11), size=(360, 480), mode="nearest").long()
+    weight = None if a.class_weights == "none" else cvk.class_weights(masks, 12, method=a.class_weights, device=dev)
+    loss_fn = cvk.CrossEntropyLoss(weight=weight, label_smoothing=a.label_smoothing)   # train.py:105
     for epoch in range(1, a.epochs + 1):
         net.train()
         t0 = time.time()

@@ -439,6 +439,39 @@ int cvk_softmax_ce_fwd(const float* logits, int ld, const int64_t* target, float
 int cvk_softmax_ce_bwd(const float* logits, int ld, const int64_t* target, const float* loss3, const float* grad_out,
                        float scale, float* dlogits, int ld_d, int M, int C, int ignore_index, void* stream);
 
+/* ---- softmax cross-entropy with class weights, label smoothing and a reduction (nn.CrossEntropyLoss(weight=w,
+ * label_smoothing=eps, reduction=...)) ------------------------------------------------------------------------------
+ * logits: dense NHWC rows [M][ld] (ld >= C, 0 < C <= 128), target int64 [M] (DEVICE).  weight: DEVICE float [C], nullable (all
+ * ones); label_smoothing eps in [0, 1]; reduction CVK_REDUCTION_*.  With lse = log sum_c exp(x[c]) and t = target, a pixel's
+ *   loss = (1 - eps) w[t] (lse - x[t]) + (eps / C) sum_c w[c] (lse - x[c]);
+ * mean = sum of the losses / sum of w[t] (0/0 = NaN when every pixel is ignored), sum = their sum.  Pixels whose target equals
+ * ignore_index count nowhere and get a zero gradient; any other target outside [0, C) makes the loss NaN and is counted, as in
+ * cvk_softmax_ce_fwd.  fwd: `part` is DEVICE scratch of cvk_ce_ex_part_floats(M) floats; loss is DEVICE float[4]: loss[0] = the
+ * reduced loss (reduction none: the sum), loss[1] = valid pixels, loss[2] = out-of-range targets, loss[3] = the backward's divisor
+ * (mean: sum of w[t]; sum / none: 1).  loss_px: DEVICE float [M], per-pixel loss (0 where ignored, NaN where out of range);
+ * required for reduction none, nullable otherwise.  No allocation, no float atomics (fixed-order fp64 finish), no host sync.
+ * bwd: dlogits [M][ld_d] = g (softmax ((1 - eps) w[t] + (eps / C) sum_c w[c]) - (1 - eps) w[t] onehot(t) - (eps / C) w),
+ * g = grad_out * scale / loss4[3]; loss4 is fwd's loss.  grad_out: DEVICE, float [M] for reduction none (required), else one
+ * float (nullable: 1).  Rows of ignored or out-of-range targets and columns [C, ld_d) are written as zeros. */
+#define CVK_REDUCTION_NONE 0
+#define CVK_REDUCTION_MEAN 1
+#define CVK_REDUCTION_SUM 2
+int cvk_ce_ex_part_floats(int M);
+int cvk_softmax_ce_fwd_ex(const float* logits, int ld, const int64_t* target, const float* weight, float label_smoothing,
+                          int reduction, float* part, float* loss, float* loss_px, int M, int C, int ignore_index, void* stream);
+int cvk_softmax_ce_bwd_ex(const float* logits, int ld, const int64_t* target, const float* weight, float label_smoothing,
+                          int reduction, const float* loss4, const float* grad_out, float scale, float* dlogits, int ld_d,
+                          int M, int C, int ignore_index, void* stream);
+
+/* ---- class statistics of label masks (class weights for the loss above; SegNet's median-frequency balancing) ----------
+ * masks: DEVICE [N][HW] of mask_bytes = 1 (uint8) or 8 (int64) per label (cvk_augment_u8's convention); 0 < num_classes <= 256.
+ * Accumulates into DEVICE int64 hist[2 * num_classes + 1] (the caller zeroes it once): hist[c] += pixels of class c,
+ * hist[num_classes + c] += the counted pixels (labels in [0, num_classes)) of every mask in which c occurs, hist[2 * num_classes]
+ * += labels outside [0, num_classes) that are not ignore_index.  Labels equal to ignore_index are skipped.  One workgroup per
+ * mask, integer atomics only (exact, so the result does not depend on the order); no host sync. */
+int cvk_class_histogram(const void* masks, int mask_bytes, int N, int64_t HW, int num_classes, int ignore_index, int64_t* hist,
+                        void* stream);
+
 /* ---- evaluation (train.py:191 argmax; utils.py:162-190 histograms) -------------------------------------------- */
 int cvk_argmax_channels(const float* logits, int ld, int64_t* out, int M, int C, void* stream);
 /* hist int64[3][num_classes] += (intersection, prediction area, label area), pixels with label==ignore skipped */

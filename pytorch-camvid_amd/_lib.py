@@ -177,6 +177,11 @@ SIGNATURES = {
     "cvk_ce_blocks": (c_int, [c_int]),
     "cvk_softmax_ce_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "cvk_softmax_ce_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_float, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "cvk_ce_ex_part_floats": (c_int, [c_int]),
+    "cvk_softmax_ce_fwd_ex": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "cvk_softmax_ce_bwd_ex": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_int, c_vp, c_vp, c_float, c_vp, c_int, c_int, c_int, c_int,
+                                      c_vp]),
+    "cvk_class_histogram": (c_int, [c_vp, c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp]),
     "cvk_argmax_channels": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp]),
     "cvk_confusion_accumulate": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "cvk_preprocess_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_vp]),

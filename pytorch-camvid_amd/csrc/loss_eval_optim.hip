@@ -217,6 +217,272 @@ __global__ __launch_bounds__(256) void k_ce_bwd_rows(const float* __restrict__ l
     }
 }
 
+// ---- cross-entropy with class weights, label smoothing and a reduction (cvk_softmax_ce_fwd_ex / _bwd_ex) ----------------------
+// Same memory scheme as k_ce_fwd / k_ce_bwd (256 pixel rows staged per chunk, one thread per pixel; a thread walks its row in
+// global memory when ld > CE_MAX_LD); the weight vector (all ones when absent) is staged in LDS once per workgroup.
+// For a pixel with target t, lse = log sum exp and W = sum_c w[c]:
+//   loss = (1 - eps) w[t] (lse - x[t]) + (eps / C) sum_c w[c] (lse - x[c])
+//   dx_k = g (softmax_k ((1 - eps) w[t] + (eps / C) W) - (1 - eps) w[t] [k = t] - (eps / C) w[k])
+constexpr int CE_EX_MAX_C = 128;
+
+__device__ __forceinline__ void ce_ex_stage_w(const float* __restrict__ w, float* s_w, int C) {
+    for (int c = threadIdx.x; c < C; c += blockDim.x) s_w[c] = w != nullptr ? w[c] : 1.f;
+}
+
+__device__ __forceinline__ float ce_ex_pixel_loss(const float* p, int C, int t, const float* s_w, float eps) {
+    float mx = p[0];
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(p[c] - mx);
+    const float lse = mx + logf(se);
+    float l = (1.f - eps) * s_w[t] * (lse - p[t]);
+    if (eps != 0.f) {
+        float sm = 0.f;
+        for (int c = 0; c < C; ++c) sm += s_w[c] * (lse - p[c]);
+        l += (eps / (float)C) * sm;
+    }
+    return l;
+}
+
+// o may alias p (every column is read before it is written); columns [C, ld_o) are zeroed
+__device__ __forceinline__ void ce_ex_pixel_grad(const float* p, float* o, int ld_o, int C, int t, const float* s_w, float eps,
+                                                 float wsum, float g) {
+    float mx = p[0];
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(p[c] - mx);
+    const float inv = 1.f / se;
+    const float es = eps / (float)C, wt = (1.f - eps) * s_w[t];
+    const float a = wt + es * wsum;
+    for (int c = 0; c < C; ++c) o[c] = (expf(p[c] - mx) * inv * a - (c == t ? wt : 0.f) - es * s_w[c]) * g;
+    for (int c = C; c < ld_o; ++c) o[c] = 0.f;
+}
+
+// part[b], part[nb + b], part[2 nb + b], part[3 nb + b] = the block's loss sum, divisor sum (w[t] over the valid pixels), valid
+// pixels, out-of-range targets.  loss_px (nullable): per-pixel loss, 0 at ignored pixels and NaN at out-of-range targets.
+__global__ __launch_bounds__(256) void k_ce_fwd_ex(const float* __restrict__ logits, int ld, const int64_t* __restrict__ target,
+                                                  const float* __restrict__ weight, float eps, float* __restrict__ part, int nb,
+                                                  float* __restrict__ loss_px, int M, int C, int ignore_index) {
+    extern __shared__ float lds[];
+    __shared__ float red[4];
+    __shared__ float s_w[CE_EX_MAX_C];
+    ce_ex_stage_w(weight, s_w, C);                                   // visible after the first chunk's barriers
+    const int pitch = ld + 1;
+    float acc = 0.f, div = 0.f, cnt = 0.f, bad = 0.f;
+    const int base = blockIdx.x * CE_ROWS_PER_BLOCK;
+    for (int ch = 0; ch < CE_ROWS_PER_BLOCK / CE_CHUNK; ++ch) {
+        const int m0 = base + ch * CE_CHUNK;
+        if (m0 >= M) break;
+        const int rows = min(CE_CHUNK, M - m0);
+        __syncthreads();
+        ce_chunk_load(logits + (size_t)m0 * ld, lds, rows * ld, ld);
+        __syncthreads();
+        if ((int)threadIdx.x < rows) {
+            const long t = (long)target[m0 + threadIdx.x];
+            float l = 0.f;
+            if (t != (long)ignore_index) {
+                if (t >= 0 && t < C) {
+                    l = ce_ex_pixel_loss(lds + threadIdx.x * pitch, C, (int)t, s_w, eps);
+                    acc += l;
+                    div += s_w[t];
+                    cnt += 1.f;
+                } else {
+                    l = __builtin_nanf("");
+                    bad += 1.f;
+                }
+            }
+            if (loss_px != nullptr) loss_px[m0 + threadIdx.x] = l;
+        }
+    }
+    const float s = block_sum_256(acc, red);
+    const float d = block_sum_256(div, red);
+    const float n = block_sum_256(cnt, red);
+    const float b = block_sum_256(bad, red);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = s;
+        part[nb + blockIdx.x] = d;
+        part[2 * nb + blockIdx.x] = n;
+        part[3 * nb + blockIdx.x] = b;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ce_fwd_ex_rows(const float* __restrict__ logits, int ld, const int64_t* __restrict__ target,
+                                                       const float* __restrict__ weight, float eps, float* __restrict__ part, int nb,
+                                                       float* __restrict__ loss_px, int M, int C, int ignore_index) {
+    __shared__ float red[4];
+    __shared__ float s_w[CE_EX_MAX_C];
+    ce_ex_stage_w(weight, s_w, C);
+    __syncthreads();
+    float acc = 0.f, div = 0.f, cnt = 0.f, bad = 0.f;
+    const int base = blockIdx.x * CE_ROWS_PER_BLOCK;
+    for (int m = base + threadIdx.x; m < min(M, base + CE_ROWS_PER_BLOCK); m += CE_CHUNK) {
+        const long t = (long)target[m];
+        float l = 0.f;
+        if (t != (long)ignore_index) {
+            if (t >= 0 && t < C) {
+                l = ce_ex_pixel_loss(logits + (size_t)m * ld, C, (int)t, s_w, eps);
+                acc += l;
+                div += s_w[t];
+                cnt += 1.f;
+            } else {
+                l = __builtin_nanf("");
+                bad += 1.f;
+            }
+        }
+        if (loss_px != nullptr) loss_px[m] = l;
+    }
+    const float s = block_sum_256(acc, red);
+    const float d = block_sum_256(div, red);
+    const float n = block_sum_256(cnt, red);
+    const float b = block_sum_256(bad, red);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = s;
+        part[nb + blockIdx.x] = d;
+        part[2 * nb + blockIdx.x] = n;
+        part[3 * nb + blockIdx.x] = b;
+    }
+}
+
+// Fixed-order fp64 reduction of the four partial rows: loss[0] = the reduced loss (mean: sum / divisor, 0/0 = NaN; sum and none:
+// the sum; NaN when a target was out of range), loss[1] = valid pixels, loss[2] = out-of-range targets, loss[3] = the backward's
+// divisor (mean: sum of w[t] over the valid pixels; sum and none: 1).
+__global__ __launch_bounds__(256) void k_ce_finish_ex(const float* __restrict__ part, int nb, int reduction, float* loss) {
+    __shared__ double red[4][256];
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < nb; i += 256)
+        for (int k = 0; k < 4; ++k) v[k] += (double)part[k * nb + i];
+    for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o)
+            for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const bool mean = reduction == CVK_REDUCTION_MEAN;
+        loss[0] = red[3][0] > 0.0 ? __builtin_nanf("") : (float)(mean ? red[0][0] / red[1][0] : red[0][0]);
+        loss[1] = (float)red[2][0];
+        loss[2] = (float)red[3][0];
+        loss[3] = mean ? (float)red[1][0] : 1.f;
+    }
+}
+
+// grad_out: one value per pixel for reduction 'none', else a scalar (nullptr = 1).  Ignored pixels and out-of-range targets get a
+// zero gradient row.
+__global__ __launch_bounds__(256) void k_ce_bwd_ex(const float* __restrict__ logits, int ld, const int64_t* __restrict__ target,
+                                                  const float* __restrict__ weight, float eps, int reduction,
+                                                  const float* __restrict__ loss4, const float* __restrict__ grad_out, float scale,
+                                                  float* __restrict__ dl, int ld_d, int M, int C, int ignore_index) {
+    extern __shared__ float lds[];
+    __shared__ float s_w[CE_EX_MAX_C];
+    ce_ex_stage_w(weight, s_w, C);
+    __syncthreads();
+    float wsum = 0.f;
+    for (int c = 0; c < C; ++c) wsum += s_w[c];
+    const bool per_px = reduction == CVK_REDUCTION_NONE;
+    const float g0 = (per_px || grad_out == nullptr ? 1.f : *grad_out) * scale / loss4[3];
+    const int pitch = ld + 1;
+    const int base = blockIdx.x * CE_ROWS_PER_BLOCK;
+    for (int ch = 0; ch < CE_ROWS_PER_BLOCK / CE_CHUNK; ++ch) {
+        const int m0 = base + ch * CE_CHUNK;
+        if (m0 >= M) break;
+        const int rows = min(CE_CHUNK, M - m0);
+        __syncthreads();
+        ce_chunk_load(logits + (size_t)m0 * ld, lds, rows * ld, ld);
+        __syncthreads();
+        if ((int)threadIdx.x < rows) {
+            float* p = lds + threadIdx.x * pitch;
+            const long t = (long)target[m0 + threadIdx.x];
+            if (t == (long)ignore_index || t < 0 || t >= C) {
+                for (int c = 0; c < ld; ++c) p[c] = 0.f;
+            } else {
+                const float g = per_px ? g0 * grad_out[m0 + threadIdx.x] : g0;
+                ce_ex_pixel_grad(p, p, ld, C, (int)t, s_w, eps, wsum, g);
+            }
+        }
+        __syncthreads();
+        if (ld_d == ld) {
+            ce_chunk_store(dl + (size_t)m0 * ld_d, lds, rows * ld, ld);
+        } else {
+            for (int f = threadIdx.x; f < rows * ld_d; f += CE_CHUNK) {
+                const int r = f / ld_d, c = f - r * ld_d;
+                dl[(size_t)m0 * ld_d + f] = c < ld ? lds[r * pitch + c] : 0.f;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ce_bwd_ex_rows(const float* __restrict__ logits, int ld, const int64_t* __restrict__ target,
+                                                       const float* __restrict__ weight, float eps, int reduction,
+                                                       const float* __restrict__ loss4, const float* __restrict__ grad_out, float scale,
+                                                       float* __restrict__ dl, int ld_d, int M, int C, int ignore_index) {
+    __shared__ float s_w[CE_EX_MAX_C];
+    ce_ex_stage_w(weight, s_w, C);
+    __syncthreads();
+    float wsum = 0.f;
+    for (int c = 0; c < C; ++c) wsum += s_w[c];
+    const bool per_px = reduction == CVK_REDUCTION_NONE;
+    const float g0 = (per_px || grad_out == nullptr ? 1.f : *grad_out) * scale / loss4[3];
+    for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
+        float* o = dl + (size_t)m * ld_d;
+        const long t = (long)target[m];
+        if (t == (long)ignore_index || t < 0 || t >= C) {
+            for (int c = 0; c < ld_d; ++c) o[c] = 0.f;
+            continue;
+        }
+        const float g = per_px ? g0 * grad_out[m] : g0;
+        ce_ex_pixel_grad(logits + (size_t)m * ld, o, ld_d, C, (int)t, s_w, eps, wsum, g);
+    }
+}
+
+// Class statistics of label masks: one workgroup per mask.  Every wave counts into its own LDS histogram (integer atomics:
+// exact, so the totals do not depend on the order); the folded per-mask counts go to the device counters with 64-bit integer
+// atomics: hist[c] += pixels of class c, hist[C + c] += the mask's counted pixels if c occurs in it, hist[2C] += labels outside
+// [0, C) that are not ignore_index.
+constexpr int HIST_THREADS = 1024, HIST_WAVES = HIST_THREADS / 64, HIST_MAX_C = 256;
+
+__global__ __launch_bounds__(HIST_THREADS) void k_class_hist(const void* __restrict__ masks, int mask_bytes, int64_t hw, int C,
+                                                             int ignore_index, unsigned long long* __restrict__ hist) {
+    __shared__ unsigned int h[HIST_WAVES * HIST_MAX_C];
+    __shared__ unsigned long long cnt[HIST_MAX_C];
+    __shared__ unsigned long long s_tot;
+    __shared__ unsigned int s_bad;
+    for (int i = threadIdx.x; i < HIST_WAVES * C; i += HIST_THREADS) h[i] = 0u;
+    if (threadIdx.x == 0) s_bad = 0u;
+    __syncthreads();
+    unsigned int* mine = h + (threadIdx.x >> 6) * C;
+    const size_t base = (size_t)blockIdx.x * hw;
+    unsigned int bad = 0u;
+    for (int64_t i = threadIdx.x; i < hw; i += HIST_THREADS) {
+        const long l = mask_bytes == 1 ? (long)static_cast<const uint8_t*>(masks)[base + i]
+                                       : (long)static_cast<const int64_t*>(masks)[base + i];
+        if (l == (long)ignore_index) continue;
+        if (l >= 0 && l < C) atomicAdd(&mine[l], 1u);
+        else ++bad;
+    }
+    if (bad) atomicAdd(&s_bad, bad);
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += HIST_THREADS) {
+        unsigned long long n = 0;
+        for (int k = 0; k < HIST_WAVES; ++k) n += h[k * C + c];
+        cnt[c] = n;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = 0;
+        for (int c = 0; c < C; ++c) tot += cnt[c];
+        s_tot = tot;
+        if (s_bad) atomicAdd(&hist[2 * C], (unsigned long long)s_bad);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += HIST_THREADS) {
+        if (cnt[c]) {
+            atomicAdd(&hist[c], cnt[c]);
+            atomicAdd(&hist[C + c], s_tot);
+        }
+    }
+}
+
 __global__ void k_argmax(const float* __restrict__ logits, int ld, int64_t* __restrict__ out, int M, int C) {
     for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
         const float* p = logits + (size_t)m * ld;
@@ -487,6 +753,57 @@ extern "C" int cvk_softmax_ce_bwd(const float* logits, int ld, const int64_t* ta
         hipLaunchKernelGGL(k_ce_bwd_rows, dim3(cvk_cdiv(M, 256) < 8192 ? cvk_cdiv(M, 256) : 8192), dim3(256), 0, (hipStream_t)stream, logits, ld,
                            target, loss3, grad_out, scale, dlogits, ld_d, M, C, ignore_index);
     CVK_LAUNCH_RETURN("cvk_softmax_ce_bwd");
+}
+
+extern "C" int cvk_ce_ex_part_floats(int M) { return M > 0 ? 4 * cvk_ce_blocks(M) : 0; }
+
+static bool ce_ex_args_ok(int M, int C, int ld, float eps, int reduction) {
+    return M > 0 && C > 0 && C <= CE_EX_MAX_C && ld >= C && eps >= 0.f && eps <= 1.f &&
+           (reduction == CVK_REDUCTION_NONE || reduction == CVK_REDUCTION_MEAN || reduction == CVK_REDUCTION_SUM);
+}
+
+extern "C" int cvk_softmax_ce_fwd_ex(const float* logits, int ld, const int64_t* target, const float* weight, float label_smoothing,
+                                     int reduction, float* part, float* loss, float* loss_px, int M, int C, int ignore_index,
+                                     void* stream) {
+    CVK_CHECK_ARG(logits && target && part && loss, "cvk_softmax_ce_fwd_ex: null pointer");
+    CVK_CHECK_ARG(ce_ex_args_ok(M, C, ld, label_smoothing, reduction), "cvk_softmax_ce_fwd_ex: bad arguments");
+    CVK_CHECK_ARG(reduction != CVK_REDUCTION_NONE || loss_px, "cvk_softmax_ce_fwd_ex: reduction none needs loss_px");
+    const int nb = cvk_ce_blocks(M);
+    hipStream_t s = (hipStream_t)stream;
+    if (ld <= CE_MAX_LD)
+        hipLaunchKernelGGL(k_ce_fwd_ex, dim3(nb), dim3(256), CE_CHUNK * (ld + 1) * sizeof(float), s, logits, ld, target, weight,
+                           label_smoothing, part, nb, loss_px, M, C, ignore_index);
+    else
+        hipLaunchKernelGGL(k_ce_fwd_ex_rows, dim3(nb), dim3(256), 0, s, logits, ld, target, weight, label_smoothing, part, nb, loss_px, M,
+                           C, ignore_index);
+    hipLaunchKernelGGL(k_ce_finish_ex, dim3(1), dim3(256), 0, s, part, nb, reduction, loss);
+    CVK_LAUNCH_RETURN("cvk_softmax_ce_fwd_ex");
+}
+
+extern "C" int cvk_softmax_ce_bwd_ex(const float* logits, int ld, const int64_t* target, const float* weight, float label_smoothing,
+                                     int reduction, const float* loss4, const float* grad_out, float scale, float* dlogits, int ld_d,
+                                     int M, int C, int ignore_index, void* stream) {
+    CVK_CHECK_ARG(logits && target && loss4 && dlogits, "cvk_softmax_ce_bwd_ex: null pointer");
+    CVK_CHECK_ARG(ce_ex_args_ok(M, C, ld, label_smoothing, reduction) && ld_d >= C, "cvk_softmax_ce_bwd_ex: bad arguments");
+    CVK_CHECK_ARG(reduction != CVK_REDUCTION_NONE || grad_out, "cvk_softmax_ce_bwd_ex: reduction none needs a per-pixel grad_out");
+    hipStream_t s = (hipStream_t)stream;
+    if (ld <= CE_MAX_LD)
+        hipLaunchKernelGGL(k_ce_bwd_ex, dim3(cvk_ce_blocks(M)), dim3(256), CE_CHUNK * (ld + 1) * sizeof(float), s, logits, ld, target,
+                           weight, label_smoothing, reduction, loss4, grad_out, scale, dlogits, ld_d, M, C, ignore_index);
+    else
+        hipLaunchKernelGGL(k_ce_bwd_ex_rows, dim3(cvk_cdiv(M, 256) < 8192 ? cvk_cdiv(M, 256) : 8192), dim3(256), 0, s, logits, ld, target,
+                           weight, label_smoothing, reduction, loss4, grad_out, scale, dlogits, ld_d, M, C, ignore_index);
+    CVK_LAUNCH_RETURN("cvk_softmax_ce_bwd_ex");
+}
+
+extern "C" int cvk_class_histogram(const void* masks, int mask_bytes, int N, int64_t HW, int num_classes, int ignore_index,
+                                   int64_t* hist, void* stream) {
+    CVK_CHECK_ARG(masks && hist, "cvk_class_histogram: null pointer");
+    CVK_CHECK_ARG((mask_bytes == 1 || mask_bytes == 8) && N > 0 && HW > 0 && num_classes > 0 && num_classes <= HIST_MAX_C,
+                  "cvk_class_histogram: bad arguments");
+    hipLaunchKernelGGL(k_class_hist, dim3(N), dim3(HIST_THREADS), 0, (hipStream_t)stream, masks, mask_bytes, HW, num_classes,
+                       ignore_index, (unsigned long long*)hist);
+    CVK_LAUNCH_RETURN("cvk_class_histogram");
 }
 
 extern "C" int cvk_argmax_channels(const float* logits, int ld, int64_t* out, int M, int C, void* stream) {

@@ -1,6 +1,9 @@
 """Loss / evaluation operators of the hot path as autograd-aware callables on HIP tensors.
 
-  CrossEntropyLoss  <- nn.CrossEntropyLoss() of reference train.py:105 (mean over N*H*W, no ignored class)
+  CrossEntropyLoss  <- nn.CrossEntropyLoss() of reference train.py:105 (mean over N*H*W, no ignored class); also torch's
+                       weight / reduction / label_smoothing options
+  ClassFrequencyMeter, class_weights
+                    <- median-frequency (SegNet) / ENet class weights from device-side class histograms of the masks
   argmax_channels   <- preds.argmax(dim=1) of train.py:191
   ConfusionMeter    <- utils.intersect_and_union / mean_iou (utils.py:162-228) accumulated on device, with the
                        np.float crash (utils.py:210) and the per-batch-sum bug of train.py:192-206 not reproduced
@@ -73,24 +76,111 @@ class _CrossEntropy(torch.autograd.Function):
         return d.permute(0, 3, 1, 2), None, None, None
 
 
-class CrossEntropyLoss(nn.Module):
-    """Drop-in for the reference's `nn.CrossEntropyLoss()` (train.py:105): reduction='mean', no class weights, no label
-    smoothing; targets are int64 class indices in [0, C) or `ignore_index` (default -100 as in torch: such pixels are
-    left out of the mean and get no gradient).  Any other out-of-range target makes the loss NaN — torch raises a
-    device-side assert there; raising here would need a host sync in every step — and `last_ce_status()` reports the
-    count.  `grad_scale` multiplies the backward only (data-parallel training can fold 1/world_size in here)."""
+REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}      # include/cvk.h CVK_REDUCTION_*
 
-    def __init__(self, grad_scale=1.0, ignore_index=-100):
+
+class _CrossEntropyEx(torch.autograd.Function):
+    """Class weights / label smoothing / reduction 'none' | 'sum' (cvk_softmax_ce_fwd_ex / _bwd_ex)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, grad_scale, ignore_index, reduction, label_smoothing):
+        lib = _lib.load()
+        if not logits.is_cuda:
+            raise RuntimeError("pytorch_camvid_amd.CrossEntropyLoss needs HIP tensors (no CPU fallback)")
+        if logits.dtype != torch.float32 or target.dtype != torch.int64:
+            raise RuntimeError(f"expected float32 logits and int64 target, got {logits.dtype} / {target.dtype}")
+        N, C, H, W = logits.shape
+        if tuple(target.shape) != (N, H, W):
+            raise ValueError(f"Expected target size {[N, H, W]}, got {list(target.shape)}")
+        if weight is not None:
+            if weight.dim() != 1 or weight.numel() != C:
+                raise RuntimeError(f"weight tensor should be defined either for all {C} classes or no classes but got weight tensor "
+                                   f"of shape: {list(weight.shape)}")
+            if weight.device != logits.device:
+                raise RuntimeError(f"weight is on {weight.device} but the logits are on {logits.device} (no implicit copy: the loss "
+                                   "stays capturable); move the loss module with .to(device)")
+            if weight.dtype != torch.float32:
+                raise RuntimeError(f"expected a float32 weight, got {weight.dtype}")
+            weight = weight.detach().contiguous()
+        red = REDUCTIONS[reduction]
+        lg, ld = _as_nhwc(logits)
+        tg = target.contiguous()
+        M = N * H * W
+        part = torch.empty(lib.cvk_ce_ex_part_floats(M), device=logits.device, dtype=torch.float32)
+        loss4 = torch.empty(4, device=logits.device, dtype=torch.float32)   # loss | valid pixels | out-of-range targets | divisor
+        px = torch.empty((N, H, W), device=logits.device, dtype=torch.float32) if red == 0 else None
+        wp = weight.data_ptr() if weight is not None else None
+        from . import engine
+        engine._timed(None, "k_ce_fwd_ex", 4.0 * M * ld + 8.0 * M, lambda: check(
+            lib.cvk_softmax_ce_fwd_ex(lg.data_ptr(), ld, tg.data_ptr(), wp, float(label_smoothing), red, part.data_ptr(), loss4.data_ptr(),
+                                      px.data_ptr() if px is not None else None, M, C, int(ignore_index), _stream(logits)),
+            "cvk_softmax_ce_fwd_ex"), "byte")
+        ctx.save_for_backward(lg, tg, loss4, weight)
+        ctx.meta = (N, C, H, W, ld, grad_scale, int(ignore_index), red, float(label_smoothing))
+        _CrossEntropy.last_status = loss4
+        return px if px is not None else loss4[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        lg, tg, loss4, weight = ctx.saved_tensors
+        N, C, H, W, ld, grad_scale, ignore_index, red, eps = ctx.meta
+        M = N * H * W
+        d = torch.empty((N, H, W, C), device=lg.device, dtype=torch.float32)
+        g = gout.contiguous()
+        wp = weight.data_ptr() if weight is not None else None
+        from . import engine
+        engine._timed(None, "k_ce_bwd_ex", 4.0 * M * ld + 8.0 * M + 4.0 * M * C, lambda: check(
+            lib.cvk_softmax_ce_bwd_ex(lg.data_ptr(), ld, tg.data_ptr(), wp, eps, red, loss4.data_ptr(), g.data_ptr(), float(grad_scale),
+                                      d.data_ptr(), C, M, C, ignore_index, _stream(lg)), "cvk_softmax_ce_bwd_ex"), "byte")
+        return d.permute(0, 3, 1, 2), None, None, None, None, None, None
+
+
+def _check_ce_options(weight, reduction, label_smoothing):
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"{reduction} is not a valid value for reduction")
+    if not 0.0 <= float(label_smoothing) <= 1.0:
+        raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}")
+    if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dim() != 1):
+        raise ValueError("weight must be a 1-D tensor of one value per class")
+
+
+def _ce(logits, target, weight, grad_scale, ignore_index, reduction, label_smoothing):
+    if weight is None and reduction == "mean" and float(label_smoothing) == 0.0:
+        return _CrossEntropy.apply(logits, target, grad_scale, ignore_index)       # the default loss: k_ce_fwd -> k_ce_finish -> k_ce_bwd
+    return _CrossEntropyEx.apply(logits, target, weight, grad_scale, ignore_index, reduction, float(label_smoothing))
+
+
+class CrossEntropyLoss(nn.Module):
+    """Drop-in for the reference's `nn.CrossEntropyLoss()` (train.py:105); targets are int64 class indices in [0, C) or
+    `ignore_index` (default -100 as in torch: such pixels are left out of the loss and get no gradient).  Any other
+    out-of-range target makes the loss NaN — torch raises a device-side assert there; raising here would need a host sync
+    in every step — and `last_ce_status()` reports the count.  `grad_scale` multiplies the backward only (data-parallel
+    training can fold 1/world_size in here).
+    Keyword options as in torch: `weight` (float32 [C] on the logits' device; a registered buffer, so it follows .to() and
+    is in state_dict), `reduction` ('mean' divides by the sum of the targets' weights, 'sum', or 'none' for an [N, H, W]
+    loss map) and `label_smoothing` in [0, 1].  With all three at their defaults the loss runs the unweighted kernels."""
+
+    def __init__(self, grad_scale=1.0, ignore_index=-100, *, weight=None, reduction="mean", label_smoothing=0.0):
         super().__init__()
+        _check_ce_options(weight, reduction, label_smoothing)
         self.grad_scale = grad_scale
         self.ignore_index = ignore_index
+        self.reduction = reduction
+        self.label_smoothing = float(label_smoothing)
+        self.register_buffer("weight", weight)
 
     def forward(self, logits, target):
-        return _CrossEntropy.apply(logits, target, self.grad_scale, self.ignore_index)
+        return _ce(logits, target, self.weight, self.grad_scale, self.ignore_index, self.reduction, self.label_smoothing)
 
 
-def cross_entropy(logits, target, ignore_index=-100):
-    return _CrossEntropy.apply(logits, target, 1.0, ignore_index)
+def cross_entropy(logits, target, weight=None, ignore_index=-100, reduction="mean", label_smoothing=0.0):
+    """torch.nn.functional.cross_entropy's options on the HIP kernels.  An int in the third position is read as
+    `ignore_index`, what that position meant before `weight` existed."""
+    if isinstance(weight, int) and not isinstance(weight, bool):
+        weight, ignore_index = None, weight
+    _check_ce_options(weight, reduction, label_smoothing)
+    return _ce(logits, target, weight, 1.0, ignore_index, reduction, label_smoothing)
 
 
 def last_ce_status():
@@ -99,7 +189,7 @@ def last_ce_status():
     st = getattr(_CrossEntropy, "last_status", None)
     if st is None:
         raise RuntimeError("no cross-entropy forward has run yet")
-    _, valid, bad = st.cpu().tolist()
+    _, valid, bad = st.cpu().tolist()[:3]
     if bad:
         raise IndexError(f"Target out of bounds: {int(bad)} pixels have a class index outside [0, C) that is not ignore_index")
     return int(valid), int(bad)
@@ -152,6 +242,91 @@ class ConfusionMeter:
         prec = (h[0] / (h[1] + 1e-15))[valid].mean()
         rec = (h[0] / (h[2] + 1e-15))[valid].mean()
         return float(prec), float(rec)
+
+
+WEIGHT_METHODS = ("median_frequency", "enet")
+
+
+def weights_from_counts(pixels, image_pixels, method="median_frequency"):
+    """Class weights from per-class counts (numpy float64 [C]); classes with no pixel get weight 0.
+      median_frequency (SegNet, Eigen & Fergus): freq(c) = pixels[c] / image_pixels[c] (the counted pixels of the images that
+        contain c), w_c = median over the present classes of freq / freq(c);
+      enet (ENet, Paszke et al.): p_c = pixels[c] / all counted pixels, w_c = 1 / ln(1.02 + p_c)."""
+    import numpy as np
+    pix = np.asarray(pixels, dtype=np.float64)
+    img = np.asarray(image_pixels, dtype=np.float64)
+    present = pix > 0
+    w = np.zeros_like(pix)
+    if not present.any():
+        return w
+    if method == "median_frequency":
+        freq = pix[present] / img[present]
+        w[present] = np.median(freq) / freq
+    elif method == "enet":
+        w[present] = 1.0 / np.log(1.02 + pix[present] / pix.sum())
+    else:
+        raise ValueError(f"method must be one of {WEIGHT_METHODS}, got {method!r}")
+    return w
+
+
+class ClassFrequencyMeter:
+    """Device-side class statistics of label masks for class weights (`weights()`), one launch per batch and no host sync
+    until `weights()` / `counts()`.  Labels equal to `ignore_index` are skipped; labels outside [0, num_classes) are counted
+    apart (`counts()[2]`).  The default counts every class, as the reference's loss trains Void (train.py:105)."""
+
+    def __init__(self, num_classes=12, ignore_index=-100, device="cuda"):
+        self.num_classes, self.ignore_index = num_classes, ignore_index
+        self.hist = torch.zeros(2 * num_classes + 1, device=device, dtype=torch.int64)
+
+    def reset(self):
+        self.hist.zero_()
+
+    def update(self, masks):
+        """masks: uint8 or int64 HIP tensor [N, H, W] (or one [H, W] mask)."""
+        lib = _lib.load()
+        m = masks.contiguous()
+        if m.dtype not in (torch.uint8, torch.int64) or m.dim() not in (2, 3) or not m.is_cuda:
+            raise ValueError("expected uint8 or int64 HIP masks of shape [N, H, W] or [H, W]")
+        if m.device != self.hist.device:
+            raise ValueError(f"masks are on {m.device}, the meter on {self.hist.device}")
+        if m.dim() == 2:
+            m = m.unsqueeze(0)
+        N = m.shape[0]
+        if m.numel() == 0:
+            return
+        check(lib.cvk_class_histogram(m.data_ptr(), m.element_size(), N, m.numel() // N, self.num_classes, int(self.ignore_index),
+                                      self.hist.data_ptr(), _stream(m)), "cvk_class_histogram")
+
+    def counts(self):
+        """(pixels per class, counted pixels of the images containing each class, labels out of range) — one device->host copy."""
+        h = self.hist.cpu().numpy()
+        K = self.num_classes
+        return h[:K].copy(), h[K:2 * K].copy(), int(h[2 * K])
+
+    def weights(self, method="median_frequency"):
+        """float32 [num_classes] class weights on the meter's device (see `weights_from_counts`)."""
+        if method not in WEIGHT_METHODS:
+            raise ValueError(f"method must be one of {WEIGHT_METHODS}, got {method!r}")
+        pix, img, _ = self.counts()
+        return torch.tensor(weights_from_counts(pix, img, method), dtype=torch.float32).to(self.hist.device)
+
+
+def class_weights(mask_batches, num_classes, ignore_index=-100, method="median_frequency", device="cuda"):
+    """Class weights of a data set: `mask_batches` yields uint8 or int64 masks [N, H, W] (HIP tensors, or CPU tensors / numpy
+    arrays, which are uploaded to `device`).  Returns float32 [num_classes] on the device, for CrossEntropyLoss(weight=...)."""
+    if method not in WEIGHT_METHODS:
+        raise ValueError(f"method must be one of {WEIGHT_METHODS}, got {method!r}")
+    meter = None
+    for m in mask_batches:
+        m = torch.as_tensor(m)
+        if not m.is_cuda:
+            m = m.to(device)
+        if meter is None:
+            meter = ClassFrequencyMeter(num_classes, ignore_index, m.device)
+        meter.update(m)
+    if meter is None:
+        raise ValueError("class_weights(): no batches")
+    return meter.weights(method)
 
 
 # reference conf/settings.py:8-9 (BGR order, as cv2 decodes)
