@@ -4,6 +4,7 @@ driving the MI355X-native network.  Frames are synthesised at the network's inpu
 augmentation of 960x720 frames on the device see examples/train_augmented.py.  Everything from the tensors onward is the product path.
 
   python examples/train_synthetic.py --net unet --epochs 2 --iters 20 -b 8
+  python examples/train_synthetic.py --graphed      # each iteration (step, AdamW, log line) as ONE graph replay
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_synthetic.py   # data parallel
 """
 import argparse
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20, help="synthetic batches per epoch")
     ap.add_argument("-wd", type=float, default=0.0)            # train.py:25
     ap.add_argument("--flat-adamw", action="store_true", help="one fused optimizer kernel (cvk.FlatAdamW)")
+    ap.add_argument("--graphed", action="store_true", help="the whole iteration (forward, loss, backward, FlatAdamW, the log line) as one "
+                    "captured graph (cvk.GraphedStep); the log is read once per epoch.  Implies --flat-adamw")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--class-weights", default="none", choices=["none", "median_frequency", "enet"],
                     help="class-weighted loss, weights from the training masks (cvk.class_weights)")
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--split-operands", type=int, default=0, choices=[0, 2, 3],
                     help="opt-in for fp32: matrix products on the 16-bit matrix pipe with split fp32 operands (cvk.set_split_operands; 2 = fp16 x 2)")
     a = ap.parse_args()
+    a.flat_adamw = a.flat_adamw or a.graphed
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -56,6 +60,7 @@ def main():
     masks = torch.nn.functional.interpolate((base * 12).floor().clamp(0, 11), size=(360, 480), mode="nearest").long()
     weight = None if a.class_weights == "none" else cvk.class_weights(masks, 12, method=a.class_weights, device=dev)
     loss_fn = cvk.CrossEntropyLoss(weight=weight, label_smoothing=a.label_smoothing)   # train.py:105
+    step = None
     for epoch in range(1, a.epochs + 1):
         net.train()
         t0 = time.time()
@@ -64,6 +69,12 @@ def main():
             frames = ((m.unsqueeze(-1) * torch.tensor([20, 15, 10], device=dev)) % 256 +
                       torch.randint(0, 30, (a.b, 360, 480, 3), device=dev)).clamp(0, 255).to(torch.uint8)
             images = cvk.preprocess_uint8(frames)                           # transforms.ToTensor + Normalize on device
+            if a.graphed:
+                if step is None:                                            # capture once, on the first batch of the geometry
+                    step = cvk.GraphedStep(net, loss_fn, images, m, allow_grad_sync=world > 1, optimizer=opt, scheduler=sched,
+                                           log_capacity=a.iters)
+                loss = step.replay(images, m)                               # train.py:124-134 + the log line, one launch
+                continue
             opt.zero_grad()                                                 # train.py:124
             preds = model(images)                                           # :128
             loss = loss_fn(preds, m)                                        # :130
@@ -71,6 +82,13 @@ def main():
             opt.step(); sched.step()                                        # :133-134
         torch.cuda.synchronize()
         dt = time.time() - t0
+        if step is not None and rank == 0:
+            rows, dropped = step.log()                                      # the epoch's per-iteration lines: one D2H copy
+            for i, (l, lr, beta, gw, gb) in enumerate(rows):                # train.py:135-143 + utils.visulaize_lastlayer
+                print(("Training Epoch:{epoch} [{trained_samples}/{total_samples}] Lr:{lr:0.6f} Loss:{loss:0.4f} Beta1:{beta:0.4f} "
+                       "grad_norm2_weights:{gw:0.4e} grad_norm2_bias:{gb:0.4e}").format(
+                    epoch=epoch, trained_samples=(dropped + i + 1) * a.b, total_samples=a.iters * a.b, lr=lr, loss=l, beta=beta,
+                    gw=gw, gb=gb))
         if rank == 0:
             print(f"epoch {epoch}: loss {loss.item():.4f}  lr {sched.get_last_lr()[0]:.6f}  "
                   f"{world * a.b * a.iters / dt:.1f} img/s (incl. data synthesis + optimizer)")

@@ -509,6 +509,29 @@ int cvk_augment_u8(const uint8_t* frames, const void* masks, int mask_bytes, int
 int cvk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 
+/* The same step with its scalars read from DEVICE memory, so that a captured graph (GraphedStep(optimizer=...)) picks up the
+ * scheduler's lr / beta1 of every replay: the host fills a cvk_adamw_hyper with cvk_adamw_hyper_fill (host function, no launch;
+ * the bias corrections bc1 = 1 - beta1^step and bc2_sqrt = sqrt(1 - beta2^step) come from the same host expressions
+ * cvk_adamw_step evaluates) and copies it to the device outside the graph.  cvk_adamw_step_dev has k_adamw's arithmetic in its
+ * operation order: the update is bitwise the one cvk_adamw_step makes with the same values. */
+typedef struct cvk_adamw_hyper {
+    float lr, beta1, beta2, eps, weight_decay;
+    float bc1;                   /* 1 - beta1^step */
+    float bc2_sqrt;              /* sqrt(1 - beta2^step) */
+} cvk_adamw_hyper;
+int cvk_adamw_hyper_fill(float lr, float beta1, float beta2, float eps, float weight_decay, int step, cvk_adamw_hyper* out);
+int cvk_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                       const cvk_adamw_hyper* hyper, void* stream);
+
+/* ---- the per-iteration training log (train.py:133-143 print of loss / lr / Beta1; utils.visulaize_lastlayer utils.py:33-36) -------
+ * One single-workgroup launch appends the row [loss, lr, beta1, ||gw||_2, ||gb||_2] (fp32) to a DEVICE ring of `capacity` rows of 5
+ * floats at row counter % capacity, then increments *counter (DEVICE int64).  loss: DEVICE scalar; hyper: DEVICE record (lr and
+ * beta1 of the step); gw / gb: DEVICE gradients of nw / nb floats.  The norms are sums of squares in fp64 in a fixed order (no
+ * atomics: bitwise reproducible), rounded to fp32 after the square root.  No allocation and no synchronisation: the call can be
+ * captured in a graph. */
+int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb, float* ring,
+                 int capacity, int64_t* counter, void* stream);
+
 
 /* ================================================================================================================
  * bf16-storage path (BASELINE.json configs[3] "bf16 + MFMA im2col path"; set_conv_precision(net, "bf16")).

@@ -223,6 +223,9 @@ SIGNATURES = {
     "cvk_bilinear_up2_bwd_bf16": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "cvk_zero_frame_bf16": (c_int, [ViewH, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "cvk_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_float, c_float, c_int, c_vp]),
+    "cvk_adamw_hyper_fill": (c_int, [c_float, c_float, c_float, c_float, c_float, c_int, c_vp]),   # out: HOST AdamwHyper
+    "cvk_adamw_step_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "cvk_step_log": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp]),
 }
 
 _lib = None
@@ -232,6 +235,14 @@ _lock = threading.Lock()
 class AugmentRecord(ctypes.Structure):  # include/cvk.h cvk_augment_record (its size: cvk_augment_record_bytes())
     _fields_ = [("flip", ctypes.c_int32), ("ksize", ctypes.c_int32), ("use_lut", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("taps", ctypes.c_float * 12), ("lut", ctypes.c_uint8 * 256)]
+
+
+class AdamwHyper(ctypes.Structure):     # include/cvk.h cvk_adamw_hyper
+    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("bc1", ctypes.c_float), ("bc2_sqrt", ctypes.c_float)]
+
+
+STEP_LOG_COLUMNS = 5                    # cvk_step_log row: loss, lr, beta1, ||gw||_2, ||gb||_2
 
 
 class PackJob(ctypes.Structure):        # include/cvk.h cvk_pack_job

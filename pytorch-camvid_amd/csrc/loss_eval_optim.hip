@@ -515,18 +515,74 @@ __global__ __launch_bounds__(256) void k_confusion(const int64_t* __restrict__ p
         if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
 }
 
+// One AdamW element update (torch.optim.AdamW, decoupled weight decay).  Shared by k_adamw (scalars as kernel arguments) and
+// k_adamw_dev (scalars from a device record): one expression list, so the two cannot round differently.
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, int64_t i, float lr, float b1, float b2, float eps, float wd,
+                                             float bc1, float bc2_sqrt) {
+    const float gi = g[i];
+    float pi = p[i] * (1.f - lr * wd);
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi -= (lr / bc1) * (mi / denom);
+    p[i] = pi;
+}
+
 __global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                         int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = g[i];
-        float pi = p[i] * (1.f - lr * wd);
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        pi -= (lr / bc1) * (mi / denom);
-        p[i] = pi;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+}
+
+// The captured-graph form: the scalars come from a device record the host rewrites before every replay (uniform loads,
+// once per thread, before the loop).
+__global__ void k_adamw_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            int64_t n, const cvk_adamw_hyper* __restrict__ hyper) {
+    const float lr = hyper->lr, b1 = hyper->beta1, b2 = hyper->beta2, eps = hyper->eps, wd = hyper->weight_decay;
+    const float bc1 = hyper->bc1, bc2_sqrt = hyper->bc2_sqrt;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+}
+
+// One row [loss, lr, beta1, ||gw||_2, ||gb||_2] of the per-iteration log into ring[(*counter % capacity) * 5 ..], then ++*counter.
+// One workgroup of 256 threads: thread t sums the squares of elements t, t + 256, ... in fp64, then a fixed tree over LDS.
+constexpr int STEP_LOG_THREADS = 256;
+
+__device__ __forceinline__ double block_sum_sq_f64(const float* __restrict__ x, int n, double* red) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += STEP_LOG_THREADS) {
+        const double xi = (double)x[i];
+        s += xi * xi;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = STEP_LOG_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();                                               // red is reused by the next reduction
+    return r;
+}
+
+__global__ __launch_bounds__(STEP_LOG_THREADS) void k_step_log(const float* __restrict__ loss, const cvk_adamw_hyper* __restrict__ hyper,
+                                                               const float* __restrict__ gw, int nw, const float* __restrict__ gb, int nb,
+                                                               float* __restrict__ ring, int capacity, int64_t* __restrict__ counter) {
+    __shared__ double red[STEP_LOG_THREADS];
+    const double sw = block_sum_sq_f64(gw, nw, red);
+    const double sb = block_sum_sq_f64(gb, nb, red);
+    if (threadIdx.x == 0) {
+        const int64_t c = *counter;
+        float* row = ring + (c % capacity) * 5;
+        row[0] = *loss;
+        row[1] = hyper->lr;
+        row[2] = hyper->beta1;
+        row[3] = (float)sqrt(sw);
+        row[4] = (float)sqrt(sb);
+        *counter = c + 1;
     }
 }
 
@@ -822,15 +878,54 @@ extern "C" int cvk_confusion_accumulate(const int64_t* pred, const int64_t* labe
     CVK_LAUNCH_RETURN("cvk_confusion_accumulate");
 }
 
+// bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step), evaluated on the HOST (glibc powf) for both AdamW entry points: a
+// device powf need not round like the host's, and the captured update must be bitwise the eager one.
+static void adamw_bias_corrections(float beta1, float beta2, int step, float* bc1, float* bc2_sqrt) {
+    *bc1 = 1.f - powf(beta1, (float)step);
+    *bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+}
+
+static int adamw_blocks(int64_t n) {
+    const int64_t b = (n + 255) / 256;
+    return (int)(b < 8192 ? b : 8192);
+}
+
 extern "C" int cvk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                               float beta2, float eps, float weight_decay, int step, void* stream) {
     CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, "cvk_adamw_step: bad arguments");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-    const int64_t b = (n + 255) / 256;
-    hipLaunchKernelGGL(k_adamw, dim3((int)(b < 8192 ? b : 8192)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
+    float bc1, bc2s;
+    adamw_bias_corrections(beta1, beta2, step, &bc1, &bc2s);
+    hipLaunchKernelGGL(k_adamw, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
                        lr, beta1, beta2, eps, weight_decay, bc1, bc2s);
     CVK_LAUNCH_RETURN("cvk_adamw_step");
+}
+
+extern "C" int cvk_adamw_hyper_fill(float lr, float beta1, float beta2, float eps, float weight_decay, int step, cvk_adamw_hyper* out) {
+    CVK_CHECK_ARG(out && step >= 1, "cvk_adamw_hyper_fill: bad arguments");
+    out->lr = lr;
+    out->beta1 = beta1;
+    out->beta2 = beta2;
+    out->eps = eps;
+    out->weight_decay = weight_decay;
+    adamw_bias_corrections(beta1, beta2, step, &out->bc1, &out->bc2_sqrt);
+    return CVK_OK;
+}
+
+extern "C" int cvk_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                  const cvk_adamw_hyper* hyper, void* stream) {
+    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && hyper, "cvk_adamw_step_dev: null pointer");
+    CVK_CHECK_ARG(n > 0, "cvk_adamw_step_dev: bad arguments");
+    hipLaunchKernelGGL(k_adamw_dev, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, hyper);
+    CVK_LAUNCH_RETURN("cvk_adamw_step_dev");
+}
+
+extern "C" int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb, float* ring,
+                            int capacity, int64_t* counter, void* stream) {
+    CVK_CHECK_ARG(loss && hyper && gw && gb && ring && counter, "cvk_step_log: null pointer");
+    CVK_CHECK_ARG(nw > 0 && nb > 0 && capacity > 0, "cvk_step_log: bad arguments");
+    hipLaunchKernelGGL(k_step_log, dim3(1), dim3(STEP_LOG_THREADS), 0, (hipStream_t)stream, loss, hyper, gw, nw, gb, nb, ring, capacity,
+                       counter);
+    CVK_LAUNCH_RETURN("cvk_step_log");
 }
 
 // ---- library-wide pieces ---------------------------------------------------------------------------------------

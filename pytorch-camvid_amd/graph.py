@@ -17,13 +17,63 @@ Data parallel (round 4): RCCL collectives are stream-capturable, so a step of a 
 bucketed all-reduces (`GraphedStep(dp_net.module, ..., allow_grad_sync=True)`): every rank replays the same graph, the
 collectives run on RCCL's stream inside it, and 8 single-threaded ranks no longer sit on 11-15 ms of Python enqueue per step.
 gloo groups (CPU rehearsals) cannot be captured.
+
+The whole iteration (train.py:124-150): with `optimizer=` (a FlatAdamW) the graph also runs the AdamW step after backward (after
+the captured all-reduces under data parallel), and with `log_capacity=` it ends in one launch that appends the reference's log
+line [loss, lr, beta1, ||last weight grad||, ||last bias grad||] to a device ring.  lr, betas, eps and weight decay are read from
+param_groups[0] at every replay, the bias corrections computed on the host and uploaded into a device record the graph reads,
+so a scheduler drives the captured optimizer as it drives the eager one:
+
+    opt = FlatAdamW(net, lr=...); sched = OneCycleLR(opt, ...)
+    step = GraphedStep(net, lossf, x, t, optimizer=opt, scheduler=sched, log_capacity=len(loader))
+    for epoch in ...:
+        for xb, tb in loader:
+            step.replay(xb, tb)                # one graph launch per iteration, no host sync
+        rows, dropped = step.log()             # one D2H copy per epoch
 """
 import torch
 
+from . import _lib, engine
+from ._lib import check
+
+HYPER_FLOATS = 7                         # include/cvk.h cvk_adamw_hyper: lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt
+HYPER_SLOTS = 32                         # pinned staging records: the host may run this many replays ahead of the GPU before it waits
+
+
+def last_layer_params(net):
+    """(name, parameter) of the last parameter whose name contains 'weight' and of the last whose name contains 'bias', in
+    named_parameters() order: the reference's utils._get_lastlayer_params (utils.py:15-30)."""
+    w = b = None
+    for name, p in net.named_parameters():
+        if "weight" in name:
+            w = (name, p)
+        if "bias" in name:
+            b = (name, p)
+    return w, b
+
 
 class GraphedStep:
-    def __init__(self, net, lossf, x, t, warmup=2, allow_grad_sync=False):
+    def __init__(self, net, lossf, x, t, warmup=2, allow_grad_sync=False, *, optimizer=None, scheduler=None, log_capacity=0):
         from .modules import runner_of
+        from .optim import FlatAdamW
+        if optimizer is not None and not isinstance(optimizer, FlatAdamW):
+            raise TypeError(f"GraphedStep: only FlatAdamW can be captured with the step, not {type(optimizer).__name__}; step other "
+                            "optimizers after replay()")
+        if scheduler is not None and optimizer is None:
+            raise ValueError("GraphedStep: a scheduler needs the captured optimizer it drives (optimizer=)")
+        if scheduler is not None and getattr(scheduler, "optimizer", optimizer) is not optimizer:
+            raise ValueError("GraphedStep: the scheduler drives another optimizer")
+        log_capacity = int(log_capacity)
+        if log_capacity < 0:
+            raise ValueError("GraphedStep: log_capacity must be >= 0")
+        if log_capacity and optimizer is None:
+            raise ValueError("GraphedStep: the log records the step's lr and beta1: it needs optimizer=")
+        if optimizer is not None:
+            if len(optimizer.param_groups) != 1:
+                raise ValueError("GraphedStep: FlatAdamW with one parameter group only")
+            if {id(p) for p in optimizer._plist} != {id(p) for p in net.parameters()}:
+                raise ValueError("GraphedStep: the optimizer was built for another network")
+            optimizer._check_homes()
         R = runner_of(net)
         if R.grad_sync is not None:
             if not allow_grad_sync:
@@ -35,10 +85,22 @@ class GraphedStep:
             raise RuntimeError("GraphedStep needs the example batch on the GPU")
         self.net, self.lossf = net, lossf
         self._runner = R
+        self.optimizer, self.scheduler, self.log_capacity = optimizer, scheduler, log_capacity
         # what the captured graph bakes in: replay() refuses to run once any of it has changed
         self._sig = self._signature()
         self.x, self.t = x.clone(), t.clone()
         self.params = [p for p in net.parameters() if p.requires_grad]
+        if optimizer is not None:
+            # the record the captured AdamW step (and the log) reads; rewritten before every replay from a ring of pinned host slots
+            self._hyper = torch.zeros(HYPER_FLOATS, device=x.device, dtype=torch.float32)
+            self._hyper_pin = torch.zeros(HYPER_SLOTS, HYPER_FLOATS, dtype=torch.float32, pin_memory=True)
+            self._hyper_busy = [None] * HYPER_SLOTS     # per slot: event after the H2D copy that READ it
+            self._hyper_slot = 0
+        if log_capacity:
+            # one buffer, so that log() is one D2H copy: int64 row counter, then capacity rows of STEP_LOG_COLUMNS floats
+            self._logbuf = torch.zeros(2 + log_capacity * _lib.STEP_LOG_COLUMNS, device=x.device, dtype=torch.float32)
+            self._log_read = 0                  # rows the host has consumed
+            (_, self._log_w), (_, self._log_b) = last_layer_params(net)
         cur = torch.cuda.current_stream(x.device)
         side = torch.cuda.Stream(device=x.device)
         side.wait_stream(cur)
@@ -65,10 +127,68 @@ class GraphedStep:
         with torch.cuda.graph(self.graph, capture_error_mode=mode):
             self.loss = lossf(net(self.x), self.t)
             self.loss.backward()
+            if optimizer is not None or log_capacity:
+                self._capture_tail(x.device)
         # every tensor a replay writes must stay alive as long as the graph: the gradients (views of the flat buffer the
         # capture allocated) and the runner's workspace (a later, larger eager call would otherwise release it)
         self.grads = [p.grad for p in self.params]
         self._keep = R._ws
+
+    def _capture_tail(self, device):
+        """Inside the capture, after backward (and after the stream's waits for the all-reduces): the AdamW step, then the log row."""
+        lib, stream = _lib.load(), torch.cuda.current_stream(device).cuda_stream
+        opt = self.optimizer
+        if opt is not None:
+            self._gflat = opt._flat_grad()      # the executor's flat gradient buffer (graph pool): same address in every replay
+            check(lib.cvk_adamw_step_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
+                                         opt._flat.numel(), self._hyper.data_ptr(), stream), "cvk_adamw_step_dev")
+        if self.log_capacity:
+            gw, gb = self._log_w.grad, self._log_b.grad
+            if gw is None or gb is None:
+                raise RuntimeError("GraphedStep: the last layer's parameters received no gradient; the log cannot be captured")
+            # a conv weight's gradient is a permuted view of one dense segment: the norm does not depend on the order
+            for g in (gw, gb):
+                if not (g.is_contiguous() or g.is_contiguous(memory_format=torch.channels_last)):
+                    raise RuntimeError("GraphedStep: the last layer's gradient is not one dense block")
+            check(lib.cvk_step_log(self.loss.data_ptr(), self._hyper.data_ptr(), gw.data_ptr(), gw.numel(), gb.data_ptr(), gb.numel(),
+                                   self._logbuf.data_ptr() + 8, self.log_capacity, self._logbuf.data_ptr(), stream), "cvk_step_log")
+
+    def _upload_hyper(self):
+        """param_groups[0] as the scheduler left it + the next step number -> the device record, on the current stream (no host sync:
+        the host waits only when it is HYPER_SLOTS replays ahead of the copies that read its pinned slots)."""
+        opt = self.optimizer
+        g = opt.param_groups[0]
+        opt._step += 1
+        slot = self._hyper_slot
+        self._hyper_slot = (slot + 1) % HYPER_SLOTS
+        if self._hyper_busy[slot] is not None:
+            self._hyper_busy[slot].synchronize()
+        pin = self._hyper_pin[slot]
+        check(_lib.load().cvk_adamw_hyper_fill(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                               float(g["weight_decay"]), opt._step, pin.data_ptr()), "cvk_adamw_hyper_fill")
+        self._hyper.copy_(pin, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._hyper_busy[slot] = ev
+
+    def log(self):
+        """The log rows the replays wrote since the previous call, oldest first: (rows [k, 5] float32 numpy array of
+        [loss, lr, beta1, ||grad of the last weight||_2, ||grad of the last bias||_2], dropped).  When more than log_capacity rows were
+        written since the last call, the oldest were overwritten on the device: rows holds the newest log_capacity of them and
+        dropped says how many were lost.  One device-to-host copy (waits for the replays enqueued so far)."""
+        import numpy as np
+        if not self.log_capacity:
+            raise RuntimeError("GraphedStep.log(): built without a log (log_capacity=0)")
+        buf = self._logbuf.cpu().numpy()
+        written = int(buf[:2].view(np.int64)[0])
+        cap = self.log_capacity
+        ring = buf[2:].reshape(cap, _lib.STEP_LOG_COLUMNS)
+        new = written - self._log_read
+        dropped = max(0, new - cap)
+        first = written - min(new, cap)
+        rows = ring[[i % cap for i in range(first, written)]].copy() if written > first else np.zeros((0, _lib.STEP_LOG_COLUMNS), np.float32)
+        self._log_read = written
+        return rows, dropped
 
     def _zero(self):
         for p in self.params:
@@ -78,13 +198,24 @@ class GraphedStep:
         R = self._runner
         return (id(R.grad_sync), bool(self.net.training), bool(R.bf16), R.wino, R.wino4, R.wino4f, R.wgradp, R.wino2d, R.w2tile_cfg,
                 R.thin, R.persistent_wgs(), getattr(R, "w2d_split", False), getattr(R, "vplanes", None), getattr(R, "e4p", None),
-                getattr(R, "pool_bnred", None), getattr(R, "bnred_fuse", None))
+                getattr(R, "pool_bnred", None), getattr(R, "bnred_fuse", None)) + self._optimizer_signature()
+
+    def _optimizer_signature(self):
+        """The captured AdamW step writes the optimizer's flat buffers through raw pointers: the same optimizer, one parameter group, the
+        same flat buffer, and every parameter still a view of it at its capture-time address (a rebuilt FlatAdamW re-homes them)."""
+        opt = getattr(self, "optimizer", None)
+        if opt is None:
+            return ()
+        return (id(opt), len(opt.param_groups), opt._flat.data_ptr(), tuple(p.data_ptr() for p in opt._plist))
 
     def replay(self, x=None, t=None):
-        """Copy a new batch into the static input buffers (optional) and replay the step.  Returns the (static) loss tensor."""
+        """Copy a new batch into the static input buffers (optional) and replay the step.  Returns the (static) loss tensor.
+        With an optimizer: the captured step uses param_groups[0] as it is now and optimizer._step + 1, then the scheduler (if any)
+        steps — the order of the eager loop `replay(); optimizer.step(); scheduler.step()`."""
         if self._signature() != self._sig:
             raise RuntimeError("GraphedStep.replay: the network changed since the capture (train/eval mode, conv precision, a kernel "
-                               "knob, or it was wrapped in / unwrapped from ddp.DataParallel): the captured graph would silently run the "
+                               "knob, it was wrapped in / unwrapped from ddp.DataParallel, or the captured FlatAdamW was rebuilt or re-homed): the "
+                               "captured graph would silently run the "
                                "old configuration — build a new GraphedStep")
         if x is not None:
             self.x.copy_(x, non_blocking=True)
@@ -93,5 +224,12 @@ class GraphedStep:
         for p, g in zip(self.params, self.grads):   # zero_grad(set_to_none=True) between steps keeps working
             if p.grad is not g:
                 p.grad = g
+        if self.optimizer is not None:
+            self._upload_hyper()
         self.graph.replay()
+        if self.optimizer is not None:
+            engine._bump_epoch()        # the kernel wrote the parameters through raw pointers: derived weight tensors are stale
+            self.optimizer._opt_called = True   # what torch's scheduler wrapper of optimizer.step() records: a step ran before sched.step()
+            if self.scheduler is not None:
+                self.scheduler.step()
         return self.loss
