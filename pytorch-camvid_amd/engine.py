@@ -16,12 +16,10 @@ import torch
 
 from . import _lib
 from ._lib import View, ViewH, check
+from .route import W2D, conv_route, pad4, split_fmt
+from .route import layer_tile, wgrad2d_pays, wino2d_ok, wino2d_pays, wino4_pays  # noqa: F401  (engine.<predicate> stays importable)
 
 _F32 = torch.float32
-
-
-def pad4(c):
-    return (c + 3) // 4 * 4
 
 
 _BF16 = torch.bfloat16
@@ -85,6 +83,7 @@ class RunState:
         self.need_grad = need_grad
         self.act = {}      # buf.id -> tensor [N,H,W,ld]
         self.saved = {}    # op index -> tuple
+        self.routes = None  # op index -> route.ConvRoute of the conv blocks (fp32 plans: Runner.routes)
         self.grad = {}     # buf.id -> grad tensor
         self.gflat = None
         self.stream = None
@@ -105,36 +104,14 @@ def _empty(n, dev, dtype=_F32):
 
 import os
 
+# Runner switches (Runner.kernel_config); what each one selects is decided per layer in route.py
 WINO_DEFAULT = os.environ.get("CVK_WINO", "1") != "0"   # 1-D Winograd F(2,3) for eligible layers (Cin % 64 == 0, > 32 columns)
-
-
-# F(4,3) instead of F(2,3) for the forward / data-grad GEMMs of the layers where it pays (wino4_pays); Runner.wino4 may
-# also be set to "always" (tests: every eligible layer, whatever its size)
+# F(4,3) instead of F(2,3) for the forward / data-grad GEMMs of the layers where it pays (route.wino4_pays); "always": every eligible layer (tests)
 WINO4_DEFAULT = {"0": False, "1": True, "always": "always"}[os.environ.get("CVK_WINO4", "1")]
-
-
-def wino_ok(R, k_ch, n_cols):
-    return R.wino and k_ch % 64 == 0
-
-
-def wino4_pays(N, H, W, k_ch, n_cols):
-    """F(4,3) or F(2,3) for this layer?  Both kernels do the same work per workgroup (3*k_ch/32 K steps of a 128-row
-    tile); F(4,3) needs 6 workgroups per 4 columns, F(2,3) 8, and splits its K loop when the grid is small
-    (csrc/wino4.hip plan_wino4), so it wins (measured, tools/bench_conv.py wino wino4) whenever there is more than one
-    wave of work.  F(2,3) — the more accurate of the two — keeps the <= 32-column head and layers whose whole F(2,3)
-    grid is at most one workgroup per CU anyway (the small golden geometries)."""
-    if n_cols <= 32:
-        return False
-    tn = -(-n_cols // 128) if n_cols > 64 else 1
-    return -(-(N * H * ((W + 1) // 2)) // 128) * tn * 4 > 256
-
-
 # 2-D F(4x4,3x3) (csrc/wino2d.hip) for the channel-heavy layers: 2.25 multiplies per output and input channel instead of
 # the 4.5 of the 1-D kernels, paid for with three HBM passes over transform-domain planes.  "0": off, "1": where it pays,
 # "always": every eligible layer (tests).
 WINO2D_DEFAULT = {"0": False, "1": True, "always": "always"}[os.environ.get("CVK_WINO2D", "1")]
-
-
 # Output tile of the 2-D path: 6 = F(6x6,3x3) (64 GEMMs, 1.78 multiplies per output, planes 1.78x the activation), 4 = F(4x4,3x3)
 # (36 GEMMs, 2.25 / 2.25x).  Both are the same kernels of csrc/wino2d.hip; F(6x6) rounds about twice as coarsely (5e-6 relative L2
 # at 256 input channels, tests/test_gpu_w6.py).  "auto" (default): 6, except for networks with MaxUnpool2d (SegNet): their five
@@ -142,6 +119,13 @@ WINO2D_DEFAULT = {"0": False, "1": True, "always": "always"}[os.environ.get("CVK
 # the full-size SegNet parity test (distance to the reference <= 2x the reference's own distance to its 1e-6-perturbed twin) holds
 # with F(4x4) (18 % of the sampled logits move by > 1e-3, the twin: 11 %) but not with F(6x6) (26 %).
 W2TILE_DEFAULT = {"auto": None, "4": 4, "6": 6}[os.environ.get("CVK_W2D_TILE", "auto")]
+# fused F(4,3) (csrc/wino4f.hip) instead of the per-index F(4,3) kernels + output pass: "0" off, "1" on
+WINO4F_DEFAULT = os.environ.get("CVK_WINO4F", "1") != "0"
+# transposed F(4,3) weight-grad through transform-domain planes (csrc/wgradp.hip): "0" off, "1" where it pays, "always" (tests)
+WGRADP_DEFAULT = {"0": False, "1": True, "always": "always"}[os.environ.get("CVK_WGRADP", "1")]
+# Round 6: the fused F(4,3) forward launch also writes the weight-grad's V planes (cvk_conv3x3_wino4f_vplanes, slice-major) — the plane GEMM then
+# takes every F(4,3) weight-grad, not only the 64-input-channel ones, and the x -> V pass is gone.  "0" off, "1" on.
+VPLANES_DEFAULT = os.environ.get("CVK_VPLANES", "1") != "0"
 
 
 def w2fn(lib, tile, name):
@@ -153,76 +137,6 @@ def w2ws(lib, tile, N, H, W, k_ch, cout):
     return (lib.cvk_conv3x3_w6_workspace_bytes if tile == 6 else lib.cvk_conv3x3_w2d_workspace_bytes)(N, H, W, k_ch, cout)
 
 
-def layer_tile(R, N, H, W, dgrad=False):
-    """Output tile of the 2-D path for a layer geometry (dgrad: of a data-grad launch — networks with MaxUnpool2d keep 4x4 tiles in the
-    forward pass, where coarser rounding flips pool arg-maxes, but their data-grads run after the indices are fixed: 6x6).  The batched GEMM works on 128-row tiles of the tile index: at the 22x30
-    bottleneck (batch 8) 6x6 tiles give 160 rows = two row tiles of which 37 % are padding (138 us, as long as F(4x4)'s three full
-    row tiles) and 1.78x the filter-transform bytes (50 vs 28 us at 1024 x 1024 channels) — such layers keep 4x4 tiles."""
-    if (R.w2tile_dgrad if dgrad else R.w2tile) != 6:
-        return 4
-    t6 = N * ((H + 5) // 6) * ((W + 5) // 6)
-    t4 = N * ((H + 3) // 4) * ((W + 3) // 4)
-    u6 = t6 / (128.0 * ((t6 + 127) // 128))
-    u4 = t4 / (128.0 * ((t4 + 127) // 128))
-    return 4 if (u6 < 0.7 and u4 > u6 + 0.2) else 6
-
-
-def wino2d_ok(k_ch, cout, ldy):
-    return k_ch % 32 == 0 and cout % 4 == 0 and cout >= 64 and ldy % 4 == 0
-
-
-def wino2d_pays(N, H, W, k_ch, cout, tile=4):
-    """Measured at the UNet batch-8 shapes (tools/bench_conv.py wino4 w2d [--rev]; tile 6: tools/bench_w6.py).  F(4x4,3x3): the 36
-    batched GEMMs + transforms beat F(4,3) + its output pass by 13-31 % once Cin*Cout >= 256*256 (256->256 @ 90x120 ... 1024->512 @
-    45x60), by 10-13 % for 128<->256 channels at 180x240, and lose below that (the transform passes cost more than the saved
-    multiplies).  F(6x6,3x3) is 15-25 % cheaper than F(4x4) on every layer with >= 256 tiles (21 % fewer multiplies and plane
-    bytes) and would also take 128->128 @180x240 (435 vs 490 us forward) and 128<->256 @90x120 (170 vs 252 / 302 us) from the fused
-    1-D kernel — measured: no gain on the whole step (231.4 vs 232.9 img/s on two boxes) while the logits deviation from the
-    reference grows again (headline workload, sampled logits: max 6.9e-4 and 1.2 % beyond 3e-4, against 4.6e-4 / 0.3 % with the layer
-    set below; F(4x4): 2.5e-4 / none; the reference's own fp32-vs-1e-6-noise drift: 1.7e-4) — so both tile sizes take the SAME layers."""
-    T = N * ((H + 3) // 4) * ((W + 3) // 4)
-    return T >= 256 and (k_ch * cout >= 65536 or (k_ch * cout >= 32768 and T >= 16384))
-
-
-def wgrad2d_pays(N, H, W, k_ch, cout):
-    """Weight-grad through the 2-D transform: wins from 256 x 256 channels up (0.60-0.90 of the transposed F(4,3) time at the
-    UNet batch-8 shapes), loses below (the dy / x transform passes dominate)."""
-    T = N * ((H + 3) // 4) * ((W + 3) // 4)
-    return T >= 256 and k_ch * cout >= 65536
-
-
-# fused F(4,3) (csrc/wino4f.hip) instead of the per-index F(4,3) kernels + output pass: "0" off, "1" on
-WINO4F_DEFAULT = os.environ.get("CVK_WINO4F", "1") != "0"
-
-
-def wino4f_ok(k_ch, cout):
-    return k_ch % 32 == 0 and cout % 4 == 0 and cout >= 32
-
-
-# transposed F(4,3) weight-grad through transform-domain planes (csrc/wgradp.hip): "0" off, "1" where it pays, "always" (tests)
-WGRADP_DEFAULT = {"0": False, "1": True, "always": "always"}[os.environ.get("CVK_WGRADP", "1")]
-
-
-def wgradp_ok(cin_ld, cout, ldy):
-    return cin_ld % 64 == 0 and cout % 64 == 0 and ldy == cout
-
-
-def wgradp_pays(N, H, W, cin_ld, cout):
-    return cin_ld == 64 and N * H * ((W + 3) // 4) >= 4096
-
-
-# Round 6: the fused F(4,3) forward launch also writes the weight-grad's V planes (cvk_conv3x3_wino4f_vplanes, slice-major) — the plane GEMM then
-# takes every F(4,3) weight-grad, not only the 64-input-channel ones, and the x -> V pass is gone.  "0" off, "1" on.
-VPLANES_DEFAULT = os.environ.get("CVK_VPLANES", "1") != "0"
-
-
-def vplanes_pays(N, H, W, cin_ld, cout):
-    """tools/bench_vplanes.py at the headline shapes (64/128 -> 64/128/256 channels, 360x480 ... 90x120, batch 8): the forward launch costs
-    +9 ... +47 us, the weight-grad gains 34 ... 370 us on every layer; bounded by the kernel's 4 GiB plane addressing."""
-    rows = N * (H + 2) * (((W + 3) // 4 + 7) // 8 * 8)
-    return cin_ld % 64 == 0 and cout <= 512 and N * H * ((W + 3) // 4) >= 4096 and 24 * cin_ld * (rows + 64) < 2 ** 32 - 4096
-
-
 def amax_blocks(lib, n, dev):
     """n zeroed "amax blocks" (csrc/cvk_common.h: the largest magnitude of a tensor in device memory, a few slots one cache line apart): a list of
     int32 views, one fill for all of them."""
@@ -231,251 +145,225 @@ def amax_blocks(lib, n, dev):
     return [t[i * nw:(i + 1) * nw] for i in range(n)]
 
 
-def split_fmt(R):
-    """runner.w2d_split as a split-plane format (csrc/split_fmt.h): 0 = off (exact-fp32 MFMA, the default), 3 = three bf16 terms (True means
-    this one), 2 = two scaled fp16 terms."""
-    v = getattr(R, "w2d_split", 0)
-    return 3 if v is True else (int(v) if v in (2, 3) else 0)
+def absmax(R, t, rows, cols, ld, s, what):
+    """A new amax block holding the largest magnitude of t[rows][cols] (pitch ld), measured by its own pass."""
+    a = amax_blocks(R.lib, 1, t.device)[0]
+    _timed(R, "k_absmax", 4.0 * rows * cols, lambda: check(
+        R.lib.cvk_absmax_f32(t.data_ptr(), rows, cols, ld, a.data_ptr(), s), "cvk_absmax_f32(%s)" % what), "byte")
+    return a
 
 
-def wino_conv(R, lib, s, x, w, bias, y, sp, N, H, W, k_ch, cout, ldy, flops, what="", dgrad_of=None, keep_v=None, wsrc=None, ck=None,
-              bnred=None, v_pre=None, split=False, x_amax=None, h2=False, want_planes=False):
-    """y[N,H,W,ldy] = conv3x3(x[N,H,W,k_ch], w[cout][3][3][k_ch]) (+bias, +BN statistics partials at sp) through the
-    Winograd kernels: weight transform -> (input transform ->) GEMMs M_xi -> output transform.  2-D F(4x4,3x3) for the
-    channel-heavy layers (R.wino2d, wino2d_pays), else 1-D F(4,3) when R.wino4, else F(2,3).
-    Data-grad: `w` is a callable returning the rotated/transposed pack (built only if a kernel needs it) and
-    dgrad_of = (forward weights [Cout_f][3][3][Cin_f], Cout_f, Cin_f) lets F(4,3) transform straight from them.
-    Returns None, or (P, counts pointer) when the statistics partials at sp carry explicit pixel counts (2-D path:
-    P = cvk_w2d_stat_partials partials of [sum | M2] followed by the counts -> cvk_bn_finalize_counts).  keep_v: a list that
-    receives the transformed input V when the 2-D path runs (the layer's weight-grad reuses it).  wsrc / ck: the parameter the
-    filter derives from and the layer's cache key — the transformed filter is then kept across calls (Runner.derived).
-    bnred (data-grad only): (yP, scale, shift, mean, rstd pointers, out list) of the block that produced this conv's input; when
-    the fused F(4,3) kernel runs and ldy == cout it also leaves that block's BatchNorm-backward sums and appends
-    (partials tensor, partial count) to the list.  v_pre (tile, tensor): the transformed input V of the 2-D path, already computed
-    with that tile (cvk_w6_dy_transform_both: the backward pass transforms dy once for the data-grad and the weight-grad)."""
-    M = N * H * W
+class WinoConv:
+    """y[N,H,W,ldy] = conv3x3(x[N,H,W,k_ch], w[cout][3][3][k_ch]) (+bias, +BN statistics partials at sp) through the Winograd family the
+    route names: a block's forward pass, or its data-grad (dgrad_of = (forward weights [Cout_f][3][3][Cin_f], Cout_f, Cin_f); `w` then returns
+    the rotated / transposed pack).  Transformed filters are cached under key ck as functions of the parameter wsrc (Runner.derived).
+    After run: v, v_amax = the input transform kept for the weight-grad (keep); bnred_sums = (partials, count) a fused data-grad left."""
 
-    def cached(kind, build, job=None):
-        return R.derived((ck, kind), wsrc, build, job) if (ck is not None and wsrc is not None) else build()
+    def __init__(self, R, s, x, w, bias, y, sp, N, H, W, k_ch, cout, ldy, flops, wsrc, ck, what="", dgrad_of=None):
+        self.R, self.lib, self.s, self.x, self.w, self.bias, self.y, self.sp = R, R.lib, s, x, w, bias, y, sp
+        self.N, self.H, self.W, self.M, self.k_ch, self.cout, self.ldy = N, H, W, N * H * W, k_ch, cout, ldy
+        self.flops, self.wsrc, self.ck, self.what, self.dgrad_of = flops, wsrc, ck, what, dgrad_of
+        self.wt = dgrad_of[0] if dgrad_of is not None else w        # the filter the F(4,3) / split transforms read (data-grad: they rotate it)
+        self.v = self.v_amax = self.bnred_sums = None
 
-    def straight(t):                        # is tensor t the parameter itself (no packed / padded copy in between)?
-        return wsrc is not None and t is not None and not callable(t) and t.data_ptr() == wsrc.data_ptr()
-    if wino2d_ok(k_ch, cout, ldy) and (R.wino2d == "always" or (R.wino2d and wino2d_pays(N, H, W, k_ch, cout, R.w2tile))):
-        tile = layer_tile(R, N, H, W, dgrad=dgrad_of is not None)
+    def run(self, fam, tile=0, fmt=0, keep=False, v_pre=None, x_amax=None, bnred=None):
+        """v_pre: 2-D input planes already made with this tile (dy transformed once for both gradients); x_amax: the amax block of x (fp16 split
+        operands; measured when None); bnred: (y, scale, shift, mean, rstd) pointers of the block whose BatchNorm-backward sums a fused
+        data-grad leaves.  Returns (partial count, counts pointer) when the partials carry pixel counts (cvk_bn_finalize_counts), else None."""
+        if fam == "w2d":
+            return self.w2d(tile, keep, v_pre)
+        if fam == "w2d_split":
+            return self.w2d_split(tile, fmt, keep, v_pre, x_amax)
+        if fam in ("w4f", "w4f_vplanes", "w4h"):
+            return self.w4f(fam == "w4f_vplanes", bnred, fam == "w4h", x_amax)
+        return self.w4() if fam == "w4" else self.w2()
+
+    def _filter(self, kind, build, job=None):
+        """The cached transformed filter `kind`.  job = (family, floats, rows, cols, tile, dgrad): how prebuild_fp32's batched launch rebuilds it,
+        recorded only when the transform reads the parameter itself (no packed or channel-padded copy in between)."""
+        d = self.dgrad_of
+        straight = self.wt.data_ptr() == self.wsrc.data_ptr() and (d is None or (d[1] == self.k_ch and d[2] == self.cout))
+        return self.R.derived((self.ck, kind), self.wsrc, build, job if straight else None)
+
+    def _amax_w(self):
+        """The largest magnitude of the filter (fp16 split operands), cached with the layer's filters (shared by its forward and data-grad)."""
+        wt = self.wt
+        return self.R.derived(((self.ck[0], "a"), "amaxw"), self.wsrc, lambda: absmax(self.R, wt, wt.numel() // 4, 4, 4, self.s, "w"))
+
+    def _counts(self, P):
+        return self.sp + 4 * 2 * P * self.cout if self.sp is not None else None
+
+    def w2d(self, tile, keep, v_pre):
+        """2-D F(4x4,3x3) / F(6x6,3x3) (csrc/wino2d.hip)."""
+        R, lib, s, x, d = self.R, self.lib, self.s, self.x, self.dgrad_of
+        N, H, W, M, k_ch, cout, ldy = self.N, self.H, self.W, self.M, self.k_ch, self.cout, self.ldy
         NX = 64 if tile == 6 else 36
-        if split:
-            # OPT-IN path (runner.w2d_split = 3 | 2, DESIGN.md 5b round 5): the GEMM stage on the 16-bit matrix pipe with split fp32 operands
-            # (csrc/split_fmt.h: three bf16 terms / six cross-products, or two fp16 terms / three cross-products scaled by an exact power of
-            # two from the source tensors' largest magnitudes) — the transforms write split planes, cvk_w2d_gemm_split multiplies them, the
-            # plain output pass finishes
-            fmt = int(split)
-            pdt = _BF16 if fmt == 3 else torch.float16
-            tag = "split3" if fmt == 3 else "split2h"
-            T = w2fn(lib, tile, "tiles")(N, H, W)
-            Tp = lib.cvk_split3_rows_pad(T, 256)
-            Cp = lib.cvk_split3_rows_pad(cout, 128)
-            wraw = dgrad_of[0] if dgrad_of is not None else (w() if callable(w) else w)
-            am_w = None
-            if fmt == 2:
-                def build_amax_w():
-                    a = amax_blocks(lib, 1, x.device)[0]
-                    _timed(R, "k_absmax", 4.0 * wraw.numel(), lambda: check(
-                        lib.cvk_absmax_f32(wraw.data_ptr(), wraw.numel() // 4, 4, 4, a.data_ptr(), s), "cvk_absmax_f32(w)"), "byte")
-                    return a
-                am_w = R.derived(((ck[0] if ck is not None else None, "a"), "amaxw"), wsrc, build_amax_w) if (ck is not None and wsrc is not None) \
-                    else build_amax_w()
-            def build_u3():
-                u3 = torch.empty(NX * (k_ch // 32) * fmt * Cp * 32, device=x.device, dtype=pdt)
-                amp = am_w.data_ptr() if am_w is not None else None
-                if dgrad_of is not None:
-                    _timed(R, "k_w2d_weight_dgrad+" + tag, 4.0 * 9 * cout * k_ch + 2.0 * fmt * NX * cout * k_ch, lambda: check(
-                        lib.cvk_w2d_weight_transform_split(fmt, tile, wraw.data_ptr(), u3.data_ptr(), amp, dgrad_of[1], dgrad_of[2], 1, s),
-                        "cvk_w2d_weight_transform_split(dgrad)"), "byte")
-                else:
-                    _timed(R, "k_w2d_weight+" + tag, 4.0 * 9 * cout * k_ch + 2.0 * fmt * NX * cout * k_ch, lambda: check(
-                        lib.cvk_w2d_weight_transform_split(fmt, tile, wraw.data_ptr(), u3.data_ptr(), amp, cout, k_ch, 0, s),
-                        "cvk_w2d_weight_transform_split"), "byte")
-                return u3
-            U3 = cached("w2ds%d_%d" % (fmt, tile), build_u3)
-            v3fl = NX * (k_ch // 32) * fmt * Tp * 32
-            if v_pre is not None:
-                V3, am_x = v_pre[1], getattr(v_pre[1], "cvk_amax", None)
-            else:
-                V3 = torch.empty(v3fl, device=x.device, dtype=pdt)
-                am_x = x_amax           # left by the passes that wrote x (Runner.plan_amax), else measured here
-                if fmt == 2 and am_x is None:
-                    am_x = amax_blocks(lib, 1, x.device)[0]
-                    _timed(R, "k_absmax", 4.0 * M * k_ch, lambda: check(
-                        lib.cvk_absmax_f32(x.data_ptr(), M, k_ch, k_ch, am_x.data_ptr(), s), "cvk_absmax_f32(x)"), "byte")
-                V3.cvk_amax = am_x          # the planes travel with the word they were scaled by (weight-grad GEMM, data-grad GEMM)
-                if keep_v is not None:
-                    keep_v.append(V3)
-                _timed(R, "k_w2d_input<%s>" % tag, (4.0 * M + 2.0 * fmt * NX * T) * k_ch, lambda: check(
-                    lib.cvk_w2d_input_transform_split(fmt, tile, x.data_ptr(), V3.data_ptr(), am_x.data_ptr() if am_x is not None else None,
-                                                      N, H, W, k_ch, s), "cvk_w2d_input_transform_split" + what), "byte")
-            ws = R.workspace(4 * NX * T * cout + 1024, x.device)
-            _timed(R, "k_gemm_" + tag, flops, lambda: check(
-                lib.cvk_w2d_gemm_split(fmt, tile, V3.data_ptr(), U3.data_ptr(), ws.data_ptr(), am_x.data_ptr() if am_x is not None else None,
-                                       am_w.data_ptr() if am_w is not None else None, NX, T, Tp, k_ch, cout, Cp, s), "cvk_w2d_gemm_split" + what),
-                executed=2.0 * (6 if fmt == 3 else 3) * NX * Tp * k_ch * Cp)     # six bf16 / three fp16 MFMA products per fp32 product
-            P2 = w2fn(lib, tile, "stat_partials")(N, H, W)
-            cnt = sp + 4 * 2 * P2 * cout if sp is not None else None
-            _timed(R, "k_w2d_output", 4.0 * (NX * T + M) * cout, lambda: check(
-                lib.cvk_w2d_output_plain(tile, ws.data_ptr(), bias, y.data_ptr(), sp, cnt, N, H, W, cout, ldy, s), "cvk_w2d_output_plain" + what), "byte")
-            return (P2, cnt) if sp is not None else None
-        def build_u2():
-            u = _empty(NX * cout * k_ch, x.device)
-            if dgrad_of is not None and dgrad_of[1] == k_ch and dgrad_of[2] == cout:       # no channel padding: straight from the forward weights
-                _timed(R, "k_w2d_weight_dgrad", 4.0 * (9 + NX) * cout * k_ch, lambda: check(
-                    w2fn(lib, tile, "weight_transform_dgrad")(dgrad_of[0].data_ptr(), u.data_ptr(), dgrad_of[1], dgrad_of[2], s),
-                    "cvk_w2d_weight_transform_dgrad"), "byte")
-                return u
-            wt = w() if callable(w) else w
-            _timed(R, "k_w2d_weight", 4.0 * (9 + NX) * cout * k_ch, lambda: check(
-                w2fn(lib, tile, "weight_transform")(wt.data_ptr(), u.data_ptr(), cout, k_ch, s), "cvk_w2d_weight_transform"), "byte")
+
+        dg = d is not None and d[1] == k_ch and d[2] == cout          # data-grad without channel padding: straight from the forward weights
+        rows, cols = (d[1], d[2]) if dg else (cout, k_ch)
+
+        def build():
+            u, wt = _empty(NX * cout * k_ch, x.device), d[0] if dg else (self.w() if callable(self.w) else self.w)
+            kind = "weight_transform_dgrad" if dg else "weight_transform"
+            _timed(R, "k_w2d_weight_dgrad" if dg else "k_w2d_weight", 4.0 * (9 + NX) * cout * k_ch, lambda: check(
+                w2fn(lib, tile, kind)(wt.data_ptr(), u.data_ptr(), rows, cols, s), "cvk_w2d_" + kind), "byte")
             return u
-        job = None
-        if dgrad_of is not None and dgrad_of[1] == k_ch and dgrad_of[2] == cout and straight(dgrad_of[0]):
-            job = ("w2d", NX * cout * k_ch, dgrad_of[1], dgrad_of[2], tile, 1)
-        elif dgrad_of is None and straight(w):
-            job = ("w2d", NX * cout * k_ch, cout, k_ch, tile, 0)
-        U = cached("w2d%d" % tile, build_u2, job)
+        U = self._filter("w2d%d" % tile, build, ("w2d", NX * cout * k_ch, rows, cols, tile, int(d is not None)))
         T = w2fn(lib, tile, "tiles")(N, H, W)
         vfl = NX * lib.cvk_w2d_tpad(T) * k_ch + 128          # V planes + 512 bytes of slack
-        if v_pre is not None and v_pre[0] == tile:
-            ws = R.workspace(w2ws(lib, tile, N, H, W, k_ch, cout) - 4 * vfl, x.device)
-            V, Mo = v_pre[1].data_ptr(), ws.data_ptr()
-        elif keep_v is not None:    # the weight-grad of this layer reuses V: its own tensor instead of the shared workspace
-            Vt = _empty(vfl, x.device)
-            keep_v.append(Vt)
-            ws = R.workspace(w2ws(lib, tile, N, H, W, k_ch, cout) - 4 * vfl, x.device)
-            V, Mo = Vt.data_ptr(), ws.data_ptr()
-        else:
-            ws = R.workspace(w2ws(lib, tile, N, H, W, k_ch, cout), x.device)
-            V, Mo = ws.data_ptr(), ws.data_ptr() + 4 * vfl
+        if keep:        # the weight-grad of this layer reuses V: its own tensor instead of the shared workspace
+            self.v = _empty(vfl, x.device)
+        Vt = v_pre if v_pre is not None else self.v
+        ws = R.workspace(w2ws(lib, tile, N, H, W, k_ch, cout) - (4 * vfl if Vt is not None else 0), x.device)
+        V, Mo = (Vt.data_ptr(), ws.data_ptr()) if Vt is not None else (ws.data_ptr(), ws.data_ptr() + 4 * vfl)
         P2 = w2fn(lib, tile, "stat_partials")(N, H, W)
-        cnt = sp + 4 * 2 * P2 * cout if sp is not None else None
-        if not (v_pre is not None and v_pre[0] == tile):
+        cnt = self._counts(P2)
+        if v_pre is None:
             _timed(R, "k_w2d_input", 4.0 * (M + NX * T) * k_ch, lambda: check(
-                w2fn(lib, tile, "input_transform")(x.data_ptr(), V, N, H, W, k_ch, s), "cvk_w2d_input_transform" + what), "byte")
-        _timed(R, "k_w2d_gemm<128, 32, 2, 2>", flops, lambda: check(w2fn(lib, tile, "gemm")(V, U.data_ptr(), Mo, T, k_ch, cout, s), "cvk_w2d_gemm" + what),
-               executed=2.0 * NX * T * k_ch * cout)   # NX GEMMs of T x k_ch x cout really run on the matrix pipe
+                w2fn(lib, tile, "input_transform")(x.data_ptr(), V, N, H, W, k_ch, s), "cvk_w2d_input_transform" + self.what), "byte")
+        _timed(R, "k_w2d_gemm<128, 32, 2, 2>", self.flops, lambda: check(
+            w2fn(lib, tile, "gemm")(V, U.data_ptr(), Mo, T, k_ch, cout, s), "cvk_w2d_gemm" + self.what),
+            executed=2.0 * NX * T * k_ch * cout)   # NX GEMMs of T x k_ch x cout really run on the matrix pipe
         _timed(R, "k_w2d_output", 4.0 * (NX * T + M) * cout, lambda: check(
-            w2fn(lib, tile, "output")(Mo, bias, y.data_ptr(), sp, cnt, N, H, W, k_ch, cout, ldy, s), "cvk_w2d_output" + what), "byte")
-        return (P2, cnt) if sp is not None else None
-    use4 = R.wino4 == "always" or (R.wino4 and wino4_pays(N, H, W, k_ch, ldy))
-    if use4 and R.wino4f and wino4f_ok(k_ch, cout) and (dgrad_of is None or (dgrad_of[1] == k_ch and dgrad_of[2] == cout)):
-        # fused F(4,3) (csrc/wino4f.hip): all six transform indices in one workgroup, output transform + bias + statistics in
-        # registers — no product planes, no output pass
-        if h2:
-            # OPT-IN fp16 split-operand form (runner.w2d_split = 2): the same kernel with two scaled fp16 terms per operand, 18 fp16 MFMAs per K
-            # step instead of 48 fp32 ones; needs the largest magnitudes of x (left by the pass that wrote it, else measured here) and of w
-            wraw = dgrad_of[0] if dgrad_of is not None else (w() if callable(w) else w)
+            w2fn(lib, tile, "output")(Mo, self.bias, self.y.data_ptr(), self.sp, cnt, N, H, W, k_ch, cout, ldy, s), "cvk_w2d_output" + self.what), "byte")
+        return (P2, cnt) if self.sp is not None else None
 
-            def build_amax_w():
-                a = amax_blocks(lib, 1, x.device)[0]
-                _timed(R, "k_absmax", 4.0 * wraw.numel(), lambda: check(
-                    lib.cvk_absmax_f32(wraw.data_ptr(), wraw.numel() // 4, 4, 4, a.data_ptr(), s), "cvk_absmax_f32(w)"), "byte")
-                return a
-            am_w = R.derived(((ck[0], "a"), "amaxw"), wsrc, build_amax_w) if (ck is not None and wsrc is not None) else build_amax_w()
+    def w2d_split(self, tile, fmt, keep, v_pre, x_amax):
+        """OPT-IN (runner.w2d_split = 3 | 2): the 2-D path with its GEMM stage on the 16-bit matrix pipe with split fp32
+        operands (csrc/split_fmt.h: three bf16 terms / six cross-products, or two fp16 terms / three cross-products scaled by an exact power of
+        two from the source tensors' largest magnitudes) — the transforms write split planes, cvk_w2d_gemm_split multiplies them, the plain
+        output pass finishes.  With v_pre, x_amax is the amax block those planes were scaled by."""
+        R, lib, s, x, d = self.R, self.lib, self.s, self.x, self.dgrad_of
+        N, H, W, M, k_ch, cout, ldy = self.N, self.H, self.W, self.M, self.k_ch, self.cout, self.ldy
+        NX = 64 if tile == 6 else 36
+        pdt = _BF16 if fmt == 3 else torch.float16
+        tag = "split3" if fmt == 3 else "split2h"
+        T = w2fn(lib, tile, "tiles")(N, H, W)
+        Tp = lib.cvk_split3_rows_pad(T, 256)
+        Cp = lib.cvk_split3_rows_pad(cout, 128)
+        wt = self.wt
+        am_w = self._amax_w() if fmt == 2 else None
 
-            def build_uh():
-                uh = _empty(lib.cvk_wino4f_weight_floats(cout, k_ch), x.device)
-                _timed(R, "k_wino4h_weight", 4.0 * (9 + 18) * cout * k_ch, lambda: check(
-                    lib.cvk_wino4h_weight_transform(wraw.data_ptr(), uh.data_ptr(), am_w.data_ptr(), cout, k_ch, 1 if dgrad_of is not None else 0, s),
-                    "cvk_wino4h_weight_transform"), "byte")
-                return uh
-            Uh = cached("w4h", build_uh)
-            am_x = x_amax
-            if am_x is None:
-                am_x = amax_blocks(lib, 1, x.device)[0]
-                _timed(R, "k_absmax", 4.0 * M * k_ch, lambda: check(lib.cvk_absmax_f32(x.data_ptr(), M, k_ch, k_ch, am_x.data_ptr(), s), "cvk_absmax_f32(x)"), "byte")
-            Pf = lib.cvk_wino4f_stat_partials(N, H, W)
-            cnt = sp + 4 * 2 * Pf * cout if sp is not None else None
-            if bnred is not None and sp is None and bias is None and ldy == cout and R.bnred_fuse:
-                bpart = _empty(2 * Pf * cout, x.device)
-                _timed(R, "k_conv3x3_wino4h<bnred>", flops, lambda: check(
-                    lib.cvk_conv3x3_wino4h_bnred(x.data_ptr(), Uh.data_ptr(), y.data_ptr(), am_x.data_ptr(), am_w.data_ptr(), N, H, W, k_ch, cout, ldy,
-                                                 *bnred[:5], bpart.data_ptr(), R.launch_wgs(), s), "cvk_conv3x3_wino4h_bnred"), executed=1.5 * flops)
-                bnred[5].append((bpart, Pf))
-                return None
-            _timed(R, "k_conv3x3_wino4h", flops, lambda: check(
-                lib.cvk_conv3x3_wino4h(x.data_ptr(), Uh.data_ptr(), bias, y.data_ptr(), sp, cnt, am_x.data_ptr(), am_w.data_ptr(), N, H, W, k_ch, cout,
-                                       ldy, R.launch_wgs(), s), "cvk_conv3x3_wino4h" + what), executed=1.5 * flops)      # 3 fp16 products per fp32 product
-            return (Pf, cnt) if sp is not None else None
-        def build_uf():
-            uf = _empty(lib.cvk_wino4f_weight_floats(cout, k_ch), x.device)
-            if dgrad_of is not None:
-                _timed(R, "k_wino4f_weight", 4.0 * (9 + 18) * cout * k_ch, lambda: check(
-                    lib.cvk_wino4f_weight_transform(dgrad_of[0].data_ptr(), uf.data_ptr(), cout, k_ch, 1, s), "cvk_wino4f_weight_transform(dgrad)"), "byte")
+        def build():
+            u3 = torch.empty(NX * (k_ch // 32) * fmt * Cp * 32, device=x.device, dtype=pdt)
+            amp = am_w.data_ptr() if am_w is not None else None
+            rows, cols = (d[1], d[2]) if d is not None else (cout, k_ch)
+            _timed(R, ("k_w2d_weight_dgrad+" if d is not None else "k_w2d_weight+") + tag, 4.0 * 9 * cout * k_ch + 2.0 * fmt * NX * cout * k_ch,
+                   lambda: check(lib.cvk_w2d_weight_transform_split(fmt, tile, wt.data_ptr(), u3.data_ptr(), amp, rows, cols, int(d is not None), s),
+                                 "cvk_w2d_weight_transform_split" + ("(dgrad)" if d is not None else "")), "byte")
+            return u3
+        U3 = self._filter("w2ds%d_%d" % (fmt, tile), build)
+        am_x = x_amax
+        if v_pre is not None:
+            V3 = v_pre
+        else:
+            V3 = torch.empty(NX * (k_ch // 32) * fmt * Tp * 32, device=x.device, dtype=pdt)
+            if fmt == 2 and am_x is None:       # left by the passes that wrote x (Runner.plan_amax), else measured here
+                am_x = absmax(R, x, M, k_ch, k_ch, s, "x")
+            if keep:            # the planes travel with the word they were scaled by (weight-grad GEMM)
+                self.v, self.v_amax = V3, am_x
+            _timed(R, "k_w2d_input<%s>" % tag, (4.0 * M + 2.0 * fmt * NX * T) * k_ch, lambda: check(
+                lib.cvk_w2d_input_transform_split(fmt, tile, x.data_ptr(), V3.data_ptr(), am_x.data_ptr() if am_x is not None else None,
+                                                  N, H, W, k_ch, s), "cvk_w2d_input_transform_split" + self.what), "byte")
+        ws = R.workspace(4 * NX * T * cout + 1024, x.device)
+        _timed(R, "k_gemm_" + tag, self.flops, lambda: check(
+            lib.cvk_w2d_gemm_split(fmt, tile, V3.data_ptr(), U3.data_ptr(), ws.data_ptr(), am_x.data_ptr() if am_x is not None else None,
+                                   am_w.data_ptr() if am_w is not None else None, NX, T, Tp, k_ch, cout, Cp, s), "cvk_w2d_gemm_split" + self.what),
+            executed=2.0 * (6 if fmt == 3 else 3) * NX * Tp * k_ch * Cp)     # six bf16 / three fp16 MFMA products per fp32 product
+        P2 = w2fn(lib, tile, "stat_partials")(N, H, W)
+        cnt = self._counts(P2)
+        _timed(R, "k_w2d_output", 4.0 * (NX * T + M) * cout, lambda: check(
+            lib.cvk_w2d_output_plain(tile, ws.data_ptr(), self.bias, self.y.data_ptr(), self.sp, cnt, N, H, W, cout, ldy, s),
+            "cvk_w2d_output_plain" + self.what), "byte")
+        return (P2, cnt) if self.sp is not None else None
+
+    def w4f(self, vplanes=False, bnred=None, h2=False, x_amax=None):
+        """Fused F(4,3) (csrc/wino4f.hip): all six transform indices in one workgroup, output transform + bias + statistics in registers — no
+        product planes, no output pass.  vplanes: the forward launch also leaves V = B^T d behind as six slice-major planes, the input of the
+        layer's plane-GEMM weight-grad (csrc/wgradp.hip); bnred: the data-grad also sums the producing block's BatchNorm backward.
+        h2: the OPT-IN fp16 split-operand form (runner.w2d_split = 2): two scaled fp16 terms per operand, 18 fp16 MFMAs per K step instead of
+        48 fp32 ones; needs the largest magnitudes of x (left by the pass that wrote it, else measured here) and of w."""
+        R, lib, s, x, d, wt = self.R, self.lib, self.s, self.x, self.dgrad_of, self.wt
+        N, H, W, M, k_ch, cout, ldy, flops = self.N, self.H, self.W, self.M, self.k_ch, self.cout, self.ldy, self.flops
+        floats, dg, f = lib.cvk_wino4f_weight_floats(cout, k_ch), int(d is not None), "h" if h2 else "f"
+        am_w = self._amax_w() if h2 else None
+
+        def build():
+            u = _empty(floats, x.device)
+            if h2:
+                _timed(R, "k_wino4h_weight", 4.0 * (9 + 18) * cout * k_ch, lambda: check(lib.cvk_wino4h_weight_transform(
+                    wt.data_ptr(), u.data_ptr(), am_w.data_ptr(), cout, k_ch, dg, s), "cvk_wino4h_weight_transform"), "byte")
             else:
-                wt = w() if callable(w) else w
-                _timed(R, "k_wino4f_weight", 4.0 * (9 + 18) * cout * k_ch, lambda: check(
-                    lib.cvk_wino4f_weight_transform(wt.data_ptr(), uf.data_ptr(), cout, k_ch, 0, s), "cvk_wino4f_weight_transform"), "byte")
-            return uf
-        job = None
-        if dgrad_of is not None and straight(dgrad_of[0]):
-            job = ("w4f", lib.cvk_wino4f_weight_floats(cout, k_ch), cout, k_ch, 0, 1)
-        elif dgrad_of is None and straight(w):
-            job = ("w4f", lib.cvk_wino4f_weight_floats(cout, k_ch), cout, k_ch, 0, 0)
-        Uf = cached("w4f", build_uf, job)
-        Pf = lib.cvk_wino4f_stat_partials(N, H, W)
-        cnt = sp + 4 * 2 * Pf * cout if sp is not None else None
-        if bnred is not None and sp is None and bias is None and ldy == cout and R.bnred_fuse:
-            bpart = _empty(2 * Pf * cout, x.device)
-            _timed(R, "k_conv3x3_wino4f<bnred>", flops, lambda: check(
-                lib.cvk_conv3x3_wino4f_bnred(x.data_ptr(), Uf.data_ptr(), y.data_ptr(), N, H, W, k_ch, cout, ldy, *bnred[:5],
-                                             bpart.data_ptr(), R.launch_wgs(), s), "cvk_conv3x3_wino4f_bnred"), executed=0.5 * flops)
-            bnred[5].append((bpart, Pf))
-            return None
-        if want_planes and keep_v is not None and dgrad_of is None:
-            # forward launch of a layer whose weight-grad runs the plane GEMM (csrc/wgradp.hip): the kernel's staging path leaves V = B^T d
-            # behind as six slice-major planes, kept for the backward pass like the 2-D path's V
-            rows6 = lib.cvk_wgradp_plane_rows(N, H, W)
-            V6 = _empty(6 * rows6 * k_ch, x.device)
-            V6.cvk_sm = True
-            check(lib.cvk_wgradp_zero_pads_sm(V6.data_ptr(), N, H, W, k_ch, s), "cvk_wgradp_zero_pads_sm")
-            _timed(R, "k_conv3x3_wino4f<vplanes>", flops, lambda: check(
-                lib.cvk_conv3x3_wino4f_vplanes(x.data_ptr(), Uf.data_ptr(), bias, y.data_ptr(), sp, cnt, V6.data_ptr(), N, H, W, k_ch, cout, ldy,
-                                               R.launch_wgs(), s), "cvk_conv3x3_wino4f_vplanes" + what), executed=0.5 * flops)
-            keep_v.append(V6)
-            return (Pf, cnt) if sp is not None else None
-        _timed(R, "k_conv3x3_wino4f", flops, lambda: check(
-            lib.cvk_conv3x3_wino4f(x.data_ptr(), Uf.data_ptr(), bias, y.data_ptr(), sp, cnt, N, H, W, k_ch, cout, ldy, R.launch_wgs(), s),
-            "cvk_conv3x3_wino4f" + what), executed=0.5 * flops)
-        return (Pf, cnt) if sp is not None else None
-    if use4:
-        def build_u4():
-            u = _empty(6 * cout * 3 * k_ch, x.device)
-            if dgrad_of is not None and dgrad_of[1] == k_ch and dgrad_of[2] == cout:       # no channel padding on either side
-                _timed(R, "k_wino4_weight_dgrad", 4.0 * (9 + 18) * cout * k_ch, lambda: check(
-                    lib.cvk_wino4_weight_transform_dgrad(dgrad_of[0].data_ptr(), u.data_ptr(), dgrad_of[1], dgrad_of[2], s),
-                    "cvk_wino4_weight_transform_dgrad"), "byte")
-            else:
-                wt = w() if callable(w) else w
-                _timed(R, "k_wino4_weight", 4.0 * (9 + 18) * cout * k_ch, lambda: check(
-                    lib.cvk_wino4_weight_transform(wt.data_ptr(), u.data_ptr(), cout, k_ch, s), "cvk_wino4_weight_transform"), "byte")
+                _timed(R, "k_wino4f_weight", 4.0 * (9 + 18) * cout * k_ch, lambda: check(lib.cvk_wino4f_weight_transform(
+                    wt.data_ptr(), u.data_ptr(), cout, k_ch, dg, s), "cvk_wino4f_weight_transform" + ("(dgrad)" if dg else "")), "byte")
             return u
-        U = cached("w4", build_u4)
+        U = self._filter("w4" + f, build, None if h2 else ("w4f", floats, cout, k_ch, 0, dg))
+        am = ()
+        if h2:
+            am_x = x_amax if x_amax is not None else absmax(R, x, M, k_ch, k_ch, s, "x")
+            am = (am_x.data_ptr(), am_w.data_ptr())
+        executed = (1.5 if h2 else 0.5) * flops        # 3 fp16 products per fp32 product / the F(4,3) saving
+        Pf = lib.cvk_wino4f_stat_partials(N, H, W)
+        cnt = self._counts(Pf)
+        if bnred is not None:
+            bpart = _empty(2 * Pf * cout, x.device)
+            name = "cvk_conv3x3_wino4%s_bnred" % f
+            _timed(R, "k_conv3x3_wino4%s<bnred>" % f, flops, lambda: check(getattr(lib, name)(
+                x.data_ptr(), U.data_ptr(), self.y.data_ptr(), *am, N, H, W, k_ch, cout, ldy, *bnred, bpart.data_ptr(), R.launch_wgs(), s), name),
+                executed=executed)
+            self.bnred_sums = (bpart, Pf)
+            return None
+        if vplanes:
+            self.v = _empty(6 * lib.cvk_wgradp_plane_rows(N, H, W) * k_ch, x.device)
+            check(lib.cvk_wgradp_zero_pads_sm(self.v.data_ptr(), N, H, W, k_ch, s), "cvk_wgradp_zero_pads_sm")
+            _timed(R, "k_conv3x3_wino4f<vplanes>", flops, lambda: check(
+                lib.cvk_conv3x3_wino4f_vplanes(x.data_ptr(), U.data_ptr(), self.bias, self.y.data_ptr(), self.sp, cnt, self.v.data_ptr(), N, H, W,
+                                               k_ch, cout, ldy, R.launch_wgs(), s), "cvk_conv3x3_wino4f_vplanes" + self.what), executed=executed)
+        else:
+            name = "cvk_conv3x3_wino4" + f
+            _timed(R, "k_conv3x3_wino4" + f, flops, lambda: check(getattr(lib, name)(
+                x.data_ptr(), U.data_ptr(), self.bias, self.y.data_ptr(), self.sp, cnt, *am, N, H, W, k_ch, cout, ldy, R.launch_wgs(), s),
+                name + self.what), executed=executed)
+        return (Pf, cnt) if self.sp is not None else None
+
+    def w4(self):
+        """Per-index F(4,3) GEMMs (csrc/wino4.hip) + output pass."""
+        R, lib, s, x, d = self.R, self.lib, self.s, self.x, self.dgrad_of
+        N, H, W, M, k_ch, cout, ldy = self.N, self.H, self.W, self.M, self.k_ch, self.cout, self.ldy
+
+        dg = d is not None and d[1] == k_ch and d[2] == cout          # no channel padding on either side: straight from the forward weights
+
+        def build():
+            u, wt = _empty(6 * cout * 3 * k_ch, x.device), d[0] if dg else (self.w() if callable(self.w) else self.w)
+            kind = "weight_transform_dgrad" if dg else "weight_transform"
+            _timed(R, "k_wino4_weight_dgrad" if dg else "k_wino4_weight", 4.0 * (9 + 18) * cout * k_ch, lambda: check(getattr(lib, "cvk_wino4_" + kind)(
+                wt.data_ptr(), u.data_ptr(), *((d[1], d[2]) if dg else (cout, k_ch)), s), "cvk_wino4_" + kind), "byte")
+            return u
+        U = self._filter("w4", build)
         ws = R.workspace(lib.cvk_conv3x3_wino4_workspace_bytes(N, H, W, k_ch, ldy), x.device)
         ksplit = lib.cvk_conv3x3_wino4_ksplit(N, H, W, k_ch, ldy)
-        _timed(R, conv_kernel_name("wino4", ldy), flops, lambda: check(
-            lib.cvk_conv3x3_wino4_gemm(x.data_ptr(), U.data_ptr(), ws.data_ptr(), N, H, W, k_ch, cout, ldy, s), "cvk_conv3x3_wino4_gemm" + what))
+        _timed(R, conv_kernel_name("wino4", ldy), self.flops, lambda: check(
+            lib.cvk_conv3x3_wino4_gemm(x.data_ptr(), U.data_ptr(), ws.data_ptr(), N, H, W, k_ch, cout, ldy, s), "cvk_conv3x3_wino4_gemm" + self.what))
         _timed(R, "k_wino4_output", (4.0 + 6.0 * ksplit) * M * ldy, lambda: check(
-            lib.cvk_wino4_output(ws.data_ptr(), bias, y.data_ptr(), sp, N, H, W, cout, ldy, ksplit, s), "cvk_wino4_output"), "byte")
-    else:
-        def build_u():
-            wt = w() if callable(w) else w
+            lib.cvk_wino4_output(ws.data_ptr(), self.bias, self.y.data_ptr(), self.sp, N, H, W, cout, ldy, ksplit, s), "cvk_wino4_output"), "byte")
+
+    def w2(self):
+        """F(2,3) GEMMs (csrc/wino.hip) + output pass."""
+        R, lib, s, x = self.R, self.lib, self.s, self.x
+        N, H, W, M, k_ch, cout, ldy = self.N, self.H, self.W, self.M, self.k_ch, self.cout, self.ldy
+
+        def build():
+            wt = self.w() if callable(self.w) else self.w
             u = _empty(4 * cout * 3 * k_ch, x.device)
             _timed(R, "k_wino_weight", 4.0 * (9 + 12) * cout * k_ch, lambda: check(
                 lib.cvk_wino_weight_transform(wt.data_ptr(), u.data_ptr(), cout, k_ch, s), "cvk_wino_weight_transform"), "byte")
             return u
-        U = cached("w", build_u)
+        U = self._filter("w", build)
         ws = R.workspace(lib.cvk_conv3x3_wino_workspace_bytes(N, H, W, ldy), x.device)
-        _timed(R, conv_kernel_name("wino", ldy), flops, lambda: check(
-            lib.cvk_conv3x3_wino_gemm(x.data_ptr(), U.data_ptr(), ws.data_ptr(), N, H, W, k_ch, cout, ldy, s), "cvk_conv3x3_wino_gemm" + what))
+        _timed(R, conv_kernel_name("wino", ldy), self.flops, lambda: check(
+            lib.cvk_conv3x3_wino_gemm(x.data_ptr(), U.data_ptr(), ws.data_ptr(), N, H, W, k_ch, cout, ldy, s), "cvk_conv3x3_wino_gemm" + self.what))
         _timed(R, "k_wino_output", 12.0 * M * ldy, lambda: check(
-            lib.cvk_wino_output(ws.data_ptr(), bias, y.data_ptr(), sp, N, H, W, cout, ldy, s), "cvk_wino_output"), "byte")
+            lib.cvk_wino_output(ws.data_ptr(), self.bias, self.y.data_ptr(), self.sp, N, H, W, cout, ldy, s), "cvk_wino_output"), "byte")
 
 
 def conv_kernel_name(kind, n_cols, k_ch=32):
@@ -599,76 +487,36 @@ class ConvBnRelu(Op):
             return out
         return R.derived(((self.pslot, "f"), "pack"), w, build)
 
-    def _wgrad2d(self, R):
-        """Does this layer's weight-grad run through the transposed 2-D F(4x4,3x3) (csrc/wino2d.hip)?  Channel-heavy layers:
-        25-40 % faster than the transposed F(4,3) from 256 x 256 channels up (tools/bench_conv.py ww2d)."""
-        src, C = self.src, self.cout
-        if not (R.wino and src.ld % 4 == 0 and C % 4 == 0 and pad4(C) == C and src.ld >= 32 and C >= 64 and R.wino2d):
-            return False
-        if R.wino2d == "always" or wgrad2d_pays(src.N, src.H, src.W, src.ld, C):
-            return True
-        # 128 <-> 256 channels at 180x240: the x transform alone makes it a tie with the transposed F(4,3), but the forward
-        # pass of these layers already runs the 2-D path and leaves V behind (0.78 of the F(4,3) time without that pass; 6x6 tiles: 0.46)
-        return (wino_ok(R, src.ld, pad4(C)) and wino2d_ok(src.ld, C, pad4(C)) and wino2d_pays(src.N, src.H, src.W, src.ld, C, R.w2tile)
-                and src.ld * C >= 32768)
-
-    def _split3(self, R):
-        """Does this layer run the OPT-IN split-operand GEMMs (runner.w2d_split; csrc/split3.hip)?  Only layers whose forward, data-grad
-        and weight-grad ALL take the 2-D path with one tile size and whose channel counts the split weight-grad GEMM serves — the three
-        GEMMs of such a layer share their split planes (V from the forward transform, V' and E from one pass over dy)."""
-        if not split_fmt(R) or not self.src_needs_grad:
-            return False
-        src, C = self.src, self.cout
-        N, H, W, ldy = src.N, src.H, src.W, pad4(self.cout)
-        if not (self._wgrad2d(R) and R.w2both and ldy == C and src.ld == self.cin and src.ld % 32 == 0 and C % 32 == 0):
-            return False
-        if not (wino_ok(R, src.ld, ldy) and wino2d_ok(src.ld, C, ldy) and (R.wino2d == "always" or wino2d_pays(N, H, W, src.ld, C, R.w2tile))):
-            return False
-        if not (wino_ok(R, ldy, src.ld) and wino2d_ok(ldy, src.ld, src.ld) and (R.wino2d == "always" or wino2d_pays(N, H, W, ldy, src.ld, R.w2tile))):
-            return False
-        if layer_tile(R, N, H, W) != layer_tile(R, N, H, W, dgrad=True):
-            return False
-        return (C % 256 == 0 and src.ld % 128 == 0) or (src.ld % 256 == 0 and C % 128 == 0)
-
-    def _wgrad4(self, R):
-        """Does this layer's weight-grad run through the transposed F(4,3) (when the 2-D path does not take it)?"""
-        return bool(R.wino and self.src.ld >= 32 and self.cout > 32 and (R.wino4 == "always" or (R.wino4 and self.src.ld >= 64)))
-
-    def _want_planes(self, R, st):
-        """Should the fused forward launch (if that is the kernel the layer runs) leave the weight-grad's V planes behind?"""
-        src, C = self.src, self.cout
-        return bool(st.need_grad and R.vplanes and R.wgradp and split_fmt(R) == 0 and self._wgrad4(R) and not self._wgrad2d(R)
-                    and wgradp_ok(src.ld, C, pad4(C)) and vplanes_pays(src.N, src.H, src.W, src.ld, C))
-
-    def _conv(self, R, st, X, wk, b, y, stats, kind, keep_v=None):
-        """y = conv3x3(X, wk) + b (+ BN statistics partials): Winograd kernels when eligible, else direct."""
+    def _conv(self, R, st, rt, X, wk, b, y, stats):
+        """y = conv3x3(X, wk) + b (+ BN statistics partials) through the route's forward family.  Returns (counts, kept): (count, pointer)
+        when the partials carry pixel counts; (V, its amax block) when the route keeps the input transform for the weight-grad."""
         lib, s, src = R.lib, st.stream, self.src
         N, H, W, M, C, ldy = src.N, src.H, src.W, src.M, self.cout, pad4(self.cout)
         sp = stats.data_ptr() if stats is not None else None
-        if (R.thin and lib.cvk_thin_fwd_supported(src.ld, C, ldy) and (sp is None or src.ld <= 8 or src.ld == 64)
-                and H * W * max(src.ld, ldy) * 4 < 2 ** 31):       # one image per buffer resource
-            # the stem (3 -> 64) and the classifier head (64 -> 12): csrc/thin.hip, the thin side is one side of a 16x16x4 MFMA
+        flops = 18.0 * M * C * self.cin
+        if rt.fwd == "thin":
             Pt = lib.cvk_thin_stat_partials(N, H, W, src.ld)
             cnt = sp + 4 * 2 * Pt * C if sp is not None else None
             head = src.ld == 64
-            _timed(R, "k_thin_co_fwd" if head else "k_thin_ci_fwd", 18.0 * M * C * self.cin, lambda: check(
+            _timed(R, "k_thin_co_fwd" if head else "k_thin_ci_fwd", flops, lambda: check(
                 lib.cvk_conv3x3_thin_fwd(X.data_ptr(), wk.data_ptr(), b.data_ptr(), y.data_ptr(), sp, cnt, N, H, W, src.ld, C, ldy, s),
                 "cvk_conv3x3_thin_fwd"), executed=18.0 * M * (16 * self.cin if head else C * src.ld), nbytes=4.0 * M * (src.ld + ldy))
-            return (Pt, cnt) if sp is not None else None
-        if wino_ok(R, src.ld, ldy):
-            return wino_conv(R, lib, s, X, wk, b.data_ptr(), y, sp, N, H, W, src.ld, C, ldy, 18.0 * M * C * self.cin, keep_v=keep_v,
-                             wsrc=st.params[4 * self.pslot], ck=(self.pslot, "f"), split=split_fmt(R) if (st.need_grad and st.training and self._split3(R)) else 0, x_amax=st.amax.get(src.id),
-                             h2=split_fmt(R) == 2 and st.need_grad and st.training, want_planes=keep_v is not None and self._want_planes(R, st))
-        else:
-            _timed(R, conv_kernel_name("fwd", ldy, src.ld), 18.0 * M * C * self.cin, lambda: check(
+            return ((Pt, cnt) if sp is not None else None), None
+        if rt.fwd == "direct":
+            _timed(R, conv_kernel_name("fwd", ldy, src.ld), flops, lambda: check(
                 lib.cvk_conv3x3_fwd(X.data_ptr(), wk.data_ptr(), b.data_ptr(), y.data_ptr(), sp, N, H, W, src.ld, C, ldy, s),
                 "cvk_conv3x3_fwd"))
+            return None, None
+        c = WinoConv(R, s, X, wk, b.data_ptr(), y, sp, N, H, W, src.ld, C, ldy, flops, st.params[4 * self.pslot], (self.pslot, "f"))
+        counted = c.run(rt.fwd, rt.tile, rt.split, keep=rt.keeps_v, x_amax=st.amax.get(src.id))
+        return counted, ((c.v, c.v_amax) if rt.keeps_v else None)
 
     def fwd(self, R, st):
         if st.plan.bf16:
             return self._fwd_bf16(R, st)
         lib, s = R.lib, st.stream
         src, dst = self.src, self.dst
+        rt = st.routes[self.idx]
         X = st.act[src.id]
         w, b, gamma, beta = st.params[4 * self.pslot:4 * self.pslot + 4]
         dev = X.device
@@ -679,14 +527,13 @@ class ConvBnRelu(Op):
         bnp = _empty(4 * ldy, dev)                      # mean | rstd | scale | shift
         pm, pr, psc, psh = (bnp.data_ptr() + 4 * ldy * i for i in range(4))
         conv, bn = self.holder.conv_bn()
-        keep_v = [] if (st.need_grad and (self._wgrad2d(R) or self._want_planes(R, st))) else None      # transformed input, reused by the weight-grad
         if st.training:
             P = (M + _lib.CVK_STAT_ROWS - 1) // _lib.CVK_STAT_ROWS
             Pm = max(P, lib.cvk_w2d_stat_partials(N, H, W), lib.cvk_w6_stat_partials(N, H, W), lib.cvk_thin_stat_partials(N, H, W, src.ld))   # room for any partial layout (+ counts)
             stats = _empty(2 * Pm * C + Pm, dev)
             if M <= 1:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size {[N, C, H, W]}")
-            counted = self._conv(R, st, X, wk, b, y, stats, "fwd", keep_v=keep_v)
+            counted, kept = self._conv(R, st, rt, X, wk, b, y, stats)
             wsb = lib.cvk_bn_finalize_workspace_bytes(Pm, C)
             ws = R.workspace(wsb, dev)
             track = bn.track_running_stats and bn.running_mean is not None
@@ -701,7 +548,7 @@ class ConvBnRelu(Op):
                                                  pm, pr, psc, psh, *run, mom, float(bn.eps), ws.data_ptr(), wsb, s),
                       "cvk_bn_finalize_counts")
         else:
-            self._conv(R, st, X, wk, b, y, None, "fwd", keep_v=keep_v)
+            _, kept = self._conv(R, st, rt, X, wk, b, y, None)
             check(lib.cvk_bn_eval_params(gamma.data_ptr(), beta.data_ptr(), bn.running_mean.data_ptr(),
                                          bn.running_var.data_ptr(), pm, pr, psc, psh, C, float(bn.eps), s), "cvk_bn_eval_params")
         out = R.alloc_act(st, dst.buf, dev)
@@ -736,18 +583,50 @@ class ConvBnRelu(Op):
                 _timed(R, "k_bn_relu_apply", 8.0 * M * C, lambda: check(
                     lib.cvk_bn_relu_apply(y.data_ptr(), ldy, psc, psh, dst.cview(out), N, H, W, C, s), "cvk_bn_relu_apply"), "byte")
         if st.need_grad:
-            st.saved[self.idx] = (y, bnp, keep_v[0] if keep_v else None)
+            st.saved[self.idx] = (y, bnp, rt, kept)
+
+    # BatchNorm-backward passes that also write the weight-grad's transformed dy (route bn_bwd): mode of cvk_bn_bwd_dx_e_amax, the entry point
+    # without the amax word, plane bytes written per 4-column group and channel
+    _BN_E = {"dx+E": (0, "cvk_bn_bwd_dx_e", 16.0), "dx+E6": (1, "cvk_bn_bwd_dx_e6", 24.0), "dx+E4p": (2, "cvk_bn_bwd_dx_e4p", 16.0)}
+
+    def _bn_bwd(self, R, st, kind, head, part, PB, gb, want_amax):
+        """BatchNorm + ReLU backward (csrc/bn.hip): dy from dO and, for kind != "dx" (route bn_bwd), the weight-grad's E planes in the same pass.
+        head: cvk_bn_bwd_dx's arguments before the partials.  Returns (planes, amax block of dy if want_amax); planes None after the plain
+        pass, which also runs when a planes pass refuses the layout (rc != 0: a strided view) — the weight-grad then transforms dy itself."""
+        lib, s, src = R.lib, st.stream, self.src
+        N, H, W, M, C, ldy = src.N, src.H, src.W, src.M, self.cout, pad4(self.cout)
+        tail = (part.data_ptr(), N, H, W, C, 1 if st.training else 0)
+        if kind != "dx":
+            mode, plain, eb = self._BN_E[kind]
+            if kind == "dx+E":
+                E = _empty(4 * N * H * ((W + 3) // 4) * ldy, st.device)
+            else:
+                E = _empty((4 if mode == 2 else 6) * lib.cvk_wgradp_plane_rows(N, H, W) * C, st.device)
+                check((lib.cvk_wgradp_zero_pads4 if mode == 2 else lib.cvk_wgradp_zero_pads)(E.data_ptr(), N, H, W, C, s), "cvk_wgradp_zero_pads")
+            blk = st.amax_spare[-1] if want_amax else None
+            rc = _timed(R, "k_bn_bwd<%s>" % kind, (12.0 * M + eb * N * H * ((W + 3) // 4)) * C, lambda: (
+                lib.cvk_bn_bwd_dx_e_amax(mode, *head, E.data_ptr(), *tail, blk.data_ptr(), s) if blk is not None
+                else getattr(lib, plain)(*head, E.data_ptr(), *tail, s)), "byte")
+            if rc == 0:
+                R.defer_colsum(st, part, lib.cvk_bn_bwd_e_blocks(N, H, W), C, gb)     # conv bias grad: finalised with the others, in one launch
+                return E, (st.amax_spare.pop() if blk is not None else None)
+        am = st.amax_spare.pop() if want_amax else None         # a zeroed word: the pass that writes dy leaves its largest magnitude there
+        fn, extra = ("cvk_bn_bwd_dx_amax", (am.data_ptr(),)) if am is not None else ("cvk_bn_bwd_dx", ())
+        _timed(R, "k_bn_bwd<dx>", 12.0 * M * C, lambda: check(getattr(lib, fn)(*head, *tail, *extra, s), fn), "byte")
+        R.defer_colsum(st, part, PB, C, gb)
+        return None, am
 
     def bwd(self, R, st):
         if st.plan.bf16:
             return self._bwd_bf16(R, st)
         lib, s = R.lib, st.stream
         src, dst = self.src, self.dst
-        y, bnp, Vkept = st.saved.pop(self.idx)
+        y, bnp, rt, kept = st.saved.pop(self.idx)
         X = st.act[src.id]
         dev = X.device
         N, H, W = src.N, src.H, src.W
         M, C, ldy = src.M, self.cout, pad4(self.cout)
+        flops = 18.0 * M * C * self.cin
         pm, pr, psc, psh = (bnp.data_ptr() + 4 * ldy * i for i in range(4))
         w = st.params[4 * self.pslot]
         gw, gb, gg, gbe = R.grad_ptrs(st, self.pslot)
@@ -762,122 +641,38 @@ class ConvBnRelu(Op):
                 lib.cvk_bn_bwd_reduce(dO, y.data_ptr(), ldy, psc, psh, pm, pr, part.data_ptr(), N, H, W, C, s), "cvk_bn_bwd_reduce"), "byte")
             check(lib.cvk_colsum_finalize(part.data_ptr(), PB, C, gbe, gg, s), "cvk_colsum_finalize")   # dbeta, dgamma
         del pre
-        # round 6: with V planes from the forward launch the plane GEMM reads E0 / E5 (columns of dy) from dy itself — dy then carries a zeroed slack
-        # behind its last row (cvk_wgradp_gemm_sm_dy) and the BatchNorm-backward pass writes four E planes instead of six
-        planes_kept = Vkept is not None and getattr(Vkept, "cvk_sm", False) and Vkept.numel() == 6 * lib.cvk_wgradp_plane_rows(N, H, W) * src.ld
-        e4p = bool(planes_kept and ldy == C and W % 4 == 0 and R.wgradp and R.e4p and self._wgrad4(R) and not self._wgrad2d(R) and wgradp_ok(src.ld, C, ldy))
-        if e4p:
-            slack = lib.cvk_wgradp_dy_slack(W) * ldy
-            dyb = _empty(M * ldy + slack, dev)
+        if rt.bn_bwd == "dx+E4p":
+            # the plane GEMM reads E0 / E5 (columns of dy) from dy itself: dy carries a zeroed slack behind its last row (cvk_wgradp_gemm_sm_dy)
+            dyb = _empty(M * ldy + lib.cvk_wgradp_dy_slack(W) * ldy, dev)
             dyb[M * ldy:].zero_()
             dy = dyb[:M * ldy]
         else:
             dy = torch.zeros(M * ldy, device=dev, dtype=_F32) if ldy != C else _empty(M * ldy, dev)
-        # layers whose weight-grad runs through the transposed F(4,3) get its transformed dy planes E1..E4 from this pass
-        wgrad4 = self._wgrad4(R)
-        # channel-heavy layers: transposed 2-D F(4x4,3x3), 36 GEMMs over the tile index (25-40 % faster than the transposed
-        # F(4,3) from 256x256 channels up: tools/bench_conv.py ww2d); it transforms dy itself, so no E planes are needed
-        wgrad2d = self._wgrad2d(R)
-        wgrad4 = wgrad4 and not wgrad2d
-        # 64-input-channel layers: both transforms outside the GEMM (csrc/wgradp.hip) — the E planes come from this pass, the V
-        # planes cost one pass over x; pays while that pass is cheap (measured: 64 -> 64 @360x480 0.74x, 64 -> 128 @180x240 0.7x
-        # the time of the transposed F(4,3) kernel; 128 input channels: the V pass eats the gain)
-        # round 6: when the fused forward launch left V behind (slice-major planes), every such layer takes the plane GEMM and no pass over x runs
-        have_planes = planes_kept
-        wgradp = wgrad4 and R.wgradp and wgradp_ok(src.ld, C, ldy) and (R.wgradp == "always" or have_planes or wgradp_pays(N, H, W, src.ld, C))
-        E = None
-        E6 = None
-        am_dy_fused = None
-        want_amax = split_fmt(R) == 2 and st.training and bool(st.amax_spare) and self.src_needs_grad
-        if wgradp:
-            e4p = e4p and have_planes
-            rows6 = lib.cvk_wgradp_plane_rows(N, H, W)
-            E6 = _empty((4 if e4p else 6) * rows6 * C, dev)
-            check((lib.cvk_wgradp_zero_pads4 if e4p else lib.cvk_wgradp_zero_pads)(E6.data_ptr(), N, H, W, C, s), "cvk_wgradp_zero_pads")
-            PBe = lib.cvk_bn_bwd_e_blocks(N, H, W)
-            blk = st.amax_spare[-1] if want_amax else None      # the opt-in fp16 data-grad scales by the largest |dy|: left by this pass
-            ebytes = (12.0 * M + (16.0 if e4p else 24.0) * N * H * ((W + 3) // 4)) * C
-            if blk is not None:
-                rc = _timed(R, "k_bn_bwd<dx+E4p>" if e4p else "k_bn_bwd<dx+E6>", ebytes, lambda: lib.cvk_bn_bwd_dx_e_amax(
-                    2 if e4p else 1, dO, y.data_ptr(), ldy, psc, psh, pm, pr, gg, gbe, dy.data_ptr(), ldy, E6.data_ptr(), part.data_ptr(),
-                    N, H, W, C, 1 if st.training else 0, blk.data_ptr(), s), "byte")
-            else:
-                rc = _timed(R, "k_bn_bwd<dx+E4p>" if e4p else "k_bn_bwd<dx+E6>", ebytes, lambda: (lib.cvk_bn_bwd_dx_e4p if e4p else lib.cvk_bn_bwd_dx_e6)(
-                    dO, y.data_ptr(), ldy, psc, psh, pm, pr, gg, gbe, dy.data_ptr(), ldy, E6.data_ptr(), part.data_ptr(),
-                    N, H, W, C, 1 if st.training else 0, s), "byte")
-            if rc == 0:
-                R.defer_colsum(st, part, PBe, C, gb)           # conv bias grad: finalised with the others, in one launch
-                if blk is not None:
-                    am_dy_fused = st.amax_spare.pop()
-            else:
-                E6 = None           # layout not vectorisable (strided view): plain pass below, the weight-grad transforms dy itself
-        if E6 is None and wgrad4 and not wgradp and ldy == C and C % 4 == 0:
-            E = _empty(4 * N * H * ((W + 3) // 4) * ldy, dev)
-            PBe = lib.cvk_bn_bwd_e_blocks(N, H, W)
-            blk = st.amax_spare[-1] if want_amax else None
-            if blk is not None:
-                rc = _timed(R, "k_bn_bwd<dx+E>", (12.0 * M + 16.0 * N * H * ((W + 3) // 4)) * C, lambda: lib.cvk_bn_bwd_dx_e_amax(
-                    0, dO, y.data_ptr(), ldy, psc, psh, pm, pr, gg, gbe, dy.data_ptr(), ldy, E.data_ptr(), part.data_ptr(),
-                    N, H, W, C, 1 if st.training else 0, blk.data_ptr(), s), "byte")
-            else:
-                rc = _timed(R, "k_bn_bwd<dx+E>", (12.0 * M + 16.0 * N * H * ((W + 3) // 4)) * C, lambda: lib.cvk_bn_bwd_dx_e(
-                    dO, y.data_ptr(), ldy, psc, psh, pm, pr, gg, gbe, dy.data_ptr(), ldy, E.data_ptr(), part.data_ptr(),
-                    N, H, W, C, 1 if st.training else 0, s), "byte")
-            if rc == 0:
-                R.defer_colsum(st, part, PBe, C, gb)           # conv bias grad: finalised with the others, in one launch
-                if blk is not None:
-                    am_dy_fused = st.amax_spare.pop()
-            else:
-                E = None            # layout not vectorisable (strided view): plain pass below, wgrad transforms dy itself
-        if E is None and E6 is None:
-            if want_amax:
-                am_dy_fused = st.amax_spare.pop()       # a zeroed word: the pass that writes dy leaves its largest magnitude there
-                _timed(R, "k_bn_bwd<dx>", 12.0 * M * C, lambda: check(
-                    lib.cvk_bn_bwd_dx_amax(dO, y.data_ptr(), ldy, psc, psh, pm, pr, gg, gbe, dy.data_ptr(), ldy, part.data_ptr(),
-                                           N, H, W, C, 1 if st.training else 0, am_dy_fused.data_ptr(), s), "cvk_bn_bwd_dx_amax"), "byte")
-            else:
-                _timed(R, "k_bn_bwd<dx>", 12.0 * M * C, lambda: check(
-                    lib.cvk_bn_bwd_dx(dO, y.data_ptr(), ldy, psc, psh, pm, pr, gg, gbe, dy.data_ptr(), ldy, part.data_ptr(),
-                                      N, H, W, C, 1 if st.training else 0, s), "cvk_bn_bwd_dx"), "byte")
-            R.defer_colsum(st, part, PB, C, gb)             # conv bias grad: finalised with the others, in one launch
+        E, am_dy = self._bn_bwd(R, st, rt.bn_bwd, (dO, y.data_ptr(), ldy, psc, psh, pm, pr, gg, gbe, dy.data_ptr(), ldy), part, PB, gb,
+                                rt.dy_amax and bool(st.amax_spare))
         del y
-        # weight-grad AND data-grad on the 2-D path with the same tile: dy is transformed for both in ONE launch (csrc/wino2d.hip
-        # k_w2d_dy_both): E for the weight-grad, V' for the data-grad; dy crosses the fabric once
-        both2 = None
-        fmt = split_fmt(R) if (wgrad2d and st.training and self._split3(R)) else 0
-        pdt = {3: _BF16, 2: torch.float16}.get(fmt)
-        split3 = fmt if (fmt and Vkept is not None and Vkept.dtype == pdt) else 0
-        if split3:
-            tile = layer_tile(R, N, H, W)
+        V, am_v = kept if kept is not None else (None, None)
+        # 2-D data-grad and weight-grad with the same tile: dy is transformed for both in ONE launch (csrc/wino2d.hip k_w2d_dy_both): E for
+        # the weight-grad, V' for the data-grad; dy crosses the fabric once
+        Eb = Vb = None
+        if rt.dy_both:
+            tile, fmt = rt.tile, rt.split
             NX = 64 if tile == 6 else 36
             T = w2fn(lib, tile, "tiles")(N, H, W)
-            Tp = lib.cvk_split3_rows_pad(T, 256)
-            tag = "split3" if fmt == 3 else "split2h"
-            Eb = torch.empty(NX * (C // 32) * fmt * Tp * 32, device=dev, dtype=pdt)
-            Vb = torch.empty(NX * (C // 32) * fmt * Tp * 32, device=dev, dtype=pdt)
-            am_dy = am_dy_fused
-            if fmt == 2 and am_dy is None:
-                am_dy = amax_blocks(lib, 1, dev)[0]
-                _timed(R, "k_absmax", 4.0 * M * C, lambda: check(lib.cvk_absmax_f32(dy.data_ptr(), M, C, ldy, am_dy.data_ptr(), s), "cvk_absmax_f32(dy)"), "byte")
-            Eb.cvk_amax = Vb.cvk_amax = am_dy
-            _timed(R, "k_w2d_dy<both,%s>" % tag, (4.0 * M + 4.0 * fmt * NX * T) * C, lambda: check(
-                lib.cvk_w2d_dy_transform_both_split(fmt, tile, dy.data_ptr(), ldy, Vb.data_ptr(), Eb.data_ptr(), 1,
-                                                    am_dy.data_ptr() if am_dy is not None else None, N, H, W, C, s),
-                "cvk_w2d_dy_transform_both_split"), "byte")
-            both2 = (tile, Eb, Vb)
-        elif Vkept is not None and Vkept.dtype in (_BF16, torch.float16):
-            Vkept = None            # the forward pass ran a split path but this backward pass does not run the same (a knob changed in between)
-        if (not split3 and wgrad2d and self.src_needs_grad and R.w2both and ldy == C and wino_ok(R, ldy, src.ld) and wino2d_ok(ldy, src.ld, src.ld)
-                and (R.wino2d == "always" or (R.wino2d and wino2d_pays(N, H, W, ldy, src.ld, R.w2tile)))
-                and layer_tile(R, N, H, W) == layer_tile(R, N, H, W, dgrad=True)):
-            tile = layer_tile(R, N, H, W)
-            NX = 64 if tile == 6 else 36
-            T = w2fn(lib, tile, "tiles")(N, H, W)
-            Tp = lib.cvk_w2d_tpad(T)
-            Eb, Vb = _empty(NX * Tp * C + 128, dev), _empty(NX * Tp * C + 128, dev)
-            _timed(R, "k_w2d_dy<both>", 4.0 * (M + 2 * NX * T) * C, lambda: check(
-                w2fn(lib, tile, "dy_transform_both")(dy.data_ptr(), ldy, Vb.data_ptr(), Eb.data_ptr(), N, H, W, C, s), "cvk_w2d_dy_transform_both"), "byte")
-            both2 = (tile, Eb, Vb)
+            n, pdt = (NX * (C // 32) * fmt * lib.cvk_split3_rows_pad(T, 256) * 32, _BF16 if fmt == 3 else torch.float16) if fmt else \
+                (NX * lib.cvk_w2d_tpad(T) * C + 128, _F32)
+            Eb, Vb = torch.empty(n, device=dev, dtype=pdt), torch.empty(n, device=dev, dtype=pdt)
+            if fmt:
+                if fmt == 2 and am_dy is None:
+                    am_dy = absmax(R, dy, M, C, ldy, s, "dy")
+                _timed(R, "k_w2d_dy<both,%s>" % ("split3" if fmt == 3 else "split2h"), (4.0 * M + 4.0 * fmt * NX * T) * C, lambda: check(
+                    lib.cvk_w2d_dy_transform_both_split(fmt, tile, dy.data_ptr(), ldy, Vb.data_ptr(), Eb.data_ptr(), 1,
+                                                        am_dy.data_ptr() if am_dy is not None else None, N, H, W, C, s),
+                    "cvk_w2d_dy_transform_both_split"), "byte")
+            else:
+                _timed(R, "k_w2d_dy<both>", 4.0 * (M + 2 * NX * T) * C, lambda: check(
+                    w2fn(lib, tile, "dy_transform_both")(dy.data_ptr(), ldy, Vb.data_ptr(), Eb.data_ptr(), N, H, W, C, s),
+                    "cvk_w2d_dy_transform_both"), "byte")
         if self.src_needs_grad:
             if src.id in st.grad:
                 raise NotImplementedError("conv data-grad must be the first writer of its input's gradient buffer")
@@ -889,124 +684,102 @@ class ConvBnRelu(Op):
                     lib.cvk_pack_weight_dgrad(wc.data_ptr(), wd_.data_ptr(), C, self.cin, src.ld, ldy, s), "cvk_pack_weight_dgrad"), "byte")
                 return wd_
             dX = _empty(M * src.ld, dev).view(N, H, W, src.ld)
-            if wino_ok(R, ldy, src.ld):
-                # dX is the whole gradient of the producing block's activation when this conv is its only reader: the fused
-                # kernel then sums it for that block's BatchNorm backward on the way out (training-mode statistics only)
-                prod = st.plan.sole_producer(src) if st.training else None
-                bnred = None
-                if prod is not None and prod.idx in st.saved and pad4(prod.cout) == prod.cout == src.ld:
-                    py, pbnp = st.saved[prod.idx][0], st.saved[prod.idx][1]
-                    bnred = (py.data_ptr(), pbnp.data_ptr() + 8 * src.ld, pbnp.data_ptr() + 12 * src.ld, pbnp.data_ptr(),
-                             pbnp.data_ptr() + 4 * src.ld, [])
-                wino_conv(R, lib, s, dy, packed, None, dX, None, N, H, W, ldy, src.ld, src.ld, 18.0 * M * C * self.cin, "(dgrad)",
-                          dgrad_of=(wc, C, self.cin), wsrc=w, ck=(self.pslot, "d"), bnred=bnred,
-                          v_pre=(both2[0], both2[2]) if both2 is not None else None, split=split3, x_amax=am_dy_fused,
-                          h2=split_fmt(R) == 2 and st.training)
-                if bnred is not None and bnred[5]:
-                    st.bnred[prod.idx] = bnred[5][0]
-            elif R.thin and lib.cvk_thin_fwd_supported(ldy, src.ld, src.ld) and H * W * max(src.ld, ldy) * 4 < 2 ** 31:      # the head's data-grad: 12 -> 64 (csrc/thin.hip)
-                wd = R.derived(((self.pslot, "d"), "pack"), w, packed)
-                _timed(R, "k_thin_ci_fwd(dgrad)", 18.0 * M * C * self.cin, lambda: check(
+            wd = R.derived(((self.pslot, "d"), "pack"), w, packed) if rt.dgrad in ("thin", "direct") else None
+            if rt.dgrad == "thin":          # the head's data-grad: 12 -> 64 (csrc/thin.hip)
+                _timed(R, "k_thin_ci_fwd(dgrad)", flops, lambda: check(
                     lib.cvk_conv3x3_thin_fwd(dy.data_ptr(), wd.data_ptr(), None, dX.data_ptr(), None, None, N, H, W, ldy, src.ld, src.ld, s),
                     "cvk_conv3x3_thin_fwd(dgrad)"), executed=18.0 * M * ldy * src.ld, nbytes=4.0 * M * (src.ld + ldy))
-            else:
-                wd = R.derived(((self.pslot, "d"), "pack"), w, packed)
-                _timed(R, conv_kernel_name("dgrad", src.ld, ldy), 18.0 * M * C * self.cin, lambda: check(
+            elif rt.dgrad == "direct":
+                _timed(R, conv_kernel_name("dgrad", src.ld, ldy), flops, lambda: check(
                     lib.cvk_conv3x3_fwd(dy.data_ptr(), wd.data_ptr(), None, dX.data_ptr(), None, N, H, W, ldy, src.ld, src.ld, s),
                     "cvk_conv3x3_fwd(dgrad)"))
-            st.grad[src.id] = dX
-        if wgrad2d and split3:
-            tile, Eb3 = both2[0], both2[1]
-            NX = 64 if tile == 6 else 36
-            T = w2fn(lib, tile, "tiles")(N, H, W)
-            Tp = lib.cvk_split3_rows_pad(T, 256)
-            f = lib.cvk_w2d_gemm_tn_split3_ksplit(NX, Tp, src.ld, C)
-            ws = R.workspace(4 * f * NX * C * src.ld, dev)
-            am_e, am_v = getattr(Eb3, "cvk_amax", None), getattr(Vkept, "cvk_amax", None)
-            _timed(R, "k_gemm_tn_" + ("split3" if split3 == 3 else "split2h"), 18.0 * M * C * self.cin, lambda: check(
-                lib.cvk_w2d_gemm_tn_split(split3, tile, Eb3.data_ptr(), Vkept.data_ptr(), ws.data_ptr(), am_e.data_ptr() if am_e is not None else None,
-                                          am_v.data_ptr() if am_v is not None else None, NX, Tp, src.ld, C, s), "cvk_w2d_gemm_tn_split"),
-                executed=2.0 * (6 if split3 == 3 else 3) * NX * Tp * src.ld * C)
-            _timed(R, "k_w2d_wgrad_out", 4.0 * (NX * f + 9) * C * self.cin, lambda: check(
-                lib.cvk_w2d_wgrad_output_f(tile, ws.data_ptr(), gw, self.cin, src.ld, C, f, s), "cvk_w2d_wgrad_output_f"), "byte")
-            del Vkept
-        elif wgrad2d:
-            tile = layer_tile(R, N, H, W)
-            NX = 64 if tile == 6 else 36
-            T = w2fn(lib, tile, "tiles")(N, H, W)
-            Tp = lib.cvk_w2d_tpad(T)
-            vfl, efl = NX * Tp * src.ld + 128, NX * Tp * C + 128
-            f = w2fn(lib, tile, "wgrad_ksplit")(T, src.ld, C)
-            if Vkept is not None and Vkept.numel() != vfl:
-                Vkept = None            # forward ran with another tile size (the knob changed in between)
-            if Vkept is None:           # forward ran another kernel (e.g. the mode changed in between): transform x now
-                Vkept = _empty(vfl, dev)
-                _timed(R, "k_w2d_input", 4.0 * (M + NX * T) * src.ld, lambda: check(
-                    w2fn(lib, tile, "input_transform")(X.data_ptr(), Vkept.data_ptr(), N, H, W, src.ld, s), "cvk_w2d_input_transform(wgrad)"), "byte")
-            if both2 is not None and both2[0] == tile:      # E came with the data-grad's V'
-                ws = R.workspace(4 * (f * NX * C * src.ld), dev)
-                Ep, Pp = both2[1].data_ptr(), ws.data_ptr()
             else:
-                ws = R.workspace(4 * (efl + f * NX * C * src.ld), dev)
-                Ep, Pp = ws.data_ptr(), ws.data_ptr() + 4 * efl
-                _timed(R, "k_w2d_dy", 4.0 * (M + NX * T) * C, lambda: check(
-                    w2fn(lib, tile, "dy_transform")(dy.data_ptr(), ldy, Ep, N, H, W, C, s), "cvk_w2d_dy_transform"), "byte")
-            _timed(R, "k_w2d_gemm_tn", 18.0 * M * C * self.cin, lambda: check(
-                w2fn(lib, tile, "gemm_tn")(Ep, Vkept.data_ptr(), Pp, T, src.ld, C, s), "cvk_w2d_gemm_tn"), executed=2.0 * NX * Tp * src.ld * C)
-            _timed(R, "k_w2d_wgrad_out", 4.0 * (NX * f + 9) * C * self.cin, lambda: check(
-                w2fn(lib, tile, "wgrad_output")(Pp, gw, T, self.cin, src.ld, C, s), "cvk_w2d_wgrad_output"), "byte")
-            del Vkept
-        elif wgradp:
+                # dX is the whole gradient of the producing block's activation when this conv is its only reader: the fused kernel then sums
+                # it for that block's BatchNorm backward on the way out (training-mode statistics only)
+                prod = st.plan.sole_producer(src) if rt.dgrad_bnred else None
+                bnred = None
+                if prod is not None and prod.idx in st.saved and pad4(prod.cout) == prod.cout == src.ld:
+                    pb = st.saved[prod.idx][1].data_ptr()
+                    bnred = (st.saved[prod.idx][0].data_ptr(), pb + 8 * src.ld, pb + 12 * src.ld, pb, pb + 4 * src.ld)
+                c = WinoConv(R, s, dy, packed, None, dX, None, N, H, W, ldy, src.ld, src.ld, flops, w, (self.pslot, "d"), "(dgrad)",
+                             dgrad_of=(wc, C, self.cin))
+                c.run(rt.dgrad, rt.dgrad_tile, rt.split, v_pre=Vb, x_amax=am_dy, bnred=bnred)
+                if c.bnred_sums is not None:
+                    st.bnred[prod.idx] = c.bnred_sums
+            st.grad[src.id] = dX
+        if rt.wgrad in W2D:
+            tile = rt.tile
+            NX = 64 if tile == 6 else 36
+            T = w2fn(lib, tile, "tiles")(N, H, W)
+            if rt.wgrad == "w2d_split":
+                fmt = rt.split
+                Tp = lib.cvk_split3_rows_pad(T, 256)
+                f = lib.cvk_w2d_gemm_tn_split3_ksplit(NX, Tp, src.ld, C)
+                ws = R.workspace(4 * f * NX * C * src.ld, dev)
+                _timed(R, "k_gemm_tn_" + ("split3" if fmt == 3 else "split2h"), flops, lambda: check(
+                    lib.cvk_w2d_gemm_tn_split(fmt, tile, Eb.data_ptr(), V.data_ptr(), ws.data_ptr(), am_dy.data_ptr() if am_dy is not None else None,
+                                              am_v.data_ptr() if am_v is not None else None, NX, Tp, src.ld, C, s), "cvk_w2d_gemm_tn_split"),
+                    executed=2.0 * (6 if fmt == 3 else 3) * NX * Tp * src.ld * C)
+                _timed(R, "k_w2d_wgrad_out", 4.0 * (NX * f + 9) * C * self.cin, lambda: check(
+                    lib.cvk_w2d_wgrad_output_f(tile, ws.data_ptr(), gw, self.cin, src.ld, C, f, s), "cvk_w2d_wgrad_output_f"), "byte")
+            else:
+                Tp = lib.cvk_w2d_tpad(T)
+                vfl, efl = NX * Tp * src.ld + 128, NX * Tp * C + 128
+                f = w2fn(lib, tile, "wgrad_ksplit")(T, src.ld, C)
+                if V is None:           # the forward pass ran another family: transform x now
+                    V = _empty(vfl, dev)
+                    _timed(R, "k_w2d_input", 4.0 * (M + NX * T) * src.ld, lambda: check(
+                        w2fn(lib, tile, "input_transform")(X.data_ptr(), V.data_ptr(), N, H, W, src.ld, s), "cvk_w2d_input_transform(wgrad)"), "byte")
+                ws = R.workspace(4 * ((0 if Eb is not None else efl) + f * NX * C * src.ld), dev)
+                Ep, Pp = (Eb.data_ptr(), ws.data_ptr()) if Eb is not None else (ws.data_ptr(), ws.data_ptr() + 4 * efl)
+                if Eb is None:          # else E came with the data-grad's V'
+                    _timed(R, "k_w2d_dy", 4.0 * (M + NX * T) * C, lambda: check(
+                        w2fn(lib, tile, "dy_transform")(dy.data_ptr(), ldy, Ep, N, H, W, C, s), "cvk_w2d_dy_transform"), "byte")
+                _timed(R, "k_w2d_gemm_tn", flops, lambda: check(
+                    w2fn(lib, tile, "gemm_tn")(Ep, V.data_ptr(), Pp, T, src.ld, C, s), "cvk_w2d_gemm_tn"), executed=2.0 * NX * Tp * src.ld * C)
+                _timed(R, "k_w2d_wgrad_out", 4.0 * (NX * f + 9) * C * self.cin, lambda: check(
+                    w2fn(lib, tile, "wgrad_output")(Pp, gw, T, self.cin, src.ld, C, s), "cvk_w2d_wgrad_output"), "byte")
+        elif rt.wgrad in ("wgradp", "wgradp_sm"):
+            # transposed F(4,3) through transform-domain planes (csrc/wgradp.hip): V from the forward launch ("wgradp_sm", slice-major) or from
+            # a pass over x; E from the BatchNorm-backward pass, or from a pass over dy when that one fell back
+            own_v = rt.wgrad == "wgradp"
             rows6 = lib.cvk_wgradp_plane_rows(N, H, W)
             wsb = lib.cvk_wgradp_gemm_workspace_bytes(N, H, W, src.ld, C)
-            nE = 0 if E6 is not None else 6 * rows6 * C
-            nV = 0 if have_planes else 6 * rows6 * src.ld
+            nE = 0 if E is not None else 6 * rows6 * C
+            nV = 6 * rows6 * src.ld if own_v else 0
             ws = R.workspace(4 * (nV + nE) + wsb, dev)
-            V6p = Vkept.data_ptr() if have_planes else ws.data_ptr()
-            E6p = E6.data_ptr() if E6 is not None else ws.data_ptr() + 4 * nV
+            V6p = ws.data_ptr() if own_v else V.data_ptr()
+            E6p = E.data_ptr() if E is not None else ws.data_ptr() + 4 * nV
             slabp = ws.data_ptr() + 4 * (nV + nE)
-            if not have_planes:
+            if own_v:
                 _timed(R, "k_wgradp_planes", 4.0 * (M + 6.0 * rows6) * src.ld, lambda: check(
                     lib.cvk_wgradp_planes(X.data_ptr(), src.ld, V6p, N, H, W, src.ld, 0, s), "cvk_wgradp_planes(x)"), "byte")
-            if E6 is None:
+            if E is None:
                 _timed(R, "k_wgradp_planes", 4.0 * (M + 6.0 * rows6) * C, lambda: check(
                     lib.cvk_wgradp_planes(dy.data_ptr(), ldy, E6p, N, H, W, C, 1, s), "cvk_wgradp_planes(dy)"), "byte")
-            if e4p and E6 is not None:
-                _timed(R, "k_wgradp_gemm", 18.0 * M * C * self.cin, lambda: check(
-                    lib.cvk_wgradp_gemm_sm_dy(E6p, dy.data_ptr(), V6p, gw, N, H, W, self.cin, src.ld, C, slabp, wsb, s), "cvk_wgradp_gemm_sm_dy"),
-                    executed=9.0 * M * C * self.cin)
-            else:
-                gemm = lib.cvk_wgradp_gemm_sm if have_planes else lib.cvk_wgradp_gemm
-                _timed(R, "k_wgradp_gemm", 18.0 * M * C * self.cin, lambda: check(
-                    gemm(E6p, V6p, gw, N, H, W, self.cin, src.ld, C, slabp, wsb, s), "cvk_wgradp_gemm"), executed=9.0 * M * C * self.cin)
-            del Vkept
-        elif wgrad4:
+            sm_dy = rt.bn_bwd == "dx+E4p" and E is not None          # E0 / E5 read from dy
+            fn = "cvk_wgradp_gemm_sm_dy" if sm_dy else ("cvk_wgradp_gemm" if own_v else "cvk_wgradp_gemm_sm")
+            ev = (E6p, dy.data_ptr(), V6p) if sm_dy else (E6p, V6p)
+            _timed(R, "k_wgradp_gemm", flops, lambda: check(getattr(lib, fn)(*ev, gw, N, H, W, self.cin, src.ld, C, slabp, wsb, s), fn),
+                   executed=9.0 * M * C * self.cin)
+        elif rt.wgrad == "w4":
             # transposed F(4,3): fastest weight-grad on every layer with >= 64 input channels (tools/bench_conv.py wgrad wwino wwino4)
             wsb = lib.cvk_conv3x3_wgrad_wino4_workspace_bytes(N, H, W, src.ld, C, ldy)
             ws = R.workspace(wsb, dev)
-            _timed(R, f"k_wgrad_wino4<{'128' if C > 64 else '64'}, 128, 2, 2>", 18.0 * M * C * self.cin, lambda: check(
+            _timed(R, f"k_wgrad_wino4<{'128' if C > 64 else '64'}, 128, 2, 2>", flops, lambda: check(
                 lib.cvk_conv3x3_wgrad_wino4(X.data_ptr(), dy.data_ptr(), E.data_ptr() if E is not None else None, gw, N, H, W,
                                             self.cin, src.ld, C, ldy, ws.data_ptr(), wsb, s),
                 "cvk_conv3x3_wgrad_wino4"))
-        elif R.thin and lib.cvk_thin_wgrad_supported(self.cin, src.ld, C, ldy) and H * W * max(src.ld, ldy) * 4 < 2 ** 31:
-            wsb = lib.cvk_conv3x3_thin_wgrad_workspace_bytes(N, H, W, src.ld, C)
+        else:       # thin (the stem, the head: csrc/thin.hip), F(2,3) or the direct kernel: one entry-point signature
+            fn = {"thin": "cvk_conv3x3_thin_wgrad", "w2": "cvk_conv3x3_wgrad_wino", "direct": "cvk_conv3x3_wgrad"}[rt.wgrad]
+            wsb = getattr(lib, fn + "_workspace_bytes")(N, H, W, src.ld, C)
             ws = R.workspace(wsb, dev)
             head = src.ld == 64
-            _timed(R, "k_thin_co_wgrad" if head else "k_thin_ci_wgrad", 18.0 * M * C * self.cin, lambda: check(
-                lib.cvk_conv3x3_thin_wgrad(X.data_ptr(), dy.data_ptr(), gw, N, H, W, self.cin, src.ld, C, ldy, ws.data_ptr(), wsb, s),
-                "cvk_conv3x3_thin_wgrad"), executed=18.0 * M * (16 * self.cin if head else C * 16 / 3.0), nbytes=4.0 * M * (src.ld + ldy))
-        elif R.wino and src.ld >= 32 and C > 32 and (src.ld > 64 or C > 64):   # 64->64 layers: the direct kernel is faster
-            wsb = lib.cvk_conv3x3_wgrad_wino_workspace_bytes(N, H, W, src.ld, C)
-            ws = R.workspace(wsb, dev)
-            _timed(R, f"k_wgrad_wino<{'128' if C > 64 else '64'}, 128, 2, 2>", 18.0 * M * C * self.cin, lambda: check(
-                lib.cvk_conv3x3_wgrad_wino(X.data_ptr(), dy.data_ptr(), gw, N, H, W, self.cin, src.ld, C, ldy, ws.data_ptr(), wsb, s),
-                "cvk_conv3x3_wgrad_wino"))
-        else:
-            wsb = lib.cvk_conv3x3_wgrad_workspace_bytes(N, H, W, src.ld, C)
-            ws = R.workspace(wsb, dev)
-            _timed(R, conv_kernel_name("wgrad", C, src.ld), 18.0 * M * C * self.cin, lambda: check(
-                lib.cvk_conv3x3_wgrad(X.data_ptr(), dy.data_ptr(), gw, N, H, W, self.cin, src.ld, C, ldy, ws.data_ptr(), wsb, s),
-                "cvk_conv3x3_wgrad"))
+            name, kw = {"thin": ("k_thin_co_wgrad" if head else "k_thin_ci_wgrad",
+                                 dict(executed=18.0 * M * (16 * self.cin if head else C * 16 / 3.0), nbytes=4.0 * M * (src.ld + ldy))),
+                        "w2": (f"k_wgrad_wino<{'128' if C > 64 else '64'}, 128, 2, 2>", {}), "direct": (conv_kernel_name("wgrad", C, src.ld), {})}[rt.wgrad]
+            _timed(R, name, flops, lambda: check(getattr(lib, fn)(
+                X.data_ptr(), dy.data_ptr(), gw, N, H, W, self.cin, src.ld, C, ldy, ws.data_ptr(), wsb, s), fn), **kw)
         R.grads_ready(st, self.pslot)
 
     # ---- bf16-storage mode (BASELINE.json configs[3]; csrc/conv_bf16s.hip, csrc/elem_bf16.hip) ------------------------
@@ -1211,7 +984,7 @@ class MaxPool(Op):
         # BatchNorm-backward sums (csrc/pointwise.hip k_pool_scatter_bnred, csrc/elem_bf16.hip k_pool_bwd_bnred_bf16) and the block's reduce pass is
         # not launched
         prod = st.plan.ops[self.producer_idx] if (self.fused and self.producer_idx >= 0) else None
-        fuse_sums = (prod is not None and st.training and R.bnred_fuse and R.pool_bnred and isinstance(prod, ConvBnRelu) and prod.idx in st.saved
+        fuse_sums = (prod is not None and st.training and R.pool_bnred and isinstance(prod, ConvBnRelu) and prod.idx in st.saved
                      and prod.idx not in st.bnred and prod.dst.buf is v.buf
                      and (prod.dst.c0, prod.dst.C, prod.dst.y0, prod.dst.x0, prod.dst.H, prod.dst.W) == (v.c0, v.C, v.y0, v.x0, v.H, v.W)
                      and prod.cout == v.C and st.plan.last_gradient_writer(v, prod.idx) == self.idx)
@@ -1366,6 +1139,7 @@ class Plan:
         self.bufs, self.ops, self.holders = [], [], []
         self._producer = {}         # (buffer id, first channel) -> the ConvBnRelu op that writes that view
         self._readers = {}          # buffer id -> number of ops that read the buffer (each one adds to its gradient)
+        self.routes = {}            # (Runner.kernel_config(), training, need_grad) -> {op index: ConvRoute} (Runner.routes)
         self.input = self.new_buf(cin, H, W, "input")
         self.output = None
         self.input_needs_grad = False
@@ -1507,17 +1281,14 @@ class Runner:
         self.wino4f = WINO4F_DEFAULT
         self.wgradp = WGRADP_DEFAULT
         self.vplanes = VPLANES_DEFAULT      # fused forward launches leave the weight-grad's V planes behind (round 6)
-        self.e4p = os.environ.get("CVK_E4P", "1") != "0"    # ... and the plane GEMM reads E0 / E5 from dy: four E planes instead of six (round 6)
         self.thin = os.environ.get("CVK_THIN", "1") != "0"    # csrc/thin.hip for the stem and the classifier head
-        self.w2both = os.environ.get("CVK_W2D_DY_BOTH", "1") != "0"   # one launch transforms dy for the data-grad and the weight-grad
-        self.bnred_fuse = os.environ.get("CVK_BNRED_FUSE", "1") != "0"   # BN-backward sums in the fused data-grad's epilogue
-        self.pool_bnred = os.environ.get("CVK_POOL_BNRED", "1") != "0"   # ... and in the max-pool backward pass behind a conv block (round 6)
+        self.pool_bnred = os.environ.get("CVK_POOL_BNRED", "1") != "0"   # BN-backward sums in the max-pool backward pass behind a conv block (round 6)
         self.wino2d = WINO2D_DEFAULT
         # OPT-IN split-operand modes (cvk.set_split_operands): the matrix products of the fp32 convolutions on the 16-bit
         # matrix pipe with split fp32 operands (csrc/split_fmt.h).  Not the product default; bench.py names the mode in `dtype` when it is on.
         self.w2d_split = _split_mode_from_env()      # 0 off | 3: bf16 x 3 | 2: fp16 x 2
         self.w2tile_cfg = W2TILE_DEFAULT    # None = auto (see W2TILE_DEFAULT), 4 or 6 = forced
-        self.w2tile = 6                     # the tile of the plan being executed (set by forward / backward)
+        self.w2tile = 6                     # the tile of the plan being routed (set by routes)
         self.w2tile_dgrad = 6               # ... of its data-grad launches
         self.bf16 = False           # opt-in: bf16-storage mode (modules.set_conv_precision; BASELINE.json configs[3])
         self.wcache = WCACHE_DEFAULT
@@ -1569,11 +1340,11 @@ class Runner:
     def prebuild_fp32(self, plan, st, need_grad):
         """fp32 plans: the Winograd-domain filters the previous pass over this plan asked for (fused F(4,3): 16 per UNet step; 2-D forward
         and data-grad filters: 26), rebuilt in TWO launches (cvk_wino4f_weight_transform_batch, cvk_w2d_weight_transform_batch) instead
-        of 42 of 5-15 us each.  Which filters a layer needs is decided where the layer runs (wino_conv); that code records a job with
+        of 42 of 5-15 us each.  Which filters a layer needs follows from its route (WinoConv); the launcher records a job with
         every cached tensor it builds straight from a parameter, and this pass replays the record."""
         if not self.wcache or torch.cuda.is_current_stream_capturing():
             return
-        cfg = (id(plan), self.w2tile, self.w2tile_dgrad, self.wino, self.wino4, self.wino4f, self.wino2d, self.wgradp, self.vplanes, self.e4p, self.thin, self.w2d_split)
+        cfg = (id(plan),) + self.kernel_config()
         if cfg != self._wjobs_cfg:          # another plan or other kernel knobs: the record starts over with this pass
             self._wjobs, self._wjobs_cfg = {}, cfg
             return
@@ -1689,11 +1460,12 @@ class Runner:
         """fp16 split-operand mode (w2d_split = 2): the transforms of a split layer scale by the EXACT largest magnitude of the tensor they
         read (csrc/split_fmt.h).  Where every pass that writes a layer's input can leave that maximum on its way (BN-apply passes: csrc/bn.hip
         *_amax; bilinear upsampling: bounded by its input's maximum; the zero frame), the input's buffer gets a device word here and no extra
-        pass runs; any other input is measured by cvk_absmax_f32 in wino_conv.  One zero fill per step for all words."""
+        pass runs; any other input is measured by cvk_absmax_f32 in WinoConv.  One zero fill per step for all words."""
         if split_fmt(self) != 2 or plan.bf16 or not (st.training and st.need_grad):
             return
-        # every conv block that can run a split form: the 2-D Winograd layers (_split3) and the fused F(4,3) of the 64/128-channel levels
-        layers = [op for op in plan.ops if isinstance(op, ConvBnRelu) and (op._split3(self) or (op.src.ld % 32 == 0 and op.cout % 4 == 0))]
+        # every conv block that can run a split form: the 2-D split layers (route.split) and the fused F(4,3) of the 64/128-channel levels
+        routes = self.routes(plan, True, True)
+        layers = [op for op in plan.ops if isinstance(op, ConvBnRelu) and (routes[op.idx].split or (op.src.ld % 32 == 0 and op.cout % 4 == 0))]
         if not layers:
             return
 
@@ -1732,6 +1504,20 @@ class Runner:
             st.amax[buf.id] = blocks[i]
         st.amax_spare = blocks[len(want):]
 
+    def kernel_config(self):
+        """Every switch that changes which kernels run: the route cache, prebuild_fp32's job record and GraphedStep's signature key on it."""
+        return (self.wino, self.wino4, self.wino4f, self.wino2d, self.wgradp, self.vplanes, self.thin, self.pool_bnred, self.w2d_split,
+                self.w2tile_cfg)
+
+    def routes(self, plan, training, need_grad):
+        """{op index: route.ConvRoute} of the conv blocks of an fp32 plan, computed once per configuration and pass kind."""
+        key = (self.kernel_config(), training, need_grad)
+        r = plan.routes.get(key)
+        if r is None:
+            self.w2tile, self.w2tile_dgrad = self.tile_for(plan)
+            r = plan.routes[key] = {op.idx: conv_route(self, op, training, need_grad) for op in plan.ops if isinstance(op, ConvBnRelu)}
+        return r
+
     def tile_for(self, plan):
         """(forward / weight-grad tile, data-grad tile) of the 2-D path for a plan."""
         if self.w2tile_cfg in (4, 6):
@@ -1740,7 +1526,6 @@ class Runner:
 
     def forward(self, plan, x, params, training, need_grad):
         dev = x.device
-        self.w2tile, self.w2tile_dgrad = self.tile_for(plan)
         self._collectives_in_flight = False     # finish() of the previous backward waited for every collective
         st = RunState(params, training, need_grad)
         st.device = dev
@@ -1769,6 +1554,7 @@ class Runner:
         if plan.bf16:
             self.prepack_bf16(plan, st, need_grad)
         else:
+            st.routes = self.routes(plan, training, need_grad)
             self.prebuild_fp32(plan, st, need_grad)
             self.plan_amax(plan, st)
         for op in plan.ops:
@@ -1782,7 +1568,6 @@ class Runner:
 
     def backward(self, plan, st, gout):
         dev = gout.device
-        self.w2tile, self.w2tile_dgrad = self.tile_for(plan)
         st.stream = torch.cuda.current_stream(dev).cuda_stream
         self._pass_token = st.pass_token
         params = st.params

@@ -196,9 +196,7 @@ class GraphedStep:
 
     def _signature(self):
         R = self._runner
-        return (id(R.grad_sync), bool(self.net.training), bool(R.bf16), R.wino, R.wino4, R.wino4f, R.wgradp, R.wino2d, R.w2tile_cfg,
-                R.thin, R.persistent_wgs(), getattr(R, "w2d_split", False), getattr(R, "vplanes", None), getattr(R, "e4p", None),
-                getattr(R, "pool_bnred", None), getattr(R, "bnred_fuse", None)) + self._optimizer_signature()
+        return (id(R.grad_sync), bool(self.net.training), bool(R.bf16), R.persistent_wgs()) + R.kernel_config() + self._optimizer_signature()
 
     def _optimizer_signature(self):
         """The captured AdamW step writes the optimizer's flat buffers through raw pointers: the same optimizer, one parameter group, the

@@ -1,4 +1,4 @@
-"""Host logic of the opt-in split-operand modes (no GPU): which layers of the headline UNet plan run split GEMMs (ConvBnRelu._split3), which input
+"""Host logic of the opt-in split-operand modes (no GPU): which layers of the headline UNet plan run split GEMMs (route.ConvRoute.split), which input
 buffers get a device word for their largest magnitude from the passes that write them (Runner.plan_amax), and the switch itself."""
 import torch
 
@@ -46,16 +46,16 @@ def test_environment_switch_is_validated(monkeypatch, capsys):
             engine._split_mode_from_env()
 
 
-def test_thirteen_layers_run_the_split_gemms_and_none_by_default():
+def test_thirteen_layers_route_the_split_gemms_and_none_by_default():
     net = A.UNet(3, 12)
     plan = _headline_plan(net)
     R = runner_of(net)
-    R.w2tile, R.w2tile_dgrad = R.tile_for(plan)
     convs = [op for op in plan.ops if isinstance(op, engine.ConvBnRelu)]
     assert len(convs) == 23
-    assert not any(op._split3(R) for op in convs)
+    assert not any(R.routes(plan, True, True)[op.idx].split for op in convs)
     R.w2d_split = 2
-    split = [op for op in convs if op._split3(R)]
+    rts = R.routes(plan, True, True)
+    split = [op for op in convs if rts[op.idx].split]
     assert len(split) == 13                                           # the channel-heavy layers of DESIGN.md 5b
     for op in split:
         assert (op.cout % 256 == 0 and op.src.ld % 128 == 0) or (op.src.ld % 256 == 0 and op.cout % 128 == 0)
