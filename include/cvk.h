@@ -523,6 +523,29 @@ int cvk_adamw_hyper_fill(float lr, float beta1, float beta2, float eps, float we
 int cvk_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                        const cvk_adamw_hyper* hyper, void* stream);
 
+/* AdamW over a RANGE TABLE of the flat buffers (fine-tuning: frozen parameters, parameter groups, a step count per parameter).  `ranges`
+ * (DEVICE, nranges entries) lists the trainable ranges [offset, offset + length) of param / grad / exp_avg / exp_avg_sq, each with the
+ * index of the cvk_adamw_hyper record (one group's lr / betas / eps / weight decay and the bias corrections of one step count) that updates
+ * it; elements outside every range (frozen parameters and their moments) are neither read nor written.  The same element update as
+ * cvk_adamw_step in the same operation order: one range over the whole buffer with one record is bitwise cvk_adamw_step.
+ * cvk_adamw_plan_ranges (host function, no launch) checks a HOST copy of the table against the buffer length n and the record count and
+ * fills every block0 (the range's first workgroup); it returns the workgroup count the launches take as nblocks, or a negative error.
+ * The table uploaded to the device must be the planned one.
+ * cvk_adamw_step_ranges: the records as kernel arguments (eager; nhyper <= CVK_ADAMW_ARG_RECORDS, host array).
+ * cvk_adamw_step_ranges_dev: the records in DEVICE memory (nhyper of them), rewritten by the host between graph replays. */
+#define CVK_ADAMW_ARG_RECORDS 16
+typedef struct cvk_adamw_range {
+    int64_t offset;              /* first element of the range in the flat buffers */
+    int64_t length;              /* elements, > 0 */
+    int32_t hyper;               /* index of the cvk_adamw_hyper record */
+    int32_t block0;              /* first workgroup of the range (cvk_adamw_plan_ranges) */
+} cvk_adamw_range;
+int cvk_adamw_plan_ranges(cvk_adamw_range* ranges, int nranges, int64_t n, int nhyper);
+int cvk_adamw_step_ranges(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const cvk_adamw_range* ranges,
+                          int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper, void* stream);
+int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const cvk_adamw_range* ranges,
+                              int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper, void* stream);
+
 /* ---- the per-iteration training log (train.py:133-143 print of loss / lr / Beta1; utils.visulaize_lastlayer utils.py:33-36) -------
  * One single-workgroup launch appends the row [loss, lr, beta1, ||gw||_2, ||gb||_2] (fp32) to a DEVICE ring of `capacity` rows of 5
  * floats at row counter % capacity, then increments *counter (DEVICE int64).  loss: DEVICE scalar; hyper: DEVICE record (lr and

@@ -225,6 +225,9 @@ SIGNATURES = {
     "cvk_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_float, c_float, c_int, c_vp]),
     "cvk_adamw_hyper_fill": (c_int, [c_float, c_float, c_float, c_float, c_float, c_int, c_vp]),   # out: HOST AdamwHyper
     "cvk_adamw_step_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "cvk_adamw_plan_ranges": (c_int, [c_vp, c_int, c_i64, c_int]),                                   # HOST table (AdamwRange)
+    "cvk_adamw_step_ranges": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp]),   # HOST AdamwHyper array
+    "cvk_adamw_step_ranges_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
     "cvk_step_log": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp]),
 }
 
@@ -242,6 +245,11 @@ class AdamwHyper(ctypes.Structure):     # include/cvk.h cvk_adamw_hyper
                 ("weight_decay", ctypes.c_float), ("bc1", ctypes.c_float), ("bc2_sqrt", ctypes.c_float)]
 
 
+class AdamwRange(ctypes.Structure):     # include/cvk.h cvk_adamw_range
+    _fields_ = [("offset", ctypes.c_int64), ("length", ctypes.c_int64), ("hyper", ctypes.c_int32), ("block0", ctypes.c_int32)]
+
+
+ADAMW_ARG_RECORDS = 16                  # include/cvk.h CVK_ADAMW_ARG_RECORDS: records cvk_adamw_step_ranges takes as kernel arguments
 STEP_LOG_COLUMNS = 5                    # cvk_step_log row: loss, lr, beta1, ||gw||_2, ||gb||_2
 
 

@@ -547,6 +547,45 @@ __global__ void k_adamw_dev(float* __restrict__ p, const float* __restrict__ g, 
         adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
 }
 
+// AdamW over a range table (cvk_adamw_step_ranges*): workgroup b serves the range whose block0 is the last one <= b (a uniform binary
+// search over the table) and strides over it with that range's workgroups.  Both entry points run this body; `hyper` points at the
+// kernel-argument records (eager) or at device memory (graph replays).  Ranges outside [0, n) or with a record index outside [0, nhyper)
+// are skipped (cvk_adamw_plan_ranges refuses them on the host).
+struct AdamwArgRecords {
+    cvk_adamw_hyper r[CVK_ADAMW_ARG_RECORDS];
+};
+
+__device__ __forceinline__ void adamw_ranges_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
+                                                  const cvk_adamw_hyper* __restrict__ hyper, int nhyper) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = nr - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rt[mid].block0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const int64_t off = rt[lo].offset, len = rt[lo].length;
+    const int hx = rt[lo].hyper, b0 = rt[lo].block0;
+    const int nb = (lo + 1 < nr ? rt[lo + 1].block0 : (int)gridDim.x) - b0;
+    if (off < 0 || len <= 0 || off + len > n || hx < 0 || hx >= nhyper || nb <= 0 || b < b0) return;
+    const float lr = hyper[hx].lr, b1 = hyper[hx].beta1, b2 = hyper[hx].beta2, eps = hyper[hx].eps, wd = hyper[hx].weight_decay;
+    const float bc1 = hyper[hx].bc1, bc2_sqrt = hyper[hx].bc2_sqrt;
+    for (int64_t i = off + (int64_t)(b - b0) * blockDim.x + threadIdx.x; i < off + len; i += (int64_t)nb * blockDim.x)
+        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+}
+
+__global__ void k_adamw_ranges(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+                               const cvk_adamw_range* __restrict__ rt, int nr, AdamwArgRecords recs, int nhyper) {
+    adamw_ranges_body(p, g, m, v, n, rt, nr, recs.r, nhyper);
+}
+
+__global__ void k_adamw_ranges_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                   int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, const cvk_adamw_hyper* __restrict__ hyper,
+                                   int nhyper) {
+    adamw_ranges_body(p, g, m, v, n, rt, nr, hyper, nhyper);
+}
+
 // One row [loss, lr, beta1, ||gw||_2, ||gb||_2] of the per-iteration log into ring[(*counter % capacity) * 5 ..], then ++*counter.
 // One workgroup of 256 threads: thread t sums the squares of elements t, t + 256, ... in fp64, then a fixed tree over LDS.
 constexpr int STEP_LOG_THREADS = 256;
@@ -917,6 +956,55 @@ extern "C" int cvk_adamw_step_dev(float* param, const float* grad, float* exp_av
     CVK_CHECK_ARG(n > 0, "cvk_adamw_step_dev: bad arguments");
     hipLaunchKernelGGL(k_adamw_dev, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, hyper);
     CVK_LAUNCH_RETURN("cvk_adamw_step_dev");
+}
+
+// Workgroups per range: as many as k_adamw would give the range's elements alone (one per 256, at most 8192 in all, shared in proportion to
+// the lengths), at least one.
+extern "C" int cvk_adamw_plan_ranges(cvk_adamw_range* ranges, int nranges, int64_t n, int nhyper) {
+    CVK_CHECK_ARG(ranges && nranges > 0 && n > 0 && nhyper > 0, "cvk_adamw_plan_ranges: bad arguments");
+    int64_t total = 0;
+    for (int r = 0; r < nranges; ++r) {
+        const cvk_adamw_range& e = ranges[r];
+        CVK_CHECK_ARG(e.offset >= 0 && e.length > 0 && e.offset + e.length <= n, "cvk_adamw_plan_ranges: range %d [%lld, +%lld) outside the "
+                      "buffer of %lld elements", r, (long long)e.offset, (long long)e.length, (long long)n);
+        CVK_CHECK_ARG(e.hyper >= 0 && e.hyper < nhyper, "cvk_adamw_plan_ranges: range %d names record %d of %d", r, e.hyper, nhyper);
+        total += e.length;
+    }
+    const int64_t budget = adamw_blocks(total);
+    int64_t blocks = 0;
+    for (int r = 0; r < nranges; ++r) {
+        int64_t nb = (ranges[r].length + 255) / 256;
+        const int64_t share = (budget * ranges[r].length + total - 1) / total;
+        if (nb > share) nb = share;
+        if (nb < 1) nb = 1;
+        ranges[r].block0 = (int32_t)blocks;
+        blocks += nb;
+    }
+    CVK_CHECK_ARG(blocks < (1LL << 30), "cvk_adamw_plan_ranges: too many workgroups");
+    return (int)blocks;
+}
+
+extern "C" int cvk_adamw_step_ranges(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                     const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                                     void* stream) {
+    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper, "cvk_adamw_step_ranges: null pointer");
+    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
+                  "cvk_adamw_step_ranges: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
+    AdamwArgRecords recs = {};
+    for (int i = 0; i < nhyper; ++i) recs.r[i] = hyper[i];
+    hipLaunchKernelGGL(k_adamw_ranges, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, ranges, nranges,
+                       recs, nhyper);
+    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges");
+}
+
+extern "C" int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                         const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                                         void* stream) {
+    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper, "cvk_adamw_step_ranges_dev: null pointer");
+    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_adamw_step_ranges_dev: bad arguments");
+    hipLaunchKernelGGL(k_adamw_ranges_dev, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, ranges,
+                       nranges, hyper, nhyper);
+    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_dev");
 }
 
 extern "C" int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb, float* ring,

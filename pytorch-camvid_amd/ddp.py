@@ -61,18 +61,23 @@ def rccl_env():
 
 def make_buckets(layer_ranges, bucket_floats):
     """layer_ranges: [(begin, end)] float offsets of each layer's gradients in completion order (ascending offsets).
-    Returns [(begin, end, n_layers)] contiguous buckets cut at layer boundaries, each >= bucket_floats except the last."""
+    Returns [(begin, end, n_layers)] contiguous buckets cut at layer boundaries, each >= bucket_floats except the last one and the last one
+    before a gap (the frozen parameters between two ranges are never part of a bucket)."""
     buckets = []
-    b0, n = None, 0
+    b0, n, prev = None, 0, None
     for (lo, hi) in layer_ranges:
+        if b0 is not None and lo != prev:
+            buckets.append((b0, prev, n))
+            b0, n = None, 0
         if b0 is None:
             b0 = lo
         n += 1
+        prev = hi
         if hi - b0 >= bucket_floats:
             buckets.append((b0, hi, n))
             b0, n = None, 0
     if b0 is not None:
-        buckets.append((b0, layer_ranges[-1][1], n))
+        buckets.append((b0, prev, n))
     return buckets
 
 
@@ -81,33 +86,60 @@ class _SyncCall:
     for each conv block in reverse execution order and finish() at the end.  Nothing is kept on the GradSync between
     calls, so two backward passes through one network inside a single autograd graph do not share bucket cursors."""
 
-    def __init__(self, owner, st):
+    def __init__(self, owner, st, plan=None):
         self.owner = owner
         offs, params = st.goffs, st.params
         nslots = len(params) // 4
+        # the gradient segments of the parameters that train (the flags the plan recorded; without a plan: all of them), merged where
+        # contiguous: a frozen parameter's segment is never all-reduced.  Only slots with one take part (the executor reports no other, and
+        # layer_done ignores any other).
         self.ranges = []
+        self.slot_end = {}          # slot -> index of its last range
+        self.slot_order = []        # the slots with a trainable parameter, completion order
         for slot in range(nslots - 1, -1, -1):                       # completion order == ascending flat offsets
-            lo = offs[4 * slot]
-            hi = offs[4 * slot + 3] + (params[4 * slot + 3].numel() + 3) // 4 * 4
-            self.ranges.append((lo, hi))
-        self.buckets = make_buckets(self.ranges, owner.bucket_floats)
+            if plan is None:
+                req = (True,) * 4
+            else:
+                op = plan.convs[slot]
+                req = (op.w_req, op.b_req, op.g_req, op.be_req)
+            pieces = []
+            if all(req):
+                pieces.append((offs[4 * slot], offs[4 * slot + 3] + (params[4 * slot + 3].numel() + 3) // 4 * 4))
+            for j in range(4) if not all(req) else ():
+                if not req[j]:
+                    continue
+                p = params[4 * slot + j]
+                lo, hi = offs[4 * slot + j], offs[4 * slot + j] + (p.numel() + 3) // 4 * 4
+                if pieces and pieces[-1][1] == lo:
+                    pieces[-1] = (pieces[-1][0], hi)
+                else:
+                    pieces.append((lo, hi))
+            if pieces:
+                self.ranges.extend(pieces)
+                self.slot_end[slot] = len(self.ranges) - 1
+                self.slot_order.append(slot)
+        self.buckets = make_buckets(self.ranges, owner.bucket_floats) if self.ranges else []
         self.next_bucket = 0
+        self.next_slot = 0
         self.layers_done = 0
         self.work = []
         self.launched = []
 
     def closes_bucket(self):
         """Will the NEXT layer_done() hand a bucket to the all-reduce?  (The executor finalises its queued gradient pieces first.)"""
-        if self.next_bucket >= len(self.buckets) or self.layers_done >= len(self.ranges):
+        if self.next_bucket >= len(self.buckets) or self.next_slot >= len(self.slot_order):
             return False
-        return self.buckets[self.next_bucket][1] <= self.ranges[self.layers_done][1]
+        return self.buckets[self.next_bucket][1] <= self.ranges[self.slot_end[self.slot_order[self.next_slot]]][1]
 
     def in_flight(self):
         """Has an asynchronous collective been issued in this backward pass (it may still be running beside the next kernels)?"""
         return len(self.work) > 0
 
     def layer_done(self, st, slot):
-        self.layers_done += 1
+        if slot not in self.slot_end:       # a frozen block: none of its segments is exchanged
+            return
+        self.layers_done = self.slot_end[slot] + 1
+        self.next_slot = self.slot_order.index(slot) + 1
         done_upto = self.ranges[self.layers_done - 1][1]
         while self.next_bucket < len(self.buckets) and self.buckets[self.next_bucket][1] <= done_upto:
             lo, hi, _ = self.buckets[self.next_bucket]
@@ -149,7 +181,7 @@ class GradSync:
         self.wait_events = None  # a list while bench.py collects (start, end) HIP events around finish()'s stream waits
 
     def begin(self, st, plan=None):
-        return _SyncCall(self, st)
+        return _SyncCall(self, st, plan)
 
     def _issue(self, call, t):
         if self.world == 1 and not self.always_issue:

@@ -96,6 +96,7 @@ class RunState:
         self.amax = {}              # buf.id -> amax block (device int32 words): the largest magnitude written into the buffer, left by the passes
                                     # that write it (opt-in fp16 split-operand layers scale by it: Runner.plan_amax)
         self.amax_spare = []        # zeroed amax blocks for the backward pass (|dy| maxima)
+        self.scratch = []           # dgamma / dbeta temporaries of blocks with frozen BatchNorm parameters (ConvBnRelu._grad_targets)
 
 
 def _empty(n, dev, dtype=_F32):
@@ -435,6 +436,8 @@ def mark_weights_dirty(module):
 
 
 PROF = None     # bench.py sets this to a list: every _timed call then appends (kernel name, work, start event, end event, unit, executed)
+PROF_OPS = None  # a list beside PROF (tests): every _timed call also appends (op index, "fwd" | "bwd" | None) of the op that launched it
+_CUR_OP = [None]
 
 
 def _timed(R, name, work, fn, unit="flop", executed=None, nbytes=None):
@@ -451,6 +454,8 @@ def _timed(R, name, work, fn, unit="flop", executed=None, nbytes=None):
     r = fn()
     e1.record()
     PROF.append((name, work, e0, e1, unit, executed, nbytes))
+    if PROF_OPS is not None:
+        PROF_OPS.append(_CUR_OP[0])
     return r
 
 
@@ -468,12 +473,43 @@ class Op:
 class ConvBnRelu(Op):
     """ReLU(BN(conv3x3(x)+b)) — reference BasicConv2d (models/unet.py:5-17) / BasicConv (models/segnet.py:5-17)."""
 
-    def __init__(self, src, dst, pslot, holder, cin, cout, src_needs_grad):
+    def __init__(self, src, dst, pslot, holder, cin, cout, src_needs_grad, bn_train=True, req=(True, True, True, True)):
         self.src, self.dst, self.pslot, self.holder = src, dst, pslot, holder
         self.cin, self.cout, self.src_needs_grad = cin, cout, src_needs_grad
+        # fixed when the plan is recorded (part of the plan-cache key, modules._run): the BatchNorm child's own mode, and which of
+        # [conv weight, conv bias, gamma, beta] need a gradient.  src_needs_grad: something upstream of the input needs its gradient.
+        self.bn_train = bool(bn_train)
+        self.w_req, self.b_req, self.g_req, self.be_req = (bool(r) for r in req)
+        self.name = None            # the block's module name (modules._run), for error messages
         self.pool_dst = None        # the ActBuf of a MaxPool2d(2,2) of this block's output, written by the BN-apply pass
         self.pool_op = None
         assert src.C == cin and dst.C == cout and dst.H == src.H and dst.W == src.W
+
+    @property
+    def trainable(self):
+        """A parameter of this block receives a gradient."""
+        return self.w_req or self.b_req or self.g_req or self.be_req
+
+    @property
+    def active(self):
+        """The block runs any backward work: its own parameters' gradients, or the gradient of its input."""
+        return self.trainable or self.src_needs_grad
+
+    @property
+    def label(self):
+        return self.name or "conv block #%d" % self.pslot
+
+    def _grad_targets(self, R, st, ld):
+        """(dW, dbias, dgamma, dbeta) pointers: the flat gradient buffer's segments of the trainable parameters; None for a frozen conv weight or
+        bias (nothing writes their segments); a scratch pair for frozen BatchNorm parameters (the BatchNorm-backward passes need the two sums
+        as temporaries in training mode, and the E-plane passes always take the pointers)."""
+        gw, gb, gg, gbe = R.grad_ptrs(st, self.pslot)
+        if not (self.g_req and self.be_req):
+            sc = _empty(2 * ld, st.device)
+            st.scratch.append(sc)
+            gg = gg if self.g_req else sc.data_ptr()
+            gbe = gbe if self.be_req else sc.data_ptr() + 4 * ld
+        return (gw if self.w_req else None), (gb if self.b_req else None), gg, gbe
 
     def _weight_fwd(self, R, st, w):
         """[Cout][9][ld_in]: the parameter itself when it is channels_last and needs no channel padding."""
@@ -527,7 +563,7 @@ class ConvBnRelu(Op):
         bnp = _empty(4 * ldy, dev)                      # mean | rstd | scale | shift
         pm, pr, psc, psh = (bnp.data_ptr() + 4 * ldy * i for i in range(4))
         conv, bn = self.holder.conv_bn()
-        if st.training:
+        if self.bn_train:
             P = (M + _lib.CVK_STAT_ROWS - 1) // _lib.CVK_STAT_ROWS
             Pm = max(P, lib.cvk_w2d_stat_partials(N, H, W), lib.cvk_w6_stat_partials(N, H, W), lib.cvk_thin_stat_partials(N, H, W, src.ld))   # room for any partial layout (+ counts)
             stats = _empty(2 * Pm * C + Pm, dev)
@@ -582,7 +618,7 @@ class ConvBnRelu(Op):
             else:
                 _timed(R, "k_bn_relu_apply", 8.0 * M * C, lambda: check(
                     lib.cvk_bn_relu_apply(y.data_ptr(), ldy, psc, psh, dst.cview(out), N, H, W, C, s), "cvk_bn_relu_apply"), "byte")
-        if st.need_grad:
+        if st.need_grad and self.active:
             st.saved[self.idx] = (y, bnp, rt, kept)
 
     # BatchNorm-backward passes that also write the weight-grad's transformed dy (route bn_bwd): mode of cvk_bn_bwd_dx_e_amax, the entry point
@@ -595,7 +631,7 @@ class ConvBnRelu(Op):
         pass, which also runs when a planes pass refuses the layout (rc != 0: a strided view) — the weight-grad then transforms dy itself."""
         lib, s, src = R.lib, st.stream, self.src
         N, H, W, M, C, ldy = src.N, src.H, src.W, src.M, self.cout, pad4(self.cout)
-        tail = (part.data_ptr(), N, H, W, C, 1 if st.training else 0)
+        tail = (part.data_ptr(), N, H, W, C, 1 if self.bn_train else 0)
         if kind != "dx":
             mode, plain, eb = self._BN_E[kind]
             if kind == "dx+E":
@@ -608,12 +644,14 @@ class ConvBnRelu(Op):
                 lib.cvk_bn_bwd_dx_e_amax(mode, *head, E.data_ptr(), *tail, blk.data_ptr(), s) if blk is not None
                 else getattr(lib, plain)(*head, E.data_ptr(), *tail, s)), "byte")
             if rc == 0:
-                R.defer_colsum(st, part, lib.cvk_bn_bwd_e_blocks(N, H, W), C, gb)     # conv bias grad: finalised with the others, in one launch
+                if gb is not None:      # conv bias grad: finalised with the others, in one launch
+                    R.defer_colsum(st, part, lib.cvk_bn_bwd_e_blocks(N, H, W), C, gb)
                 return E, (st.amax_spare.pop() if blk is not None else None)
         am = st.amax_spare.pop() if want_amax else None         # a zeroed word: the pass that writes dy leaves its largest magnitude there
         fn, extra = ("cvk_bn_bwd_dx_amax", (am.data_ptr(),)) if am is not None else ("cvk_bn_bwd_dx", ())
         _timed(R, "k_bn_bwd<dx>", 12.0 * M * C, lambda: check(getattr(lib, fn)(*head, *tail, *extra, s), fn), "byte")
-        R.defer_colsum(st, part, PB, C, gb)
+        if gb is not None:
+            R.defer_colsum(st, part, PB, C, gb)
         return None, am
 
     def bwd(self, R, st):
@@ -621,7 +659,10 @@ class ConvBnRelu(Op):
             return self._bwd_bf16(R, st)
         lib, s = R.lib, st.stream
         src, dst = self.src, self.dst
-        y, bnp, rt, kept = st.saved.pop(self.idx)
+        saved = st.saved.pop(self.idx, None)
+        if not self.active:         # frozen block with nothing upstream that needs a gradient: no backward work at all
+            return
+        y, bnp, rt, kept = saved
         X = st.act[src.id]
         dev = X.device
         N, H, W = src.N, src.H, src.W
@@ -629,18 +670,21 @@ class ConvBnRelu(Op):
         flops = 18.0 * M * C * self.cin
         pm, pr, psc, psh = (bnp.data_ptr() + 4 * ldy * i for i in range(4))
         w = st.params[4 * self.pslot]
-        gw, gb, gg, gbe = R.grad_ptrs(st, self.pslot)
+        gw, gb, gg, gbe = self._grad_targets(R, st, ldy)
         dO = dst.cview(st.grad[dst.buf.id])
         PB = lib.cvk_bn_bwd_blocks(M)
         part = _empty(2 * PB * C, dev)
         pre = st.bnred.pop(self.idx, None)
         if pre is not None:     # the data-grad that wrote dO summed it already (csrc/wino4f.hip BNR epilogue)
             check(lib.cvk_colsum_finalize(pre[0].data_ptr(), pre[1], C, gbe, gg, s), "cvk_colsum_finalize")
-        else:
+        elif self.bn_train or self.g_req or self.be_req:        # eval-mode BatchNorm with frozen gamma / beta needs neither sum
             _timed(R, "k_bn_bwd<reduce>", 8.0 * M * C, lambda: check(
                 lib.cvk_bn_bwd_reduce(dO, y.data_ptr(), ldy, psc, psh, pm, pr, part.data_ptr(), N, H, W, C, s), "cvk_bn_bwd_reduce"), "byte")
             check(lib.cvk_colsum_finalize(part.data_ptr(), PB, C, gbe, gg, s), "cvk_colsum_finalize")   # dbeta, dgamma
         del pre
+        if not (self.w_req or self.b_req or self.src_needs_grad):     # only gamma / beta train: dy is not needed
+            R.grads_ready(st, self.pslot)
+            return
         if rt.bn_bwd == "dx+E4p":
             # the plane GEMM reads E0 / E5 (columns of dy) from dy itself: dy carries a zeroed slack behind its last row (cvk_wgradp_gemm_sm_dy)
             dyb = _empty(M * ldy + lib.cvk_wgradp_dy_slack(W) * ldy, dev)
@@ -698,7 +742,7 @@ class ConvBnRelu(Op):
                 # it for that block's BatchNorm backward on the way out (training-mode statistics only)
                 prod = st.plan.sole_producer(src) if rt.dgrad_bnred else None
                 bnred = None
-                if prod is not None and prod.idx in st.saved and pad4(prod.cout) == prod.cout == src.ld:
+                if prod is not None and prod.bn_train and prod.idx in st.saved and pad4(prod.cout) == prod.cout == src.ld:
                     pb = st.saved[prod.idx][1].data_ptr()
                     bnred = (st.saved[prod.idx][0].data_ptr(), pb + 8 * src.ld, pb + 12 * src.ld, pb, pb + 4 * src.ld)
                 c = WinoConv(R, s, dy, packed, None, dX, None, N, H, W, ldy, src.ld, src.ld, flops, w, (self.pslot, "d"), "(dgrad)",
@@ -707,7 +751,9 @@ class ConvBnRelu(Op):
                 if c.bnred_sums is not None:
                     st.bnred[prod.idx] = c.bnred_sums
             st.grad[src.id] = dX
-        if rt.wgrad in W2D:
+        if rt.wgrad is None:        # frozen conv weight: no weight-grad launch
+            pass
+        elif rt.wgrad in W2D:
             tile = rt.tile
             NX = 64 if tile == 6 else 36
             T = w2fn(lib, tile, "tiles")(N, H, W)
@@ -822,7 +868,7 @@ class ConvBnRelu(Op):
         conv, bn = self.holder.conv_bn()
         flops = 18.0 * M * C * self.cin
         tname = {1: "k_thinb_head_fwd", 2: "k_thinb_wide<1>"}.get(tmode)
-        if st.training:
+        if self.bn_train:
             if M <= 1:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size {[N, C, H, W]}")
             P = lib.cvk_thin_bf16_stat_partials(N, H, W) if tmode else lib.cvk_bf16s_stat_partials_c(N, H, W, src.ld, C)
@@ -865,19 +911,22 @@ class ConvBnRelu(Op):
         _timed(R, "k_apply_bf16" + ("<pool>" if pool is not None else ""), nbytes, lambda: check(
             lib.cvk_bn_relu_apply_bf16(y.data_ptr(), C, psc, psh, dst.hview(out), out_f32, pool.data_ptr() if pool is not None else None,
                                        N, H, W, C, s), "cvk_bn_relu_apply_bf16"), "byte")
-        if st.need_grad:
+        if st.need_grad and self.active:
             st.saved[self.idx] = (y, bnp)
 
     def _bwd_bf16(self, R, st):
         lib, s = R.lib, st.stream
         src, dst = self.src, self.dst
-        y, bnp = st.saved.pop(self.idx)
+        saved = st.saved.pop(self.idx, None)
+        if not self.active:
+            return
+        y, bnp = saved
         X = st.act[src.id]
         dev = X.device
         N, H, W, M, C = src.N, src.H, src.W, src.M, self.cout
         pm, pr, psc, psh = (bnp.data_ptr() + 4 * C * i for i in range(4))
         w = st.params[4 * self.pslot]
-        gw, gb, gg, gbe = R.grad_ptrs(st, self.pslot)
+        gw, gb, gg, gbe = self._grad_targets(R, st, C)
         G = st.grad[dst.buf.id]
         dO = dst.hview(G)
         do_f32 = 1 if dst.buf.dtype == _F32 else 0
@@ -887,18 +936,22 @@ class ConvBnRelu(Op):
         pre = st.bnred.pop(self.idx, None)
         if pre is not None:     # the pass that wrote dO last summed it already (csrc/elem_bf16.hip k_pool_bwd_bnred_bf16)
             check(lib.cvk_colsum_finalize(pre[0].data_ptr(), pre[1], C, gbe, gg, s), "cvk_colsum_finalize")
-        else:
+        elif self.bn_train or self.g_req or self.be_req:
             _timed(R, "k_bnbwd_bf16<reduce>", (esz + 2.0) * M * C, lambda: check(
                 lib.cvk_bn_bwd_reduce_bf16(dO, do_f32, y.data_ptr(), C, psc, psh, pm, pr, part.data_ptr(), N, H, W, C, s),
                 "cvk_bn_bwd_reduce_bf16"), "byte")
             check(lib.cvk_colsum_finalize(part.data_ptr(), PB, C, gbe, gg, s), "cvk_colsum_finalize")   # dbeta, dgamma
         del pre
+        if not (self.w_req or self.b_req or self.src_needs_grad):
+            R.grads_ready(st, self.pslot)
+            return
         ld_dy = max(32, C)                              # the data-grad GEMM reads dy in 32-channel K slices
         dy = torch.empty(M * ld_dy, device=dev, dtype=_BF16)
         _timed(R, "k_bnbwd_bf16<dx>", (esz + 4.0) * M * C, lambda: check(
             lib.cvk_bn_bwd_dx_bf16(dO, do_f32, y.data_ptr(), C, psc, psh, pm, pr, gg, gbe, dy.data_ptr(), ld_dy, part.data_ptr(),
-                                   N, H, W, C, 1 if st.training else 0, s), "cvk_bn_bwd_dx_bf16"), "byte")
-        R.defer_colsum(st, part, PB, C, gb)             # conv bias grad: finalised with the others, in one launch
+                                   N, H, W, C, 1 if self.bn_train else 0, s), "cvk_bn_bwd_dx_bf16"), "byte")
+        if gb is not None:
+            R.defer_colsum(st, part, PB, C, gb)         # conv bias grad: finalised with the others, in one launch
         del y
         wc = w if w.is_contiguous(memory_format=torch.channels_last) else w.contiguous(memory_format=torch.channels_last)
         flops = 18.0 * M * C * self.cin
@@ -927,6 +980,9 @@ class ConvBnRelu(Op):
                     lib.cvk_conv3x3_bf16s_wg(dy.data_ptr(), wd.data_ptr(), None, dX.data_ptr(), None, None, N, H, W, ld_dy, self.cin, src.ld,
                                              R.launch_wgs(), s), "cvk_conv3x3_bf16s(dgrad)"))
             st.grad[src.id] = dX
+        if gw is None:          # frozen conv weight: no weight-grad launch
+            R.grads_ready(st, self.pslot)
+            return
         # partial slabs now, the sum over the slabs with every other layer's in ONE launch (Runner.flush_wreduces): nobody reads a weight
         # gradient before the end of backward (or the all-reduce of its bucket); 23 reductions of ~11 us were 0.26 ms of a 21 ms step
         S = lib.cvk_conv3x3_wgrad_bf16s_splits(N, H, W, self.cin, C)
@@ -947,6 +1003,7 @@ class MaxPool(Op):
         self.src, self.dst, self.keep_code = src_view, dst_buf, keep_code
         self.fused = False          # produced by the preceding block's BN-apply pass
         self.producer_idx = -1
+        self.wants = True           # something upstream of the pooled view needs a gradient (Plan._needs_grad)
         if src_view.H < 2 or src_view.W < 2:
             raise RuntimeError(f"max_pool2d: input {src_view.H}x{src_view.W} is too small for a 2x2 window")
 
@@ -970,7 +1027,8 @@ class MaxPool(Op):
 
     def bwd(self, R, st):
         v, d = self.src, self.dst
-        if d.id not in st.grad:
+        if not self.wants or d.id not in st.grad:
+            st.grad.pop(d.id, None)
             return
         X = st.act[v.buf.id]
         acc = v.buf.id in st.grad
@@ -984,7 +1042,7 @@ class MaxPool(Op):
         # BatchNorm-backward sums (csrc/pointwise.hip k_pool_scatter_bnred, csrc/elem_bf16.hip k_pool_bwd_bnred_bf16) and the block's reduce pass is
         # not launched
         prod = st.plan.ops[self.producer_idx] if (self.fused and self.producer_idx >= 0) else None
-        fuse_sums = (prod is not None and st.training and R.pool_bnred and isinstance(prod, ConvBnRelu) and prod.idx in st.saved
+        fuse_sums = (prod is not None and st.training and R.pool_bnred and isinstance(prod, ConvBnRelu) and prod.bn_train and prod.idx in st.saved
                      and prod.idx not in st.bnred and prod.dst.buf is v.buf
                      and (prod.dst.c0, prod.dst.C, prod.dst.y0, prod.dst.x0, prod.dst.H, prod.dst.W) == (v.c0, v.C, v.y0, v.x0, v.H, v.W)
                      and prod.cout == v.C and st.plan.last_gradient_writer(v, prod.idx) == self.idx)
@@ -1037,6 +1095,7 @@ class Unpool(Op):
 
     def __init__(self, src_buf, pool_op, dst_buf):
         self.src, self.pool, self.dst = src_buf, pool_op, dst_buf
+        self.wants = True
 
     def fwd(self, R, st):
         V = st.act[self.src.id]
@@ -1059,7 +1118,9 @@ class Unpool(Op):
 
     def bwd(self, R, st):
         d = self.dst
-        g = st.grad.pop(d.id)
+        g = st.grad.pop(d.id, None)
+        if not self.wants or g is None:
+            return
         dv = torch.empty_like(st.act[self.src.id])
         if st.plan.bf16:
             pv = self.pool.src
@@ -1083,6 +1144,7 @@ class Upsample(Op):
 
     def __init__(self, src_buf, dst_buf):
         self.src, self.dst = src_buf, dst_buf
+        self.wants = True
 
     def fwd(self, R, st):
         X = st.act[self.src.id]
@@ -1099,7 +1161,9 @@ class Upsample(Op):
             aw.copy_(st.amax[b.id])
 
     def bwd(self, R, st):
-        g = st.grad.pop(self.dst.id)
+        g = st.grad.pop(self.dst.id, None)
+        if not self.wants or g is None:
+            return
         b = self.src
         dx = torch.empty_like(st.act[b.id])
         if st.plan.bf16:
@@ -1137,6 +1201,8 @@ class Plan:
         self.N, self.cin, self.H, self.W = N, cin, H, W
         self.bf16 = bool(bf16)      # bf16-storage plan: activation buffers are bf16 (the logits buffer stays fp32)
         self.bufs, self.ops, self.holders = [], [], []
+        self.convs = []             # the ConvBnRelu ops by parameter slot
+        self._writers = {}          # buffer id -> [(c0, C, op)]: the ops that write channels [c0, c0 + C) of it (gradient reachability)
         self._producer = {}         # (buffer id, first channel) -> the ConvBnRelu op that writes that view
         self._readers = {}          # buffer id -> number of ops that read the buffer (each one adds to its gradient)
         self.routes = {}            # (Runner.kernel_config(), training, need_grad) -> {op index: ConvRoute} (Runner.routes)
@@ -1156,6 +1222,22 @@ class Plan:
 
     def _reads(self, buf):
         self._readers[buf.id] = self._readers.get(buf.id, 0) + 1
+
+    def _writes(self, buf, c0, C, op):
+        self._writers.setdefault(buf.id, []).append((c0, C, op))
+
+    def _needs_grad(self, buf, c0=0, C=None):
+        """Does anything upstream of channels [c0, c0 + C) of `buf` need a gradient: a writer of those channels with a trainable parameter or
+        whose own input needs one, or the network input when it requires a gradient?  Writers precede readers in the plan, so the flags of
+        every writer are final here.  Per channel range: the two halves of a zero-copy concat buffer (a frozen encoder's skip tensor, a
+        trainable upsample branch) answer separately."""
+        if buf is self.input:
+            return bool(self.input_needs_grad)
+        C = buf.C if C is None else C
+        for w0, wC, op in self._writers.get(buf.id, ()):
+            if w0 < c0 + C and c0 < w0 + wC and (op.active if isinstance(op, ConvBnRelu) else op.wants):
+                return True
+        return False
 
     def last_gradient_writer(self, view, producer_idx):
         """Index of the op whose backward pass writes LAST into the gradient of `view` (channels [c0, c0 + C) of its buffer): backward runs the plan
@@ -1190,16 +1272,23 @@ class Plan:
             dst_view = self.new_buf(cout, src_buf.H, src_buf.W, holder.tag).full_view()
         pslot = len(self.holders)
         self.holders.append(holder)
-        needs = src_buf is not self.input or self.input_needs_grad
+        conv, bn = holder.conv_bn()
+        req = (conv.weight.requires_grad, conv.bias is not None and conv.bias.requires_grad, bn.weight is not None and bn.weight.requires_grad,
+               bn.bias is not None and bn.bias.requires_grad)
+        needs = self._needs_grad(src_buf)
         self._reads(src_buf)
-        op = self.add(ConvBnRelu(src_buf, dst_view, pslot, holder, cin, cout, needs))
+        op = self.add(ConvBnRelu(src_buf, dst_view, pslot, holder, cin, cout, needs, bn.training, req))
+        self.convs.append(op)
         self._producer[(dst_view.buf.id, dst_view.c0)] = op
+        self._writes(dst_view.buf, dst_view.c0, dst_view.C, op)
         return dst_view
 
     def maxpool(self, src_view, keep_code=False):
         dst = self.new_buf(src_view.C, src_view.H // 2, src_view.W // 2, "pool")
         self._reads(src_view.buf)
         op = self.add(MaxPool(src_view, dst, keep_code))
+        op.wants = self._needs_grad(src_view.buf, src_view.c0, src_view.C)
+        self._writes(dst, 0, dst.C, op)
         prod = self._producer.get((src_view.buf.id, src_view.c0))
         if prod is not None and prod.dst.C == src_view.C and prod.pool_dst is None \
                 and prod.dst.H == src_view.H and prod.dst.W == src_view.W and prod.dst.y0 == src_view.y0 and prod.dst.x0 == src_view.x0:
@@ -1213,13 +1302,17 @@ class Plan:
         v = pool_op.src
         dst = self.new_buf(v.C, v.H, v.W, "unpool")
         self._reads(src_buf)
-        self.add(Unpool(src_buf, pool_op, dst))
+        op = self.add(Unpool(src_buf, pool_op, dst))
+        op.wants = self._needs_grad(src_buf)
+        self._writes(dst, 0, dst.C, op)
         return dst
 
     def upsample(self, src_buf):
         dst = self.new_buf(src_buf.C, 2 * src_buf.H, 2 * src_buf.W, "up")
         self._reads(src_buf)
-        self.add(Upsample(src_buf, dst))
+        op = self.add(Upsample(src_buf, dst))
+        op.wants = self._needs_grad(src_buf)
+        self._writes(dst, 0, dst.C, op)
         return dst
 
     def zero_frame(self, view):
@@ -1448,7 +1541,7 @@ class Runner:
         st.colsums.clear()
 
     def grads_ready(self, st, slot):
-        if st.sync is not None:
+        if st.sync is not None and st.plan.convs[slot].trainable:
             if st.sync.closes_bucket():     # this layer completes a bucket that is handed to the all-reduce now: its queued bias and
                 self.flush_colsums(st)      # weight gradient finalisations must have run (round 5: only then — flushing after every
                 self.flush_wreduces(st)     # layer turned the two batched launches of a backward pass into 23 + 23 under data parallel)
@@ -1514,6 +1607,8 @@ class Runner:
         key = (self.kernel_config(), training, need_grad)
         r = plan.routes.get(key)
         if r is None:
+            if split_fmt(self):
+                check_bn_modes(plan, training, "set_split_operands")
             self.w2tile, self.w2tile_dgrad = self.tile_for(plan)
             r = plan.routes[key] = {op.idx: conv_route(self, op, training, need_grad) for op in plan.ops if isinstance(op, ConvBnRelu)}
         return r
@@ -1552,13 +1647,16 @@ class Runner:
                                            st.stream), "cvk_import_nchw")
             st.act[inb.id] = t
         if plan.bf16:
+            check_bn_modes(plan, training, "bf16 mode", need_grad, forward_only_ok=True)
             self.prepack_bf16(plan, st, need_grad)
         else:
             st.routes = self.routes(plan, training, need_grad)
             self.prebuild_fp32(plan, st, need_grad)
             self.plan_amax(plan, st)
         for op in plan.ops:
+            _CUR_OP[0] = (op.idx, "fwd")
             op.fwd(self, st)
+        _CUR_OP[0] = None
         ov = plan.output
         out = st.act[ov.buf.id][..., :ov.buf.C].permute(0, 3, 1, 2)    # logical NCHW, channels_last strides
         if not need_grad:
@@ -1591,7 +1689,9 @@ class Runner:
                                            st.stream), "cvk_import_nchw")
             st.grad[ob.id] = g
         for op in reversed(plan.ops):
+            _CUR_OP[0] = (op.idx, "bwd")
             op.bwd(self, st)
+        _CUR_OP[0] = None
         self.flush_colsums(st)
         self.flush_wreduces(st)
         dx = None
@@ -1602,6 +1702,10 @@ class Runner:
                 dx = dx.float()
         grads = []
         for i, p in enumerate(params):
+            op = plan.convs[i // 4]
+            if not (op.w_req, op.b_req, op.g_req, op.be_req)[i % 4]:
+                grads.append(None)          # frozen when the plan was recorded: its segment was never written
+                continue
             n = p.numel()
             seg = st.gflat[st.goffs[i]:st.goffs[i] + n]
             if p.dim() == 4:   # [Cout][3][3][Cin] storage -> logical OIHW with channels_last strides
@@ -1613,8 +1717,20 @@ class Runner:
         if st.sync is not None:
             st.sync.finish(st)
         self._collectives_in_flight = False
-        st.act.clear(); st.saved.clear(); st.grad.clear()
+        st.act.clear(); st.saved.clear(); st.grad.clear(); st.scratch.clear()
         return dx, grads
+
+
+def check_bn_modes(plan, training, what, need_grad=True, forward_only_ok=False):
+    """The bf16 kernels and the split-operand routes serve one BatchNorm mode per pass: a block whose BatchNorm child is in the other mode
+    (a sub-module's eval() inside a training pass, or the reverse) is refused by name rather than run in the wrong mode.  forward_only_ok (bf16):
+    such a block is served when it runs no backward (a frozen encoder in eval mode: the inference forward pass of the block)."""
+    for op in plan.convs:
+        if forward_only_ok and not (need_grad and op.active):
+            continue
+        if op.bn_train != bool(training):
+            raise NotImplementedError(f"{what}: BatchNorm of {op.label} is in {'training' if op.bn_train else 'eval'} mode inside a "
+                                      f"{'training' if training else 'eval'} pass; per-block BatchNorm modes run in the fp32 mode only")
 
 
 def layout_grads(params):

@@ -20,9 +20,11 @@ gloo groups (CPU rehearsals) cannot be captured.
 
 The whole iteration (train.py:124-150): with `optimizer=` (a FlatAdamW) the graph also runs the AdamW step after backward (after
 the captured all-reduces under data parallel), and with `log_capacity=` it ends in one launch that appends the reference's log
-line [loss, lr, beta1, ||last weight grad||, ||last bias grad||] to a device ring.  lr, betas, eps and weight decay are read from
-param_groups[0] at every replay, the bias corrections computed on the host and uploaded into a device record the graph reads,
-so a scheduler drives the captured optimizer as it drives the eager one:
+line [loss, lr, beta1, ||last weight grad||, ||last bias grad||] to a device ring.  lr, betas, eps and weight decay of every parameter
+group are read at every replay, the bias corrections computed on the host and uploaded into device records the graph reads (one per
+group and step count, cvk_adamw_step_ranges_dev; the log row reads param_groups[0], as the reference prints), so a scheduler drives the
+captured optimizer as it drives the eager one.  Frozen parameters (requires_grad False, BatchNorm children in eval mode) are captured as
+they are when the GraphedStep is built; replay() refuses to run after any of that changes:
 
     opt = FlatAdamW(net, lr=...); sched = OneCycleLR(opt, ...)
     step = GraphedStep(net, lossf, x, t, optimizer=opt, scheduler=sched, log_capacity=len(loader))
@@ -37,6 +39,7 @@ from . import _lib, engine
 from ._lib import check
 
 HYPER_FLOATS = 7                         # include/cvk.h cvk_adamw_hyper: lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt
+HYPER_BYTES = 4 * HYPER_FLOATS
 HYPER_SLOTS = 32                         # pinned staging records: the host may run this many replays ahead of the GPU before it waits
 
 
@@ -69,8 +72,6 @@ class GraphedStep:
         if log_capacity and optimizer is None:
             raise ValueError("GraphedStep: the log records the step's lr and beta1: it needs optimizer=")
         if optimizer is not None:
-            if len(optimizer.param_groups) != 1:
-                raise ValueError("GraphedStep: FlatAdamW with one parameter group only")
             if {id(p) for p in optimizer._plist} != {id(p) for p in net.parameters()}:
                 raise ValueError("GraphedStep: the optimizer was built for another network")
             optimizer._check_homes()
@@ -91,9 +92,16 @@ class GraphedStep:
         self.x, self.t = x.clone(), t.clone()
         self.params = [p for p in net.parameters() if p.requires_grad]
         if optimizer is not None:
-            # the record the captured AdamW step (and the log) reads; rewritten before every replay from a ring of pinned host slots
-            self._hyper = torch.zeros(HYPER_FLOATS, device=x.device, dtype=torch.float32)
-            self._hyper_pin = torch.zeros(HYPER_SLOTS, HYPER_FLOATS, dtype=torch.float32, pin_memory=True)
+            # the parameters the captured step updates (those that receive a gradient) and its records: record 0 = param_groups[0] for the log,
+            # then one per (group, step count) of the range table (FlatAdamW._ranges); rewritten before every replay from a ring of pinned slots
+            self._opt_idx = [i for i, p in enumerate(optimizer._plist) if p.requires_grad]
+            if not self._opt_idx:
+                raise ValueError("GraphedStep: the optimizer has no trainable parameter to step")
+            self._opt_recs, self._opt_ranges = optimizer._ranges(self._opt_idx)
+            self._table, self._table_blocks = optimizer._table(self._opt_ranges, len(self._opt_recs))   # uploaded before the capture
+            nrec = 1 + len(self._opt_recs)
+            self._hyper = torch.zeros(nrec * HYPER_FLOATS, device=x.device, dtype=torch.float32)
+            self._hyper_pin = torch.zeros(HYPER_SLOTS, nrec * HYPER_FLOATS, dtype=torch.float32, pin_memory=True)
             self._hyper_busy = [None] * HYPER_SLOTS     # per slot: event after the H2D copy that READ it
             self._hyper_slot = 0
         if log_capacity:
@@ -139,9 +147,10 @@ class GraphedStep:
         lib, stream = _lib.load(), torch.cuda.current_stream(device).cuda_stream
         opt = self.optimizer
         if opt is not None:
-            self._gflat = opt._flat_grad()      # the executor's flat gradient buffer (graph pool): same address in every replay
-            check(lib.cvk_adamw_step_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
-                                         opt._flat.numel(), self._hyper.data_ptr(), stream), "cvk_adamw_step_dev")
+            self._gflat = opt._flat_grad(self._opt_idx)     # the executor's flat gradient buffer (graph pool): same address in every replay
+            check(lib.cvk_adamw_step_ranges_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
+                                                opt._flat.numel(), self._table.data_ptr(), len(self._opt_ranges), self._table_blocks,
+                                                self._hyper.data_ptr() + HYPER_BYTES, len(self._opt_recs), stream), "cvk_adamw_step_ranges_dev")
         if self.log_capacity:
             gw, gb = self._log_w.grad, self._log_b.grad
             if gw is None or gb is None:
@@ -154,11 +163,13 @@ class GraphedStep:
                                    self._logbuf.data_ptr() + 8, self.log_capacity, self._logbuf.data_ptr(), stream), "cvk_step_log")
 
     def _upload_hyper(self):
-        """param_groups[0] as the scheduler left it + the next step number -> the device record, on the current stream (no host sync:
-        the host waits only when it is HYPER_SLOTS replays ahead of the copies that read its pinned slots)."""
+        """Every group as the scheduler left it + the next step counts -> the device records, on the current stream (no host sync: the host
+        waits only when it is HYPER_SLOTS replays ahead of the copies that read its pinned slots)."""
         opt = self.optimizer
         g = opt.param_groups[0]
         opt._step += 1
+        for i in self._opt_idx:
+            opt._steps[i] += 1
         slot = self._hyper_slot
         self._hyper_slot = (slot + 1) % HYPER_SLOTS
         if self._hyper_busy[slot] is not None:
@@ -166,6 +177,7 @@ class GraphedStep:
         pin = self._hyper_pin[slot]
         check(_lib.load().cvk_adamw_hyper_fill(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                                                float(g["weight_decay"]), opt._step, pin.data_ptr()), "cvk_adamw_hyper_fill")
+        opt._fill(self._opt_recs, pin[HYPER_FLOATS:])
         self._hyper.copy_(pin, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -195,8 +207,11 @@ class GraphedStep:
             p.grad = None
 
     def _signature(self):
+        from .modules import plan_key_blocks
         R = self._runner
-        return (id(R.grad_sync), bool(self.net.training), bool(R.bf16), R.persistent_wgs()) + R.kernel_config() + self._optimizer_signature()
+        # plan_key_blocks: every block's identity, BatchNorm mode and requires-grad pattern (what the captured plan and range table fixed)
+        return (id(R.grad_sync), bool(self.net.training), bool(R.bf16), R.persistent_wgs()) + R.kernel_config() + self._optimizer_signature() \
+            + (plan_key_blocks(self.net),)
 
     def _optimizer_signature(self):
         """The captured AdamW step writes the optimizer's flat buffers through raw pointers: the same optimizer, one parameter group, the
@@ -204,15 +219,17 @@ class GraphedStep:
         opt = getattr(self, "optimizer", None)
         if opt is None:
             return ()
-        return (id(opt), len(opt.param_groups), opt._flat.data_ptr(), tuple(p.data_ptr() for p in opt._plist))
+        return (id(opt), len(opt.param_groups), tuple(opt._group_of()), opt._flat.data_ptr(), tuple(p.data_ptr() for p in opt._plist))
 
     def replay(self, x=None, t=None):
         """Copy a new batch into the static input buffers (optional) and replay the step.  Returns the (static) loss tensor.
         With an optimizer: the captured step uses param_groups[0] as it is now and optimizer._step + 1, then the scheduler (if any)
         steps — the order of the eager loop `replay(); optimizer.step(); scheduler.step()`."""
         if self._signature() != self._sig:
-            raise RuntimeError("GraphedStep.replay: the network changed since the capture (train/eval mode, conv precision, a kernel "
-                               "knob, it was wrapped in / unwrapped from ddp.DataParallel, or the captured FlatAdamW was rebuilt or re-homed): the "
+            raise RuntimeError("GraphedStep.replay: the network changed since the capture (train/eval mode of the network or of a "
+                               "block's BatchNorm, a parameter's requires_grad, a swapped block, conv precision, a kernel "
+                               "knob, it was wrapped in / unwrapped from ddp.DataParallel, or the captured FlatAdamW was rebuilt, re-homed or "
+                               "regrouped): the "
                                "captured graph would silently run the "
                                "old configuration — build a new GraphedStep")
         if x is not None:

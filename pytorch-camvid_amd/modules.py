@@ -42,6 +42,11 @@ class _Block(nn.Module):
         c, b = self.conv_bn()
         return [c.weight, c.bias, b.weight, b.bias]
 
+    def plan_flags(self):
+        """What a recorded plan fixes about this block (engine.ConvBnRelu): its BatchNorm child's mode and which parameters need a gradient."""
+        c, b = self.conv_bn()
+        return (b.training, c.weight.requires_grad, c.bias.requires_grad, b.weight.requires_grad, b.bias.requires_grad)
+
     def _emit(self, plan, src_buf, dst_view=None):
         return plan.conv_bn_relu(src_buf, self, dst_view)
 
@@ -209,6 +214,12 @@ def _holders_of(root):
     return [m for m in root.modules() if isinstance(m, _Block)]
 
 
+def plan_key_blocks(root):
+    """The per-block part of the plan-cache key: every block's identity (a swapped child records a new plan) and plan_flags() (toggling
+    requires_grad_ or a sub-module's train() / eval() records or picks the plan with those flags)."""
+    return tuple((id(h),) + h.plan_flags() for h in _holders_of(root))
+
+
 _STATE = weakref.WeakKeyDictionary()   # module -> {"runner", "plans"}; kept out of the module so deepcopy/pickle stay plain
 
 
@@ -237,13 +248,17 @@ def _run(root, x):
     state = _state_of(root)
     N, C, H, W = x.shape
     bf16 = bool(state["runner"].bf16)
-    key = (N, C, H, W, bool(x.requires_grad and torch.is_grad_enabled()), bf16, bool(state["runner"].thin) if bf16 else None)
+    key = (N, C, H, W, bool(x.requires_grad and torch.is_grad_enabled()), bf16, bool(state["runner"].thin) if bf16 else None,
+           plan_key_blocks(root))
     plan = state["plans"].get(key)
     if plan is None:
         plan = engine.Plan(N, C, H, W, bf16=bf16)
         plan.input_needs_grad = key[4]
         plan.output = root._emit(plan, plan.input)
         plan.seal(thin=bool(state["runner"].thin))
+        names = {id(m): n for n, m in root.named_modules()}
+        for op in plan.convs:
+            op.name = names.get(id(op.holder)) or type(root).__name__
         state["plans"][key] = plan
     params = []
     for h in plan.holders:

@@ -3,8 +3,14 @@
 The executor already writes every gradient into one flat fp32 buffer (engine.layout_grads).  FlatAdamW re-homes the
 parameters into a flat buffer with the SAME layout, so a step is a single `cvk_adamw_step` launch over 34.5 M
 elements (7 x 138 MB of HBM traffic) instead of ~10 multi-tensor launches over 92 tensors.  It is a
-`torch.optim.Optimizer`: `param_groups[0]["lr"]` / `["betas"]` are read every step, so `OneCycleLR` (train.py:103-104)
-drives it unchanged.  One parameter group (the reference uses one)."""
+`torch.optim.Optimizer`: every group's `lr` / `betas` are read every step, so `OneCycleLR` (train.py:103-104) drives it unchanged.
+
+Fine-tuning: `groups=` takes torch-style parameter groups (every parameter of the network in exactly one group; per-group `lr`, `betas`,
+`eps`, `weight_decay`).  As torch.optim.AdamW, a parameter whose `.grad` is None is skipped and each parameter keeps its own step count (a
+block unfrozen late starts its bias correction at 1).  The step is one launch over a device table of the trainable ranges of the flat
+buffer (cvk_adamw_step_ranges): frozen parameters and their moments are neither read nor written."""
+import ctypes
+
 import torch
 
 from . import _lib, engine
@@ -21,11 +27,22 @@ def _block_params(net):
 
 
 class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, groups=None):
         params = _block_params(net)                       # execution order == the executor's flat parameter list
         if len(params) != len(list(net.parameters())):
             raise ValueError("FlatAdamW needs a network made only of conv+BN blocks (UNet / SegNet)")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        if groups is None:
+            groups = params
+        else:
+            groups = [dict(g) for g in groups]
+            for g in groups:
+                if not isinstance(g, dict) or "params" not in g:
+                    raise ValueError("FlatAdamW: groups= takes a list of dicts with a 'params' entry, like torch parameter groups")
+                g["params"] = list(g["params"])
+            seen = [id(p) for g in groups for p in g["params"]]
+            if sorted(seen) != sorted(id(p) for p in params):
+                raise ValueError("FlatAdamW: every parameter of the network must be in exactly one group")
+        super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._plist = params
         self._offs, total = engine.layout_grads(params)
         dev = params[0].device
@@ -46,15 +63,30 @@ class FlatAdamW(torch.optim.Optimizer):
         self._m = torch.zeros_like(self._flat)
         self._v = torch.zeros_like(self._flat)
         self._gbuf = None
-        self._step = 0
+        self._step = 0                                    # step() calls (the counter the captured step and schedulers see)
+        self._steps = [0] * len(params)                   # per parameter, as torch.optim.AdamW's state[p]["step"]
+        self._tables = {}                                 # range table (host tuple) -> (device table, workgroups)
 
-    def _flat_grad(self):
-        """The executor's flat gradient buffer when every .grad is the expected view of it, else a gathered copy."""
-        p0 = self._plist[0]
-        if p0.grad is None:
+    def _group_of(self):
+        ids = {}
+        for gi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                ids[id(p)] = gi
+        return [ids[id(p)] for p in self._plist]
+
+    def _trainable(self):
+        """Indices (into the flat parameter list) of the parameters with a gradient: the ones a step updates."""
+        return [i for i, p in enumerate(self._plist) if p.grad is not None]
+
+    def _flat_grad(self, idx=None):
+        """The executor's flat gradient buffer when every gradient of the parameters `idx` (default: those with a .grad) is the expected view
+        of it, else a copy gathered from them.  Segments of other parameters are never read."""
+        idx = self._trainable() if idx is None else idx
+        if not idx:
             raise RuntimeError("FlatAdamW.step(): gradients missing")
-        base = p0.grad.data_ptr() - 4 * self._offs[0]
-        ok = all(p.grad is not None and p.grad.data_ptr() == base + 4 * o for p, o in zip(self._plist, self._offs))
+        p0, o0 = self._plist[idx[0]], self._offs[idx[0]]
+        base = p0.grad.data_ptr() - 4 * o0
+        ok = all(self._plist[i].grad.data_ptr() == base + 4 * self._offs[i] for i in idx)
         if ok:
             st = p0.grad.untyped_storage()
             start = (base - st.data_ptr()) // 4
@@ -62,10 +94,55 @@ class FlatAdamW(torch.optim.Optimizer):
                 return torch.empty(0, device=p0.device, dtype=torch.float32).set_(st, start, (self._flat.numel(),))
         if self._gbuf is None:
             self._gbuf = torch.zeros_like(self._flat)
-        for p, o in zip(self._plist, self._offs):
+        for i in idx:
+            p, o = self._plist[i], self._offs[i]
             g = p.grad.permute(0, 2, 3, 1) if p.dim() == 4 else p.grad
             self._gbuf[o:o + p.numel()].view(g.shape).copy_(g)
         return self._gbuf
+
+    def _ranges(self, idx):
+        """(records, ranges) of one step over the parameters `idx`: records = [(group, parameter whose step count it carries)], one per
+        distinct (group, step count); ranges = [(offset, length, record)] in flat-buffer order, neighbours of one record merged across the
+        16-byte alignment padding between them (all parameters trainable in one group at one step count: the single range [0, total))."""
+        gof = self._group_of()
+        recs, rix, ranges = [], {}, []
+        for i in sorted(idx, key=lambda i: self._offs[i]):
+            k = (gof[i], self._steps[i])
+            if k not in rix:
+                rix[k] = len(recs)
+                recs.append((gof[i], i))
+            o, n = self._offs[i], (self._plist[i].numel() + 3) // 4 * 4
+            if ranges and ranges[-1][2] == rix[k] and ranges[-1][0] + ranges[-1][1] == o:
+                ranges[-1] = (ranges[-1][0], ranges[-1][1] + n, rix[k])
+            else:
+                ranges.append((o, n, rix[k]))
+        return recs, ranges
+
+    def _fill(self, recs, out, step_of=None):
+        """Write the cvk_adamw_hyper records of `recs` into `out` (a host AdamwHyper array or a pinned float tensor of 7 floats per record):
+        the group's options as they are now and the bias corrections of the parameter's step count (cvk_adamw_hyper_fill)."""
+        lib = _lib.load()
+        step_of = step_of or (lambda i: self._steps[i])
+        base = out.data_ptr() if isinstance(out, torch.Tensor) else ctypes.addressof(out)
+        size = ctypes.sizeof(_lib.AdamwHyper)
+        for r, (gi, i) in enumerate(recs):
+            g = self.param_groups[gi]
+            check(lib.cvk_adamw_hyper_fill(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                           float(g["weight_decay"]), step_of(i), base + r * size), "cvk_adamw_hyper_fill")
+
+    def _table(self, ranges, nrec):
+        """The device copy of a planned range table (cached per table) and its workgroup count."""
+        key = (tuple(ranges), nrec)
+        ent = self._tables.get(key)
+        if ent is None:
+            lib = _lib.load()
+            arr = (_lib.AdamwRange * len(ranges))(*[_lib.AdamwRange(o, n, r, 0) for o, n, r in ranges])
+            nb = lib.cvk_adamw_plan_ranges(ctypes.addressof(arr), len(ranges), self._flat.numel(), nrec)
+            if nb <= 0:
+                check(nb if nb < 0 else -1, "cvk_adamw_plan_ranges")
+            dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self._flat.device)
+            ent = self._tables[key] = (dev, nb)
+        return ent
 
     def _check_homes(self):
         """The module must still read its weights from the flat buffer: net.to()/.cuda()/.float() after construction
@@ -78,8 +155,8 @@ class FlatAdamW(torch.optim.Optimizer):
 
     # ---- optimizer state: exp_avg / exp_avg_sq / step travel with state_dict() like torch.optim.AdamW's do ----------
     def state_dict(self):
-        sd = super().state_dict()
-        sd["flat_adamw"] = {"step": self._step, "exp_avg": self._m.clone(), "exp_avg_sq": self._v.clone(),
+        sd = super().state_dict()           # param_groups: every group's options and its members
+        sd["flat_adamw"] = {"step": self._step, "steps": list(self._steps), "exp_avg": self._m.clone(), "exp_avg_sq": self._v.clone(),
                             "offsets": list(self._offs)}
         return sd
 
@@ -91,18 +168,35 @@ class FlatAdamW(torch.optim.Optimizer):
             if list(extra["offsets"]) != list(self._offs) or extra["exp_avg"].numel() != self._m.numel():
                 raise ValueError("FlatAdamW.load_state_dict: the saved state belongs to a different network layout")
             self._step = int(extra["step"])
+            steps = extra.get("steps")      # absent in the single-step format: every parameter took every step
+            self._steps = [int(s) for s in steps] if steps is not None else [self._step] * len(self._plist)
+            if len(self._steps) != len(self._plist):
+                raise ValueError("FlatAdamW.load_state_dict: the saved step counts belong to a different network layout")
             self._m.copy_(extra["exp_avg"]); self._v.copy_(extra["exp_avg_sq"])
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        g = self.param_groups[0]
         self._check_homes()
+        idx = self._trainable()
+        if not idx:                   # torch.optim.AdamW: nothing has a gradient, nothing changes
+            return loss
         self._step += 1
-        grad = self._flat_grad()
+        for i in idx:
+            self._steps[i] += 1
+        grad = self._flat_grad(idx)
         lib = _lib.load()
-        check(lib.cvk_adamw_step(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), self._flat.numel(),
-                                 float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                                 self._step, torch.cuda.current_stream(self._flat.device).cuda_stream), "cvk_adamw_step")
+        stream = torch.cuda.current_stream(self._flat.device).cuda_stream
+        recs, ranges = self._ranges(idx)
+        # the records travel as kernel arguments: one launch per CVK_ADAMW_ARG_RECORDS distinct (group, step count) pairs
+        for c0 in range(0, len(recs), _lib.ADAMW_ARG_RECORDS):
+            crecs = recs[c0:c0 + _lib.ADAMW_ARG_RECORDS]
+            cranges = [(o, n, r - c0) for o, n, r in ranges if c0 <= r < c0 + len(crecs)]
+            hyper = (_lib.AdamwHyper * len(crecs))()
+            self._fill(crecs, hyper)
+            table, nb = self._table(cranges, len(crecs))
+            check(lib.cvk_adamw_step_ranges(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), self._flat.numel(),
+                                            table.data_ptr(), len(cranges), nb, ctypes.addressof(hyper), len(crecs), stream),
+                  "cvk_adamw_step_ranges")
         engine._bump_epoch()          # the kernel wrote the parameters through raw pointers: derived weight tensors are stale
         return loss

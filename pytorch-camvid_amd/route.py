@@ -107,7 +107,7 @@ class ConvRoute:
     dy_both: one launch transforms dy for the 2-D data-grad and the 2-D weight-grad (same tile)
     bn_bwd: "dx" | "dx+E" (transposed F(4,3) planes) | "dx+E6" (plane GEMM: six planes) | "dx+E4p" (four planes, E0 / E5 read from dy)
     wgrad: "w2d" | "w2d_split" | "wgradp_sm" (plane GEMM over the forward's V planes) | "wgradp" (plane GEMM, own V pass) | "w4" (transposed
-           F(4,3)) | "thin" | "w2" (F(2,3)) | "direct"
+           F(4,3)) | "thin" | "w2" (F(2,3)) | "direct"; None for a frozen conv weight (no weight-grad launch)
     dy_amax: the pass that writes dy leaves its largest magnitude for the fp16 split-operand data-grad"""
     fwd: str
     tile: int = 0
@@ -140,8 +140,12 @@ def _wino_1d(R, N, H, W, k_ch, cout, ldy, fused_ok, h2):
 
 
 def conv_route(R, op, training, need_grad):
-    """The route of conv block `op` (engine.ConvBnRelu) of a plan whose 2-D tiles are R.w2tile / R.w2tile_dgrad (Runner.tile_for)."""
+    """The route of conv block `op` (engine.ConvBnRelu) of a plan whose 2-D tiles are R.w2tile / R.w2tile_dgrad (Runner.tile_for).  The block's
+    own flags decide its backward: no backward route when it is frozen with nothing upstream needing a gradient (op.active), no weight-grad
+    (and no V kept by the forward pass) when its conv weight is frozen (op.w_req), no data-grad when nothing upstream needs one."""
     lib, src = R.lib, op.src
+    bwd = need_grad and op.active
+    wg = bwd and op.w_req
     N, H, W, k, C, cin = src.N, src.H, src.W, src.ld, op.cout, op.cin
     ldy = pad4(C)
     fmt = split_fmt(R)
@@ -152,17 +156,17 @@ def conv_route(R, op, training, need_grad):
     # weight-grad: transposed 2-D F(4x4,3x3) for the channel-heavy layers (25-40 % faster than the transposed F(4,3) from 256 x 256
     # channels up: tools/bench_conv.py ww2d); 128 <-> 256 channels at 180x240 tie on the x transform alone, but their forward pass runs the
     # 2-D path and leaves V behind (0.78 of the F(4,3) time without that pass; 6x6 tiles: 0.46)
-    wgrad2d = bool(R.wino and R.wino2d and k % 4 == 0 and ldy == C and k >= 32 and C >= 64
+    wgrad2d = bool(wg and R.wino and R.wino2d and k % 4 == 0 and ldy == C and k >= 32 and C >= 64
                    and (R.wino2d == "always" or wgrad2d_pays(N, H, W, k, C) or (fwd2d and k * C >= 32768)))
     # ... else the transposed F(4,3): fastest weight-grad on every layer with >= 64 input channels (tools/bench_conv.py wgrad wwino wwino4)
-    wgrad4 = bool(not wgrad2d and R.wino and k >= 32 and C > 32 and (R.wino4 == "always" or (R.wino4 and k >= 64)))
+    wgrad4 = bool(wg and not wgrad2d and R.wino and k >= 32 and C > 32 and (R.wino4 == "always" or (R.wino4 and k >= 64)))
     # OPT-IN split-operand GEMMs (csrc/split3.hip): layers whose forward, data-grad and weight-grad ALL take the 2-D path with one tile and
     # whose channel counts the split weight-grad GEMM serves — the three GEMMs share their split planes (V from the forward transform, V'
     # and E from one pass over dy)
-    split = fmt if (need_grad and training and fmt and op.src_needs_grad and wgrad2d and k == cin and k % 32 == 0 and C % 32 == 0 and fwd2d
+    split = fmt if (wg and training and fmt and op.src_needs_grad and wgrad2d and k == cin and k % 32 == 0 and C % 32 == 0 and fwd2d
                     and dgrad2d and tile == dtile and ((C % 256 == 0 and k % 128 == 0) or (k % 256 == 0 and C % 128 == 0))) else 0
     # the fused forward launch leaves the V planes of a plane-GEMM weight-grad behind (csrc/wgradp.hip)
-    planes = bool(need_grad and R.vplanes and R.wgradp and fmt == 0 and wgrad4 and wgradp_ok(k, C, ldy) and vplanes_pays(lib, N, H, W, k, C))
+    planes = bool(wg and R.vplanes and R.wgradp and fmt == 0 and wgrad4 and wgradp_ok(k, C, ldy) and vplanes_pays(lib, N, H, W, k, C))
 
     if R.thin and lib.cvk_thin_fwd_supported(k, C, ldy) and (not training or k <= 8 or k == 64) and fits:
         fwd = "thin"            # the stem (3 -> 64) and the classifier head (64 -> 12): the thin side is one side of a 16x16x4 MFMA
@@ -175,14 +179,16 @@ def conv_route(R, op, training, need_grad):
         if fwd == "w4f" and planes:
             fwd = "w4f_vplanes"
     split = split if fwd == "w2d_split" else 0
-    if not need_grad:
+    if not bwd:
         return ConvRoute(fwd, tile if fwd in W2D else 0, split)
 
     # 64-input-channel layers (and every layer whose forward left V planes): both transforms outside the GEMM (csrc/wgradp.hip) — the E
     # planes come from the BatchNorm-backward pass; pays while the V pass over x is cheap (64 -> 64 @360x480 0.74x, 64 -> 128 @180x240 0.7x
     # the time of the transposed F(4,3) kernel; 128 input channels: the V pass eats the gain)
     wgradp = wgrad4 and R.wgradp and wgradp_ok(k, C, ldy) and (R.wgradp == "always" or fwd == "w4f_vplanes" or wgradp_pays(N, H, W, k, C))
-    if wgrad2d:
+    if not wg:
+        wgrad = None
+    elif wgrad2d:
         wgrad = "w2d_split" if split else "w2d"
     elif wgradp:
         wgrad = "wgradp_sm" if fwd == "w4f_vplanes" else "wgradp"
