@@ -6,6 +6,7 @@ and validation through train.py's valid transforms.  Synthetic frames stand in f
 package); random.seed makes the augmentation decisions of the reference's Compose under the same seed.
 
   python examples/train_augmented.py --epochs 2 --iters 20 -b 8
+  python examples/train_augmented.py --graphed --clip-grad-norm 1.0    # FlatAdamW with global-norm clipping, one graph replay per iteration
 """
 import argparse
 import os
@@ -42,29 +43,49 @@ def main():
     ap.add_argument("--class-weights", default="none", choices=["none", "median_frequency", "enet"],
                     help="class-weighted loss, weights from one pass over the training masks (cvk.class_weights)")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
+    ap.add_argument("--graphed", action="store_true", help="cvk.FlatAdamW and the whole iteration as one captured graph (cvk.GraphedStep)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the global gradient 2-norm to X (cvk.clip_grad_norm_; with --graphed: FlatAdamW(max_grad_norm=X), inside the "
+                    "captured step); prints the epoch's largest norm and the share of clipped steps")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     random.seed(a.seed)
     net = cvk.get_model(a.net, 3, 12).to(dev)
-    opt = torch.optim.AdamW(net.parameters(), lr=a.lr)
+    opt = cvk.FlatAdamW(net, lr=a.lr, max_grad_norm=a.clip_grad_norm) if a.graphed else torch.optim.AdamW(net.parameters(), lr=a.lr)
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=a.iters, epochs=a.epochs)
     weight = None
     if a.class_weights != "none":
         weight = cvk.class_weights((m for _, m in synthetic_camvid(a.iters, a.b, 1)), 12, method=a.class_weights, device=dev)
     loss_fn = cvk.CrossEntropyLoss(weight=weight, label_smoothing=a.label_smoothing)
     train_tf, valid_tf = transforms.train_transforms(), transforms.valid_transforms()
+    step = None
     for epoch in range(1, a.epochs + 1):
         net.train()
         t0 = time.time()
+        norms = []                                                          # device scalars: read once per epoch
         for images, masks in cvk.DevicePrefetcher(synthetic_camvid(a.iters, a.b, epoch), transforms=train_tf):
+            if a.graphed:
+                if step is None:
+                    step = cvk.GraphedStep(net, loss_fn, images, masks, optimizer=opt, scheduler=sched, log_capacity=a.iters)
+                loss = step.replay(images, masks)
+                continue
             opt.zero_grad()
             loss = loss_fn(net(images), masks)
             loss.backward()
+            if a.clip_grad_norm is not None:
+                norms.append(cvk.clip_grad_norm_(net, a.clip_grad_norm))    # reduction, finish, in-place scale: no host sync
             opt.step(); sched.step()
         torch.cuda.synchronize()
         dt = time.time() - t0
         print(f"epoch {epoch}: loss {loss.item():.4f}  {a.b * a.iters / dt:.1f} img/s (incl. host data synthesis)")
+        if step is not None:
+            rows, _ = step.log()                                            # with clipping: 7 columns, the norm is column 5
+            norms = list(torch.from_numpy(rows[:, 5].copy())) if a.clip_grad_norm is not None else []
+        if norms:
+            n = torch.stack([v.detach().float().cpu() for v in norms])
+            print(f"  grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of {n.numel()} steps "
+                  f"(max_norm {a.clip_grad_norm:g})")
         val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
         acc, iou, miou = cvk.evaluate(net, val, num_classes=12, ignore_index=11)
         print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}")

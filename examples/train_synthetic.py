@@ -5,6 +5,7 @@ augmentation of 960x720 frames on the device see examples/train_augmented.py.  E
 
   python examples/train_synthetic.py --net unet --epochs 2 --iters 20 -b 8
   python examples/train_synthetic.py --graphed      # each iteration (step, AdamW, log line) as ONE graph replay
+  python examples/train_synthetic.py --graphed --clip-grad-norm 1.0     # global-norm clipping inside the captured AdamW step
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_synthetic.py   # data parallel
 """
 import argparse
@@ -36,6 +37,9 @@ def main():
     ap.add_argument("--label-smoothing", type=float, default=0.0)
     ap.add_argument("--split-operands", type=int, default=0, choices=[0, 2, 3],
                     help="opt-in for fp32: matrix products on the 16-bit matrix pipe with split fp32 operands (cvk.set_split_operands; 2 = fp16 x 2)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the global gradient 2-norm to X: fused into the step with --flat-adamw / --graphed (FlatAdamW(max_grad_norm=X)), "
+                    "cvk.clip_grad_norm_ before torch's AdamW otherwise; prints the epoch's largest norm and the share of clipped steps")
     a = ap.parse_args()
     a.flat_adamw = a.flat_adamw or a.graphed
 
@@ -51,7 +55,7 @@ def main():
     cvk.set_conv_precision(net, a.precision)
     cvk.set_split_operands(net, a.split_operands)
     model = cvk.ddp.DataParallel(net) if world > 1 else net
-    opt = cvk.FlatAdamW(net, lr=a.lr, weight_decay=a.wd) if a.flat_adamw else \
+    opt = cvk.FlatAdamW(net, lr=a.lr, weight_decay=a.wd, max_grad_norm=a.clip_grad_norm) if a.flat_adamw else \
         torch.optim.AdamW(net.parameters(), lr=a.lr, weight_decay=a.wd)     # train.py:100
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=a.iters, epochs=a.epochs)  # :103-104
     g = torch.Generator().manual_seed(1234 + rank)
@@ -64,6 +68,7 @@ def main():
     for epoch in range(1, a.epochs + 1):
         net.train()
         t0 = time.time()
+        norms = []                                                          # device scalars: read once per epoch
         for it in range(a.iters):
             m = masks[it].to(dev)
             frames = ((m.unsqueeze(-1) * torch.tensor([20, 15, 10], device=dev)) % 256 +
@@ -79,12 +84,18 @@ def main():
             preds = model(images)                                           # :128
             loss = loss_fn(preds, m)                                        # :130
             loss.backward()                                                 # :131
+            if a.clip_grad_norm is not None and not a.flat_adamw:
+                norms.append(cvk.clip_grad_norm_(net, a.clip_grad_norm))    # reduction, finish, in-place scale: no host sync
             opt.step(); sched.step()                                        # :133-134
+            if a.clip_grad_norm is not None and a.flat_adamw:
+                norms.append(opt.grad_norm.clone())                         # the fused step's record
         torch.cuda.synchronize()
         dt = time.time() - t0
         if step is not None and rank == 0:
             rows, dropped = step.log()                                      # the epoch's per-iteration lines: one D2H copy
-            for i, (l, lr, beta, gw, gb) in enumerate(rows):                # train.py:135-143 + utils.visulaize_lastlayer
+            if a.clip_grad_norm is not None:                                # 7 columns: ..., global norm, clip coefficient
+                norms = list(torch.from_numpy(rows[:, 5].copy()))
+            for i, (l, lr, beta, gw, gb) in enumerate(rows[:, :5]):         # train.py:135-143 + utils.visulaize_lastlayer
                 print(("Training Epoch:{epoch} [{trained_samples}/{total_samples}] Lr:{lr:0.6f} Loss:{loss:0.4f} Beta1:{beta:0.4f} "
                        "grad_norm2_weights:{gw:0.4e} grad_norm2_bias:{gb:0.4e}").format(
                     epoch=epoch, trained_samples=(dropped + i + 1) * a.b, total_samples=a.iters * a.b, lr=lr, loss=l, beta=beta,
@@ -92,6 +103,10 @@ def main():
         if rank == 0:
             print(f"epoch {epoch}: loss {loss.item():.4f}  lr {sched.get_last_lr()[0]:.6f}  "
                   f"{world * a.b * a.iters / dt:.1f} img/s (incl. data synthesis + optimizer)")
+            if norms:
+                n = torch.stack([v.detach().float().cpu() for v in norms])
+                print(f"          grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of "
+                      f"{n.numel()} steps (max_norm {a.clip_grad_norm:g})")
         # validation (train.py:169-206) on two of the batches
         batches = []
         for it in range(2):

@@ -555,6 +555,49 @@ int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, f
 int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb, float* ring,
                  int capacity, int64_t* counter, void* stream);
 
+/* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) fused into the AdamW step ------------------------------------
+ * The norm of the flat gradient buffer over a table of EXACT parameter segments, as a device record {total_norm, clip_coef} that the
+ * clipped AdamW launches, the in-place scale and the log row read.  The flat gradient buffer is uninitialised between its segments
+ * (16-byte alignment padding, frozen parameters): the table lists [offset, offset + length) per parameter that has a gradient,
+ * neighbours merged only where no padding float lies between them.  No element outside the table is read.
+ *
+ * cvk_clip_coef (host function): torch's clip coefficient in fp32, max_norm / (total_norm + 1e-6f) clamped to at most 1 the way
+ *   torch.clamp(max=1) clamps: a NaN norm gives NaN, an infinite norm gives 0.  The finish kernel evaluates the same expression.
+ * cvk_grad_norm_plan (host function, no launch): checks a HOST copy of the table against the buffer length n (every segment inside
+ *   [0, n), length > 0), fills every block0 and returns the workgroup count the launches take as nblocks, or a negative error.
+ * cvk_grad_norm: two launches.  (1) nblocks workgroups reduce their share of the segments (16-byte loads where the address allows,
+ *   every element converted to fp64) into one fp64 partial each: the sum of squares (norm_type 2) or the maximum of |g| (norm_type
+ *   INFINITY; a NaN stays a NaN).  (2) one workgroup combines the partials in a fixed order and writes record[0] = total_norm (fp32:
+ *   the square root of the fp64 sum, rounded once) and record[1] = cvk_clip_coef(max_norm, total_norm).  No atomics: the record is
+ *   bitwise reproducible from run to run, eager or captured.  partials: DEVICE, nblocks doubles.  record: DEVICE, 2 floats.
+ *   max_norm >= 0; norm_type 2 or INFINITY, anything else is refused.
+ * cvk_grad_scale: grad[i] *= record[1] over the same table, in place (what torch's clip_grad_norm_ leaves in .grad); a coefficient
+ *   of exactly 1 leaves the buffer untouched.
+ * cvk_adamw_step_ranges_clip / _clip_dev: cvk_adamw_step_ranges / _dev with every gradient element multiplied by record[1] on its way
+ *   into the update (one more operand of the same expression list: with a coefficient of 1.0f the step is bitwise the unclipped one).
+ *   The gradient buffer is not rewritten.
+ * cvk_step_log_norm: cvk_step_log with rows of 7 floats: the five columns, then record[0] and record[1]. */
+typedef struct cvk_norm_segment {
+    int64_t offset;              /* first element of the segment in the flat gradient buffer */
+    int64_t length;              /* elements, > 0 */
+    int32_t block0;              /* first workgroup of the segment (cvk_grad_norm_plan) */
+    int32_t reserved;
+} cvk_norm_segment;
+float cvk_clip_coef(float max_norm, float total_norm);
+int cvk_grad_norm_plan(cvk_norm_segment* segments, int nsegments, int64_t n);
+int cvk_grad_norm(const float* grad, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks, float norm_type,
+                  float max_norm, double* partials, float* record, void* stream);
+int cvk_grad_scale(float* grad, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks, const float* record,
+                   void* stream);
+int cvk_adamw_step_ranges_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                               const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                               const float* record, void* stream);
+int cvk_adamw_step_ranges_clip_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                   const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                                   const float* record, void* stream);
+int cvk_step_log_norm(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb,
+                      const float* record, float* ring, int capacity, int64_t* counter, void* stream);
+
 
 /* ================================================================================================================
  * bf16-storage path (BASELINE.json configs[3] "bf16 + MFMA im2col path"; set_conv_precision(net, "bf16")).

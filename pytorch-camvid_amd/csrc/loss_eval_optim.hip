@@ -515,12 +515,14 @@ __global__ __launch_bounds__(256) void k_confusion(const int64_t* __restrict__ p
         if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
 }
 
-// One AdamW element update (torch.optim.AdamW, decoupled weight decay).  Shared by k_adamw (scalars as kernel arguments) and
-// k_adamw_dev (scalars from a device record): one expression list, so the two cannot round differently.
+// One AdamW element update (torch.optim.AdamW, decoupled weight decay).  Shared by k_adamw (scalars as kernel arguments),
+// k_adamw_dev (scalars from a device record) and the range-table kernels: one expression list, so they cannot round differently.
+// coef scales the gradient on its way in (global-norm clipping, cvk_adamw_step_ranges_clip*); the unclipped kernels pass the
+// literal 1.f, and x * 1.f is x.
 __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                              float* __restrict__ v, int64_t i, float lr, float b1, float b2, float eps, float wd,
-                                             float bc1, float bc2_sqrt) {
-    const float gi = g[i];
+                                             float bc1, float bc2_sqrt, float coef) {
+    const float gi = g[i] * coef;
     float pi = p[i] * (1.f - lr * wd);
     const float mi = b1 * m[i] + (1.f - b1) * gi;
     const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
@@ -534,7 +536,7 @@ __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float*
 __global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                         int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, 1.f);
 }
 
 // The captured-graph form: the scalars come from a device record the host rewrites before every replay (uniform loads,
@@ -544,7 +546,7 @@ __global__ void k_adamw_dev(float* __restrict__ p, const float* __restrict__ g, 
     const float lr = hyper->lr, b1 = hyper->beta1, b2 = hyper->beta2, eps = hyper->eps, wd = hyper->weight_decay;
     const float bc1 = hyper->bc1, bc2_sqrt = hyper->bc2_sqrt;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, 1.f);
 }
 
 // AdamW over a range table (cvk_adamw_step_ranges*): workgroup b serves the range whose block0 is the last one <= b (a uniform binary
@@ -557,7 +559,8 @@ struct AdamwArgRecords {
 
 __device__ __forceinline__ void adamw_ranges_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                   float* __restrict__ v, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
-                                                  const cvk_adamw_hyper* __restrict__ hyper, int nhyper) {
+                                                  const cvk_adamw_hyper* __restrict__ hyper, int nhyper,
+                                                  const float* __restrict__ clip) {
     const int b = blockIdx.x;
     int lo = 0, hi = nr - 1;
     while (lo < hi) {
@@ -571,19 +574,33 @@ __device__ __forceinline__ void adamw_ranges_body(float* __restrict__ p, const f
     if (off < 0 || len <= 0 || off + len > n || hx < 0 || hx >= nhyper || nb <= 0 || b < b0) return;
     const float lr = hyper[hx].lr, b1 = hyper[hx].beta1, b2 = hyper[hx].beta2, eps = hyper[hx].eps, wd = hyper[hx].weight_decay;
     const float bc1 = hyper[hx].bc1, bc2_sqrt = hyper[hx].bc2_sqrt;
+    const float coef = clip != nullptr ? clip[1] : 1.f;           // the {total_norm, clip_coef} record of cvk_grad_norm, once per thread
     for (int64_t i = off + (int64_t)(b - b0) * blockDim.x + threadIdx.x; i < off + len; i += (int64_t)nb * blockDim.x)
-        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, coef);
 }
 
 __global__ void k_adamw_ranges(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                                const cvk_adamw_range* __restrict__ rt, int nr, AdamwArgRecords recs, int nhyper) {
-    adamw_ranges_body(p, g, m, v, n, rt, nr, recs.r, nhyper);
+    adamw_ranges_body(p, g, m, v, n, rt, nr, recs.r, nhyper, nullptr);
 }
 
 __global__ void k_adamw_ranges_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                    int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, const cvk_adamw_hyper* __restrict__ hyper,
                                    int nhyper) {
-    adamw_ranges_body(p, g, m, v, n, rt, nr, hyper, nhyper);
+    adamw_ranges_body(p, g, m, v, n, rt, nr, hyper, nhyper, nullptr);
+}
+
+// The clipped forms (cvk_adamw_step_ranges_clip*): the same body, the gradient scaled by the clip coefficient of the device record.
+__global__ void k_adamw_ranges_clip(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                    int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, AdamwArgRecords recs, int nhyper,
+                                    const float* __restrict__ clip) {
+    adamw_ranges_body(p, g, m, v, n, rt, nr, recs.r, nhyper, clip);
+}
+
+__global__ void k_adamw_ranges_clip_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                        int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
+                                        const cvk_adamw_hyper* __restrict__ hyper, int nhyper, const float* __restrict__ clip) {
+    adamw_ranges_body(p, g, m, v, n, rt, nr, hyper, nhyper, clip);
 }
 
 // One row [loss, lr, beta1, ||gw||_2, ||gb||_2] of the per-iteration log into ring[(*counter % capacity) * 5 ..], then ++*counter.
@@ -607,21 +624,184 @@ __device__ __forceinline__ double block_sum_sq_f64(const float* __restrict__ x, 
     return r;
 }
 
-__global__ __launch_bounds__(STEP_LOG_THREADS) void k_step_log(const float* __restrict__ loss, const cvk_adamw_hyper* __restrict__ hyper,
-                                                               const float* __restrict__ gw, int nw, const float* __restrict__ gb, int nb,
-                                                               float* __restrict__ ring, int capacity, int64_t* __restrict__ counter) {
+// COLS = 5: cvk_step_log; COLS = 7: cvk_step_log_norm, the row ends in the {total_norm, clip_coef} record of cvk_grad_norm.
+template <int COLS>
+__device__ __forceinline__ void step_log_body(const float* __restrict__ loss, const cvk_adamw_hyper* __restrict__ hyper,
+                                              const float* __restrict__ gw, int nw, const float* __restrict__ gb, int nb,
+                                              const float* __restrict__ rec, float* __restrict__ ring, int capacity,
+                                              int64_t* __restrict__ counter) {
     __shared__ double red[STEP_LOG_THREADS];
     const double sw = block_sum_sq_f64(gw, nw, red);
     const double sb = block_sum_sq_f64(gb, nb, red);
     if (threadIdx.x == 0) {
         const int64_t c = *counter;
-        float* row = ring + (c % capacity) * 5;
+        float* row = ring + (c % capacity) * COLS;
         row[0] = *loss;
         row[1] = hyper->lr;
         row[2] = hyper->beta1;
         row[3] = (float)sqrt(sw);
         row[4] = (float)sqrt(sb);
+        if (COLS == 7) {
+            row[5] = rec[0];
+            row[6] = rec[1];
+        }
         *counter = c + 1;
+    }
+}
+
+__global__ __launch_bounds__(STEP_LOG_THREADS) void k_step_log(const float* __restrict__ loss, const cvk_adamw_hyper* __restrict__ hyper,
+                                                               const float* __restrict__ gw, int nw, const float* __restrict__ gb, int nb,
+                                                               float* __restrict__ ring, int capacity, int64_t* __restrict__ counter) {
+    step_log_body<5>(loss, hyper, gw, nw, gb, nb, nullptr, ring, capacity, counter);
+}
+
+__global__ __launch_bounds__(STEP_LOG_THREADS) void k_step_log_norm(const float* __restrict__ loss,
+                                                                    const cvk_adamw_hyper* __restrict__ hyper,
+                                                                    const float* __restrict__ gw, int nw, const float* __restrict__ gb,
+                                                                    int nb, const float* __restrict__ rec, float* __restrict__ ring,
+                                                                    int capacity, int64_t* __restrict__ counter) {
+    step_log_body<7>(loss, hyper, gw, nw, gb, nb, rec, ring, capacity, counter);
+}
+
+// ---- global-norm gradient clipping (cvk_grad_norm, cvk_grad_scale) -----------------------------------------------------------------
+// torch.nn.utils.clip_grad_norm_'s coefficient in fp32: clamp(max_norm / (total_norm + 1e-6), max=1).  `c > 1 ? 1 : c` keeps a NaN
+// (fminf would return 1).  One expression for the host entry point and the finish kernel (IEEE division on both sides).
+__host__ __device__ __forceinline__ float clip_coef_f32(float max_norm, float total_norm) {
+    const float c = max_norm / (total_norm + 1e-6f);
+    return c > 1.f ? 1.f : c;
+}
+
+constexpr int NORM_THREADS = 256;
+constexpr int NORM_UNROLL = 4;                  // independent 16-byte loads per lane and trip
+constexpr int NORM_MAX_BLOCKS = 2048;           // 8 workgroups per CU: a grid-stride streaming read
+
+// The workgroup's segment (uniform binary search over block0, as adamw_ranges_body) and its place among the segment's workgroups.
+// False when the table entry is unusable (cvk_grad_norm_plan refuses such a table on the host).
+__device__ __forceinline__ bool norm_segment_of(const cvk_norm_segment* __restrict__ st, int ns, int64_t n, int64_t* off, int64_t* len,
+                                                int* rank, int* nb) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = ns - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (st[mid].block0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    *off = st[lo].offset;
+    *len = st[lo].length;
+    const int b0 = st[lo].block0;
+    *nb = (lo + 1 < ns ? st[lo + 1].block0 : (int)gridDim.x) - b0;
+    *rank = b - b0;
+    return *off >= 0 && *len > 0 && *off + *len <= n && *nb > 0 && b >= b0;
+}
+
+// A segment as [head scalars][16-byte vectors][tail scalars]: head = the elements before the first 16-byte boundary of g + off.
+__device__ __forceinline__ int64_t norm_head(const float* g, int64_t off, int64_t len) {
+    const int64_t h = (4 - (int64_t)((reinterpret_cast<uintptr_t>(g + off) >> 2) & 3)) & 3;
+    return h < len ? h : len;
+}
+
+// NaN-keeping maximum: once m is a NaN it stays one (torch.linalg.vector_norm(inf) of a buffer with a NaN is NaN).
+__device__ __forceinline__ double norm_max(double m, double x) { return (x > m || x != x) ? x : m; }
+
+template <bool INF>
+__device__ __forceinline__ double norm_acc(double a, float x) {
+    const double d = (double)x;
+    return INF ? norm_max(a, fabs(d)) : fma(d, d, a);
+}
+
+template <bool INF>
+__device__ __forceinline__ double norm_join(double a, double b) { return INF ? norm_max(a, b) : a + b; }
+
+// A fixed tree: xor-shuffles inside each wave, then the 4 wave results in order.  Every thread of the workgroup calls it.
+template <bool INF>
+__device__ __forceinline__ double norm_block_reduce(double a, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a = norm_join<INF>(a, __shfl_xor(a, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    return norm_join<INF>(norm_join<INF>(red[0], red[1]), norm_join<INF>(red[2], red[3]));
+}
+
+template <bool INF>
+__global__ __launch_bounds__(NORM_THREADS) void k_grad_norm_partial(const float* __restrict__ g, int64_t n,
+                                                                    const cvk_norm_segment* __restrict__ st, int ns,
+                                                                    double* __restrict__ partials) {
+    __shared__ double red[NORM_THREADS / 64];
+    int64_t off, len;
+    int rank, nb;
+    const bool ok = norm_segment_of(st, ns, n, &off, &len, &rank, &nb);      // uniform
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if (ok) {
+        const int64_t head = norm_head(g, off, len);
+        const int64_t nvec = (len - head) >> 2;
+        const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + off + head);
+        const int64_t tid = (int64_t)rank * NORM_THREADS + threadIdx.x, stride = (int64_t)nb * NORM_THREADS;
+        int64_t i = tid;
+        for (; i + (NORM_UNROLL - 1) * stride < nvec; i += NORM_UNROLL * stride) {
+            f32x4 x[NORM_UNROLL];
+#pragma unroll
+            for (int u = 0; u < NORM_UNROLL; ++u) x[u] = gv[i + u * stride];
+#pragma unroll
+            for (int u = 0; u < NORM_UNROLL; ++u) {
+                a0 = norm_acc<INF>(a0, x[u][0]);
+                a1 = norm_acc<INF>(a1, x[u][1]);
+                a2 = norm_acc<INF>(a2, x[u][2]);
+                a3 = norm_acc<INF>(a3, x[u][3]);
+            }
+        }
+        for (; i < nvec; i += stride) {
+            const f32x4 x = gv[i];
+            a0 = norm_acc<INF>(a0, x[0]);
+            a1 = norm_acc<INF>(a1, x[1]);
+            a2 = norm_acc<INF>(a2, x[2]);
+            a3 = norm_acc<INF>(a3, x[3]);
+        }
+        // the at most 3 + 3 elements around the vectors: the segment's first thread
+        if (tid == 0) {
+            for (int64_t j = 0; j < head; ++j) a0 = norm_acc<INF>(a0, g[off + j]);
+            for (int64_t j = head + 4 * nvec; j < len; ++j) a0 = norm_acc<INF>(a0, g[off + j]);
+        }
+    }
+    const double a = norm_join<INF>(norm_join<INF>(a0, a1), norm_join<INF>(a2, a3));
+    const double r = norm_block_reduce<INF>(a, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = r;                 // every workgroup writes its slot: the finish reads all of them
+}
+
+// One workgroup: thread t joins partials t, t + 256, ... in order, then the fixed tree; thread 0 writes {total_norm, clip_coef}.
+template <bool INF>
+__global__ __launch_bounds__(NORM_THREADS) void k_grad_norm_finish(const double* __restrict__ partials, int nblocks, float max_norm,
+                                                                   float* __restrict__ rec) {
+    __shared__ double red[NORM_THREADS / 64];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += NORM_THREADS) a = norm_join<INF>(a, partials[i]);
+    const double r = norm_block_reduce<INF>(a, red);
+    if (threadIdx.x == 0) {
+        const float total = INF ? (float)r : (float)sqrt(r);
+        rec[0] = total;
+        rec[1] = clip_coef_f32(max_norm, total);
+    }
+}
+
+// grad[i] *= clip_coef over the segment table (cvk_grad_scale).  A coefficient of exactly 1 leaves the buffer untouched.
+__global__ __launch_bounds__(NORM_THREADS) void k_grad_scale(float* __restrict__ g, int64_t n, const cvk_norm_segment* __restrict__ st,
+                                                             int ns, const float* __restrict__ rec) {
+    const float coef = rec[1];
+    if (coef == 1.f) return;
+    int64_t off, len;
+    int rank, nb;
+    if (!norm_segment_of(st, ns, n, &off, &len, &rank, &nb)) return;
+    const int64_t head = norm_head(g, off, len);
+    const int64_t nvec = (len - head) >> 2;
+    f32x4* __restrict__ gv = reinterpret_cast<f32x4*>(g + off + head);
+    const int64_t tid = (int64_t)rank * NORM_THREADS + threadIdx.x, stride = (int64_t)nb * NORM_THREADS;
+    for (int64_t i = tid; i < nvec; i += stride) {
+        f32x4 x = gv[i];
+        x[0] *= coef; x[1] *= coef; x[2] *= coef; x[3] *= coef;
+        gv[i] = x;
+    }
+    if (tid == 0) {
+        for (int64_t j = 0; j < head; ++j) g[off + j] *= coef;
+        for (int64_t j = head + 4 * nvec; j < len; ++j) g[off + j] *= coef;
     }
 }
 
@@ -1014,6 +1194,101 @@ extern "C" int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, con
     hipLaunchKernelGGL(k_step_log, dim3(1), dim3(STEP_LOG_THREADS), 0, (hipStream_t)stream, loss, hyper, gw, nw, gb, nb, ring, capacity,
                        counter);
     CVK_LAUNCH_RETURN("cvk_step_log");
+}
+
+extern "C" int cvk_step_log_norm(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb,
+                                 const float* record, float* ring, int capacity, int64_t* counter, void* stream) {
+    CVK_CHECK_ARG(loss && hyper && gw && gb && record && ring && counter, "cvk_step_log_norm: null pointer");
+    CVK_CHECK_ARG(nw > 0 && nb > 0 && capacity > 0, "cvk_step_log_norm: bad arguments");
+    hipLaunchKernelGGL(k_step_log_norm, dim3(1), dim3(STEP_LOG_THREADS), 0, (hipStream_t)stream, loss, hyper, gw, nw, gb, nb, record, ring,
+                       capacity, counter);
+    CVK_LAUNCH_RETURN("cvk_step_log_norm");
+}
+
+extern "C" float cvk_clip_coef(float max_norm, float total_norm) { return clip_coef_f32(max_norm, total_norm); }
+
+// Workgroups per segment: one per NORM_THREADS * NORM_UNROLL 16-byte vectors, at most NORM_MAX_BLOCKS in all (shared in proportion to
+// the lengths), at least one.
+extern "C" int cvk_grad_norm_plan(cvk_norm_segment* segments, int nsegments, int64_t n) {
+    CVK_CHECK_ARG(segments, "cvk_grad_norm_plan: null pointer");
+    CVK_CHECK_ARG(nsegments > 0 && n > 0, "cvk_grad_norm_plan: empty table or buffer (%d segments, %lld elements)", nsegments, (long long)n);
+    int64_t total = 0;
+    for (int r = 0; r < nsegments; ++r) {
+        const cvk_norm_segment& e = segments[r];
+        CVK_CHECK_ARG(e.offset >= 0 && e.length > 0 && e.length <= n && e.offset <= n - e.length, "cvk_grad_norm_plan: segment %d [%lld, "
+                      "+%lld) outside the buffer of %lld elements", r, (long long)e.offset, (long long)e.length, (long long)n);
+        total += e.length;
+    }
+    const int64_t per = (int64_t)NORM_THREADS * NORM_UNROLL * 4;
+    int64_t budget = (total + per - 1) / per;
+    if (budget > NORM_MAX_BLOCKS) budget = NORM_MAX_BLOCKS;
+    int64_t blocks = 0;
+    for (int r = 0; r < nsegments; ++r) {
+        int64_t nb = (segments[r].length + per - 1) / per;
+        const int64_t share = (int64_t)(((__int128)budget * segments[r].length + total - 1) / total);
+        if (nb > share) nb = share;
+        if (nb < 1) nb = 1;
+        segments[r].block0 = (int32_t)blocks;
+        blocks += nb;
+        CVK_CHECK_ARG(blocks < (1LL << 30), "cvk_grad_norm_plan: too many workgroups");
+    }
+    return (int)blocks;
+}
+
+extern "C" int cvk_grad_norm(const float* grad, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks, float norm_type,
+                             float max_norm, double* partials, float* record, void* stream) {
+    CVK_CHECK_ARG(grad && segments && partials && record, "cvk_grad_norm: null pointer");
+    CVK_CHECK_ARG(n > 0 && nsegments > 0 && nblocks >= nsegments, "cvk_grad_norm: empty table or buffer (%d segments, %d workgroups)",
+                  nsegments, nblocks);
+    const bool inf = norm_type == __builtin_inff();
+    CVK_CHECK_ARG(inf || norm_type == 2.f, "cvk_grad_norm: norm_type %g (2 and infinity are implemented)", (double)norm_type);
+    CVK_CHECK_ARG(max_norm >= 0.f, "cvk_grad_norm: max_norm %g is negative or not a number", (double)max_norm);
+    CVK_CHECK_ARG((((uintptr_t)grad) & 3u) == 0 && (((uintptr_t)partials) & 7u) == 0, "cvk_grad_norm: misaligned buffer");
+    if (inf) {
+        hipLaunchKernelGGL(k_grad_norm_partial<true>, dim3(nblocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, grad, n, segments, nsegments,
+                           partials);
+        hipLaunchKernelGGL(k_grad_norm_finish<true>, dim3(1), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const double*)partials, nblocks,
+                           max_norm, record);
+    } else {
+        hipLaunchKernelGGL(k_grad_norm_partial<false>, dim3(nblocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, grad, n, segments, nsegments,
+                           partials);
+        hipLaunchKernelGGL(k_grad_norm_finish<false>, dim3(1), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const double*)partials, nblocks,
+                           max_norm, record);
+    }
+    CVK_LAUNCH_RETURN("cvk_grad_norm");
+}
+
+extern "C" int cvk_grad_scale(float* grad, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks, const float* record,
+                              void* stream) {
+    CVK_CHECK_ARG(grad && segments && record, "cvk_grad_scale: null pointer");
+    CVK_CHECK_ARG(n > 0 && nsegments > 0 && nblocks >= nsegments, "cvk_grad_scale: empty table or buffer (%d segments, %d workgroups)",
+                  nsegments, nblocks);
+    CVK_CHECK_ARG((((uintptr_t)grad) & 3u) == 0, "cvk_grad_scale: misaligned buffer");
+    hipLaunchKernelGGL(k_grad_scale, dim3(nblocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, grad, n, segments, nsegments, record);
+    CVK_LAUNCH_RETURN("cvk_grad_scale");
+}
+
+extern "C" int cvk_adamw_step_ranges_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                          const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                                          const float* record, void* stream) {
+    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper && record, "cvk_adamw_step_ranges_clip: null pointer");
+    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
+                  "cvk_adamw_step_ranges_clip: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
+    AdamwArgRecords recs = {};
+    for (int i = 0; i < nhyper; ++i) recs.r[i] = hyper[i];
+    hipLaunchKernelGGL(k_adamw_ranges_clip, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, ranges,
+                       nranges, recs, nhyper, record);
+    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_clip");
+}
+
+extern "C" int cvk_adamw_step_ranges_clip_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                              const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper,
+                                              int nhyper, const float* record, void* stream) {
+    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper && record, "cvk_adamw_step_ranges_clip_dev: null pointer");
+    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_adamw_step_ranges_clip_dev: bad arguments");
+    hipLaunchKernelGGL(k_adamw_ranges_clip_dev, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
+                       ranges, nranges, hyper, nhyper, record);
+    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_clip_dev");
 }
 
 // ---- library-wide pieces ---------------------------------------------------------------------------------------

@@ -23,7 +23,10 @@ the captured all-reduces under data parallel), and with `log_capacity=` it ends 
 line [loss, lr, beta1, ||last weight grad||, ||last bias grad||] to a device ring.  lr, betas, eps and weight decay of every parameter
 group are read at every replay, the bias corrections computed on the host and uploaded into device records the graph reads (one per
 group and step count, cvk_adamw_step_ranges_dev; the log row reads param_groups[0], as the reference prints), so a scheduler drives the
-captured optimizer as it drives the eager one.  Frozen parameters (requires_grad False, BatchNorm children in eval mode) are captured as
+captured optimizer as it drives the eager one.  A FlatAdamW with `max_grad_norm` is captured with its norm reduction and finish between
+backward and the AdamW launch (after the stream's waits for the all-reduces: every rank reduces the same averaged buffer, so no extra
+collective), and the log rows gain the global norm and the clip coefficient; `max_grad_norm` / `norm_type` are baked into the graph.
+Frozen parameters (requires_grad False, BatchNorm children in eval mode) are captured as
 they are when the GraphedStep is built; replay() refuses to run after any of that changes:
 
     opt = FlatAdamW(net, lr=...); sched = OneCycleLR(opt, ...)
@@ -104,9 +107,13 @@ class GraphedStep:
             self._hyper_pin = torch.zeros(HYPER_SLOTS, nrec * HYPER_FLOATS, dtype=torch.float32, pin_memory=True)
             self._hyper_busy = [None] * HYPER_SLOTS     # per slot: event after the H2D copy that READ it
             self._hyper_slot = 0
+            # global-norm clipping (FlatAdamW(max_grad_norm=...)): the norm's segment table and partials are uploaded before the capture
+            self._clip = optimizer._clip_options()
+            self._norm_plan = optimizer._norm_plan(self._opt_idx) if self._clip[0] is not None else None
+        self._log_cols = _lib.STEP_LOG_NORM_COLUMNS if optimizer is not None and self._clip[0] is not None else _lib.STEP_LOG_COLUMNS
         if log_capacity:
-            # one buffer, so that log() is one D2H copy: int64 row counter, then capacity rows of STEP_LOG_COLUMNS floats
-            self._logbuf = torch.zeros(2 + log_capacity * _lib.STEP_LOG_COLUMNS, device=x.device, dtype=torch.float32)
+            # one buffer, so that log() is one D2H copy: int64 row counter, then capacity rows of _log_cols floats
+            self._logbuf = torch.zeros(2 + log_capacity * self._log_cols, device=x.device, dtype=torch.float32)
             self._log_read = 0                  # rows the host has consumed
             (_, self._log_w), (_, self._log_b) = last_layer_params(net)
         cur = torch.cuda.current_stream(x.device)
@@ -148,9 +155,18 @@ class GraphedStep:
         opt = self.optimizer
         if opt is not None:
             self._gflat = opt._flat_grad(self._opt_idx)     # the executor's flat gradient buffer (graph pool): same address in every replay
-            check(lib.cvk_adamw_step_ranges_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
-                                                opt._flat.numel(), self._table.data_ptr(), len(self._opt_ranges), self._table_blocks,
-                                                self._hyper.data_ptr() + HYPER_BYTES, len(self._opt_recs), stream), "cvk_adamw_step_ranges_dev")
+            if self._norm_plan is not None:
+                # reduction + finish into the optimizer's {total_norm, clip_coef} record, then the AdamW launch that scales by it
+                self._norm_plan.norm(self._gflat.data_ptr(), self._clip[1], self._clip[0], opt._clip_rec, stream)
+                check(lib.cvk_adamw_step_ranges_clip_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
+                                                         opt._flat.numel(), self._table.data_ptr(), len(self._opt_ranges),
+                                                         self._table_blocks, self._hyper.data_ptr() + HYPER_BYTES, len(self._opt_recs),
+                                                         opt._clip_rec.data_ptr(), stream), "cvk_adamw_step_ranges_clip_dev")
+            else:
+                check(lib.cvk_adamw_step_ranges_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
+                                                    opt._flat.numel(), self._table.data_ptr(), len(self._opt_ranges), self._table_blocks,
+                                                    self._hyper.data_ptr() + HYPER_BYTES, len(self._opt_recs), stream),
+                      "cvk_adamw_step_ranges_dev")
         if self.log_capacity:
             gw, gb = self._log_w.grad, self._log_b.grad
             if gw is None or gb is None:
@@ -159,8 +175,13 @@ class GraphedStep:
             for g in (gw, gb):
                 if not (g.is_contiguous() or g.is_contiguous(memory_format=torch.channels_last)):
                     raise RuntimeError("GraphedStep: the last layer's gradient is not one dense block")
-            check(lib.cvk_step_log(self.loss.data_ptr(), self._hyper.data_ptr(), gw.data_ptr(), gw.numel(), gb.data_ptr(), gb.numel(),
-                                   self._logbuf.data_ptr() + 8, self.log_capacity, self._logbuf.data_ptr(), stream), "cvk_step_log")
+            if self._log_cols == _lib.STEP_LOG_NORM_COLUMNS:
+                check(lib.cvk_step_log_norm(self.loss.data_ptr(), self._hyper.data_ptr(), gw.data_ptr(), gw.numel(), gb.data_ptr(),
+                                            gb.numel(), opt._clip_rec.data_ptr(), self._logbuf.data_ptr() + 8, self.log_capacity,
+                                            self._logbuf.data_ptr(), stream), "cvk_step_log_norm")
+            else:
+                check(lib.cvk_step_log(self.loss.data_ptr(), self._hyper.data_ptr(), gw.data_ptr(), gw.numel(), gb.data_ptr(), gb.numel(),
+                                       self._logbuf.data_ptr() + 8, self.log_capacity, self._logbuf.data_ptr(), stream), "cvk_step_log")
 
     def _upload_hyper(self):
         """Every group as the scheduler left it + the next step counts -> the device records, on the current stream (no host sync: the host
@@ -185,7 +206,9 @@ class GraphedStep:
 
     def log(self):
         """The log rows the replays wrote since the previous call, oldest first: (rows [k, 5] float32 numpy array of
-        [loss, lr, beta1, ||grad of the last weight||_2, ||grad of the last bias||_2], dropped).  When more than log_capacity rows were
+        [loss, lr, beta1, ||grad of the last weight||_2, ||grad of the last bias||_2], dropped).  With a clipping optimizer
+        (FlatAdamW(max_grad_norm=...)) the rows have 7 columns: the five, then the step's global gradient norm and its clip coefficient.
+        When more than log_capacity rows were
         written since the last call, the oldest were overwritten on the device: rows holds the newest log_capacity of them and
         dropped says how many were lost.  One device-to-host copy (waits for the replays enqueued so far)."""
         import numpy as np
@@ -194,11 +217,11 @@ class GraphedStep:
         buf = self._logbuf.cpu().numpy()
         written = int(buf[:2].view(np.int64)[0])
         cap = self.log_capacity
-        ring = buf[2:].reshape(cap, _lib.STEP_LOG_COLUMNS)
+        ring = buf[2:].reshape(cap, self._log_cols)
         new = written - self._log_read
         dropped = max(0, new - cap)
         first = written - min(new, cap)
-        rows = ring[[i % cap for i in range(first, written)]].copy() if written > first else np.zeros((0, _lib.STEP_LOG_COLUMNS), np.float32)
+        rows = ring[[i % cap for i in range(first, written)]].copy() if written > first else np.zeros((0, self._log_cols), np.float32)
         self._log_read = written
         return rows, dropped
 
@@ -219,7 +242,8 @@ class GraphedStep:
         opt = getattr(self, "optimizer", None)
         if opt is None:
             return ()
-        return (id(opt), len(opt.param_groups), tuple(opt._group_of()), opt._flat.data_ptr(), tuple(p.data_ptr() for p in opt._plist))
+        return (id(opt), len(opt.param_groups), tuple(opt._group_of()), opt._flat.data_ptr(), tuple(p.data_ptr() for p in opt._plist),
+                opt.max_grad_norm, opt.norm_type)
 
     def replay(self, x=None, t=None):
         """Copy a new batch into the static input buffers (optional) and replay the step.  Returns the (static) loss tensor.
@@ -228,8 +252,8 @@ class GraphedStep:
         if self._signature() != self._sig:
             raise RuntimeError("GraphedStep.replay: the network changed since the capture (train/eval mode of the network or of a "
                                "block's BatchNorm, a parameter's requires_grad, a swapped block, conv precision, a kernel "
-                               "knob, it was wrapped in / unwrapped from ddp.DataParallel, or the captured FlatAdamW was rebuilt, re-homed or "
-                               "regrouped): the "
+                               "knob, it was wrapped in / unwrapped from ddp.DataParallel, or the captured FlatAdamW was rebuilt, re-homed, "
+                               "regrouped or given another max_grad_norm / norm_type): the "
                                "captured graph would silently run the "
                                "old configuration — build a new GraphedStep")
         if x is not None:

@@ -8,8 +8,17 @@ elements (7 x 138 MB of HBM traffic) instead of ~10 multi-tensor launches over 9
 Fine-tuning: `groups=` takes torch-style parameter groups (every parameter of the network in exactly one group; per-group `lr`, `betas`,
 `eps`, `weight_decay`).  As torch.optim.AdamW, a parameter whose `.grad` is None is skipped and each parameter keeps its own step count (a
 block unfrozen late starts its bias correction at 1).  The step is one launch over a device table of the trainable ranges of the flat
-buffer (cvk_adamw_step_ranges): frozen parameters and their moments are neither read nor written."""
+buffer (cvk_adamw_step_ranges): frozen parameters and their moments are neither read nor written.
+
+Gradient clipping: `FlatAdamW(net, max_grad_norm=X, norm_type=2.0)` clips by the global norm inside the step.  A deterministic fp64
+reduction over the exact gradient segments of the parameters that take the step (all groups together, as torch's clip is global) writes a
+device record {total_norm, clip_coef}; the AdamW launch multiplies every gradient element by clip_coef on its way into the update
+(cvk_adamw_step_ranges_clip).  `.grad` is NOT rescaled — the one difference from the two-call idiom `clip_grad_norm_(...); opt.step()`,
+which rewrites all gradients in place: after a clipped step `.grad` still holds what backward produced, `opt.grad_norm` its norm and
+`opt.clip_coef` the factor the update applied.  `clip_grad_norm_` below is the stand-alone form with torch's contract (scaled `.grad`s).
+Parameter gradients are fp32 in every mode (fp32, bf16 storage, split operands), so clipping is the same code under all of them."""
 import ctypes
+import math
 
 import torch
 
@@ -26,8 +35,116 @@ def _block_params(net):
     return out
 
 
+def _check_clip_options(max_norm, norm_type, what):
+    """(max_norm or None, norm_type) as floats; ValueError for a negative / NaN max_norm or a norm_type other than 2 and infinity."""
+    try:
+        nt = float(norm_type)
+    except (TypeError, ValueError):
+        nt = float("nan")
+    if not (nt == 2.0 or nt == math.inf):
+        raise ValueError(f"{what}: norm_type {norm_type!r} is not implemented (2 and infinity are)")
+    if max_norm is None:
+        return None, nt
+    mx = float(max_norm)
+    if not mx >= 0.0:
+        raise ValueError(f"{what}: max_norm {max_norm!r} must be >= 0")
+    return mx, nt
+
+
+def norm_segments(pairs):
+    """The segment table of a gradient norm: `pairs` = (offset, numel) of every parameter that has a gradient, in floats of the flat gradient
+    buffer.  Sorted by offset; neighbours are merged only when the first ends exactly where the second begins, so no alignment padding
+    (engine.layout_grads rounds every parameter up to 4 floats and the buffer is torch.empty) and no frozen parameter's segment is ever
+    covered.  Overlapping entries are refused."""
+    out = []
+    for o, n in sorted((int(o), int(n)) for o, n in pairs):
+        if n <= 0:
+            continue
+        if out and o < out[-1][0] + out[-1][1]:
+            raise ValueError("norm_segments: overlapping gradient segments")
+        if out and out[-1][0] + out[-1][1] == o:
+            out[-1] = (out[-1][0], out[-1][1] + n)
+        else:
+            out.append((o, n))
+    return out
+
+
+class _NormPlan:
+    """A planned segment table on the device, its workgroup count and the fp64 partials buffer of the reduction."""
+
+    def __init__(self, segments, n, device):
+        lib = _lib.load()
+        if not segments:
+            raise RuntimeError("gradient norm: no parameter has a gradient")
+        arr = (_lib.NormSegment * len(segments))(*[_lib.NormSegment(o, m, 0, 0) for o, m in segments])
+        nb = lib.cvk_grad_norm_plan(ctypes.addressof(arr), len(segments), n)
+        if nb <= 0:
+            check(nb if nb < 0 else -1, "cvk_grad_norm_plan")
+        self.nseg, self.n, self.blocks = len(segments), n, nb
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+        self.partials = torch.empty(nb, device=device, dtype=torch.float64)
+
+    def norm(self, grad_ptr, norm_type, max_norm, rec, stream):
+        check(_lib.load().cvk_grad_norm(grad_ptr, self.n, self.table.data_ptr(), self.nseg, self.blocks, norm_type, max_norm,
+                                        self.partials.data_ptr(), rec.data_ptr(), stream), "cvk_grad_norm")
+
+    def scale(self, grad_ptr, rec, stream):
+        check(_lib.load().cvk_grad_scale(grad_ptr, self.n, self.table.data_ptr(), self.nseg, self.blocks, rec.data_ptr(), stream),
+              "cvk_grad_scale")
+
+
+_PLANS = {}             # clip_grad_norm_: (device, buffer floats, segments) -> _NormPlan
+_PLANS_MAX = 16
+
+
+def _dense(g):
+    return g.is_contiguous() or (g.dim() == 4 and g.permute(0, 2, 3, 1).is_contiguous())
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False):
+    """torch.nn.utils.clip_grad_norm_ (same signature, same return value: the total norm as a 0-dim fp32 device tensor; `.grad`s scaled in
+    place by min(1, max_norm / (total_norm + 1e-6))) for a network, an iterable of parameters or one tensor.  Parameters without a gradient
+    are skipped.  When the gradients are dense fp32 views of ONE device buffer — what backward of a UNet / SegNet of this package leaves:
+    the executor's flat gradient buffer — it is three launches and no host synchronisation (unless error_if_nonfinite): the fp64 reduction
+    over the exact segments, its finish, the in-place scale (cvk_grad_norm, cvk_grad_scale).  Any other gradient set goes to torch's own
+    function.  Gradients are fp32 in the bf16 and split-operand modes too, so nothing differs there."""
+    if isinstance(parameters, torch.nn.Module):
+        parameters = parameters.parameters()
+    elif isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = [p for p in parameters if p.grad is not None]
+    mx, nt = _check_clip_options(max_norm, norm_type, "clip_grad_norm_")
+    if mx is None:
+        raise ValueError("clip_grad_norm_: max_norm is required")
+    grads = [p.grad for p in params]
+    flat = bool(grads) and all(g.is_cuda and g.dtype == torch.float32 and _dense(g) for g in grads)
+    if flat:
+        st = grads[0].untyped_storage()
+        flat = all(g.untyped_storage().data_ptr() == st.data_ptr() for g in grads) and len({id(g) for g in grads}) == len(grads)
+    if not flat:
+        return torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite)
+    dev = grads[0].device
+    n = st.nbytes() // 4
+    segs = tuple(norm_segments((g.storage_offset(), g.numel()) for g in grads))
+    key = (dev, n, segs)
+    plan = _PLANS.get(key)
+    if plan is None:
+        if len(_PLANS) >= _PLANS_MAX:
+            _PLANS.clear()
+        plan = _PLANS[key] = _NormPlan(list(segs), n, dev)
+    rec = torch.empty(2, device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    plan.norm(st.data_ptr(), nt, mx, rec, stream)
+    if error_if_nonfinite and not bool(torch.isfinite(rec[0])):
+        raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be clipped. "
+                           "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    plan.scale(st.data_ptr(), rec, stream)
+    return rec[0]
+
+
 class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, groups=None):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, groups=None, max_grad_norm=None, norm_type=2.0):
+        self.max_grad_norm, self.norm_type = _check_clip_options(max_grad_norm, norm_type, "FlatAdamW")
         params = _block_params(net)                       # execution order == the executor's flat parameter list
         if len(params) != len(list(net.parameters())):
             raise ValueError("FlatAdamW needs a network made only of conv+BN blocks (UNet / SegNet)")
@@ -66,6 +183,29 @@ class FlatAdamW(torch.optim.Optimizer):
         self._step = 0                                    # step() calls (the counter the captured step and schedulers see)
         self._steps = [0] * len(params)                   # per parameter, as torch.optim.AdamW's state[p]["step"]
         self._tables = {}                                 # range table (host tuple) -> (device table, workgroups)
+        self._clip_rec = torch.zeros(2, device=dev, dtype=torch.float32)    # {total_norm, clip_coef} of the last clipped step
+        self._norm_plans = {}                             # segment table (host tuple) -> _NormPlan
+
+    @property
+    def grad_norm(self):
+        """0-dim view of the device record: the gradient norm of the last clipped step (no host sync)."""
+        return self._clip_rec[0]
+
+    @property
+    def clip_coef(self):
+        """0-dim view of the device record: the factor the last clipped step applied to every gradient element."""
+        return self._clip_rec[1]
+
+    def _norm_plan(self, idx):
+        """The norm's segment table over the parameters `idx`: exact (offset, numel) per parameter, never the padded AdamW ranges."""
+        segs = tuple(norm_segments((self._offs[i], self._plist[i].numel()) for i in idx))
+        plan = self._norm_plans.get(segs)
+        if plan is None:
+            plan = self._norm_plans[segs] = _NormPlan(list(segs), self._flat.numel(), self._flat.device)
+        return plan
+
+    def _clip_options(self):
+        return _check_clip_options(self.max_grad_norm, self.norm_type, "FlatAdamW")
 
     def _group_of(self):
         ids = {}
@@ -157,7 +297,7 @@ class FlatAdamW(torch.optim.Optimizer):
     def state_dict(self):
         sd = super().state_dict()           # param_groups: every group's options and its members
         sd["flat_adamw"] = {"step": self._step, "steps": list(self._steps), "exp_avg": self._m.clone(), "exp_avg_sq": self._v.clone(),
-                            "offsets": list(self._offs)}
+                            "offsets": list(self._offs), "max_grad_norm": self.max_grad_norm, "norm_type": self.norm_type}
         return sd
 
     def load_state_dict(self, state_dict):
@@ -173,6 +313,9 @@ class FlatAdamW(torch.optim.Optimizer):
             if len(self._steps) != len(self._plist):
                 raise ValueError("FlatAdamW.load_state_dict: the saved step counts belong to a different network layout")
             self._m.copy_(extra["exp_avg"]); self._v.copy_(extra["exp_avg_sq"])
+            if "max_grad_norm" in extra:    # absent in a state dict saved before clipping existed: the constructor's options stay
+                self.max_grad_norm, self.norm_type = _check_clip_options(extra["max_grad_norm"], extra.get("norm_type", 2.0),
+                                                                         "FlatAdamW.load_state_dict")
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -181,6 +324,7 @@ class FlatAdamW(torch.optim.Optimizer):
         idx = self._trainable()
         if not idx:                   # torch.optim.AdamW: nothing has a gradient, nothing changes
             return loss
+        max_norm, norm_type = self._clip_options()
         self._step += 1
         for i in idx:
             self._steps[i] += 1
@@ -188,6 +332,8 @@ class FlatAdamW(torch.optim.Optimizer):
         lib = _lib.load()
         stream = torch.cuda.current_stream(self._flat.device).cuda_stream
         recs, ranges = self._ranges(idx)
+        if max_norm is not None:      # one norm over everything that takes this step, all groups together: reduction + finish
+            self._norm_plan(idx).norm(grad.data_ptr(), norm_type, max_norm, self._clip_rec, stream)
         # the records travel as kernel arguments: one launch per CVK_ADAMW_ARG_RECORDS distinct (group, step count) pairs
         for c0 in range(0, len(recs), _lib.ADAMW_ARG_RECORDS):
             crecs = recs[c0:c0 + _lib.ADAMW_ARG_RECORDS]
@@ -195,6 +341,11 @@ class FlatAdamW(torch.optim.Optimizer):
             hyper = (_lib.AdamwHyper * len(crecs))()
             self._fill(crecs, hyper)
             table, nb = self._table(cranges, len(crecs))
+            if max_norm is not None:
+                check(lib.cvk_adamw_step_ranges_clip(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                                                     self._flat.numel(), table.data_ptr(), len(cranges), nb, ctypes.addressof(hyper),
+                                                     len(crecs), self._clip_rec.data_ptr(), stream), "cvk_adamw_step_ranges_clip")
+                continue
             check(lib.cvk_adamw_step_ranges(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), self._flat.numel(),
                                             table.data_ptr(), len(cranges), nb, ctypes.addressof(hyper), len(crecs), stream),
                   "cvk_adamw_step_ranges")
