@@ -47,13 +47,21 @@ def main():
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                     help="clip the global gradient 2-norm to X (cvk.clip_grad_norm_; with --graphed: FlatAdamW(max_grad_norm=X), inside the "
                     "captured step); prints the epoch's largest norm and the share of clipped steps")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="gradient accumulation: one optimizer update per K batches on their mean gradient (cvk.GradAccumulator; with --graphed "
+                    "the whole window of K batches is one captured graph).  --iters must be a multiple of K")
     a = ap.parse_args()
+    K = a.accumulate
+    if K < 1 or a.iters % K:
+        ap.error("--accumulate K needs K >= 1 and --iters a multiple of K")
+    updates = a.iters // K
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     random.seed(a.seed)
     net = cvk.get_model(a.net, 3, 12).to(dev)
     opt = cvk.FlatAdamW(net, lr=a.lr, max_grad_norm=a.clip_grad_norm) if a.graphed else torch.optim.AdamW(net.parameters(), lr=a.lr)
-    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=a.iters, epochs=a.epochs)
+    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=updates, epochs=a.epochs)
+    accum = cvk.GradAccumulator(net, steps=K) if K > 1 else None
     weight = None
     if a.class_weights != "none":
         weight = cvk.class_weights((m for _, m in synthetic_camvid(a.iters, a.b, 1)), 12, method=a.class_weights, device=dev)
@@ -64,15 +72,26 @@ def main():
         net.train()
         t0 = time.time()
         norms = []                                                          # device scalars: read once per epoch
+        window = []
         for images, masks in cvk.DevicePrefetcher(synthetic_camvid(a.iters, a.b, epoch), transforms=train_tf):
             if a.graphed:
+                if accum is not None:                                       # a window of K batches: [K, N, 3, H, W], [K, N, H, W]
+                    window.append((images, masks))
+                    if len(window) < K:
+                        continue
+                    images, masks = torch.stack([w[0] for w in window]), torch.stack([w[1] for w in window])
+                    window = []
                 if step is None:
-                    step = cvk.GraphedStep(net, loss_fn, images, masks, optimizer=opt, scheduler=sched, log_capacity=a.iters)
+                    step = cvk.GraphedStep(net, loss_fn, images, masks, optimizer=opt, scheduler=sched, log_capacity=updates,
+                                           accumulator=accum)
                 loss = step.replay(images, masks)
                 continue
-            opt.zero_grad()
+            if accum is None or accum.micro_step == 0:
+                opt.zero_grad()
             loss = loss_fn(net(images), masks)
             loss.backward()
+            if accum is not None and not accum.ready:                       # the window is still open: .grad is None, nothing to step
+                continue
             if a.clip_grad_norm is not None:
                 norms.append(cvk.clip_grad_norm_(net, a.clip_grad_norm))    # reduction, finish, in-place scale: no host sync
             opt.step(); sched.step()

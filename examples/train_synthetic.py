@@ -40,8 +40,15 @@ def main():
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                     help="clip the global gradient 2-norm to X: fused into the step with --flat-adamw / --graphed (FlatAdamW(max_grad_norm=X)), "
                     "cvk.clip_grad_norm_ before torch's AdamW otherwise; prints the epoch's largest norm and the share of clipped steps")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="gradient accumulation: one optimizer update per K batches on their mean gradient (cvk.GradAccumulator; with --graphed "
+                    "the whole window of K batches is one captured graph).  --iters must be a multiple of K")
     a = ap.parse_args()
     a.flat_adamw = a.flat_adamw or a.graphed
+    K = a.accumulate
+    if K < 1 or a.iters % K:
+        ap.error("--accumulate K needs K >= 1 and --iters a multiple of K")
+    updates = a.iters // K
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -57,7 +64,10 @@ def main():
     model = cvk.ddp.DataParallel(net) if world > 1 else net
     opt = cvk.FlatAdamW(net, lr=a.lr, weight_decay=a.wd, max_grad_norm=a.clip_grad_norm) if a.flat_adamw else \
         torch.optim.AdamW(net.parameters(), lr=a.lr, weight_decay=a.wd)     # train.py:100
-    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=a.iters, epochs=a.epochs)  # :103-104
+    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=updates, epochs=a.epochs)  # :103-104
+    if K > 1 and a.graphed and world > 1:
+        ap.error("--accumulate with --graphed runs on one GPU (a window with captured collectives is not supported)")
+    accum = cvk.GradAccumulator(model, steps=K) if K > 1 else None           # folds the flat gradient buffers of K backward passes
     g = torch.Generator().manual_seed(1234 + rank)
     # a fixed synthetic "dataset": uint8 HWC frames like cv2 delivers + 12-class masks; smooth blobs so it is learnable
     base = torch.rand(a.iters, a.b, 45, 60, generator=g)
@@ -69,21 +79,31 @@ def main():
         net.train()
         t0 = time.time()
         norms = []                                                          # device scalars: read once per epoch
+        window = []
         for it in range(a.iters):
             m = masks[it].to(dev)
             frames = ((m.unsqueeze(-1) * torch.tensor([20, 15, 10], device=dev)) % 256 +
                       torch.randint(0, 30, (a.b, 360, 480, 3), device=dev)).clamp(0, 255).to(torch.uint8)
             images = cvk.preprocess_uint8(frames)                           # transforms.ToTensor + Normalize on device
             if a.graphed:
+                if accum is not None:                                       # a window of K batches: [K, N, 3, H, W], [K, N, H, W]
+                    window.append((images, m))
+                    if len(window) < K:
+                        continue
+                    images, m = torch.stack([w[0] for w in window]), torch.stack([w[1] for w in window])
+                    window = []
                 if step is None:                                            # capture once, on the first batch of the geometry
                     step = cvk.GraphedStep(net, loss_fn, images, m, allow_grad_sync=world > 1, optimizer=opt, scheduler=sched,
-                                           log_capacity=a.iters)
+                                           log_capacity=updates, accumulator=accum)
                 loss = step.replay(images, m)                               # train.py:124-134 + the log line, one launch
                 continue
-            opt.zero_grad()                                                 # train.py:124
+            if accum is None or accum.micro_step == 0:
+                opt.zero_grad()                                             # train.py:124
             preds = model(images)                                           # :128
             loss = loss_fn(preds, m)                                        # :130
             loss.backward()                                                 # :131
+            if accum is not None and not accum.ready:                       # the window is still open: .grad is None, nothing to step
+                continue
             if a.clip_grad_norm is not None and not a.flat_adamw:
                 norms.append(cvk.clip_grad_norm_(net, a.clip_grad_norm))    # reduction, finish, in-place scale: no host sync
             opt.step(); sched.step()                                        # :133-134
@@ -98,7 +118,7 @@ def main():
             for i, (l, lr, beta, gw, gb) in enumerate(rows[:, :5]):         # train.py:135-143 + utils.visulaize_lastlayer
                 print(("Training Epoch:{epoch} [{trained_samples}/{total_samples}] Lr:{lr:0.6f} Loss:{loss:0.4f} Beta1:{beta:0.4f} "
                        "grad_norm2_weights:{gw:0.4e} grad_norm2_bias:{gb:0.4e}").format(
-                    epoch=epoch, trained_samples=(dropped + i + 1) * a.b, total_samples=a.iters * a.b, lr=lr, loss=l, beta=beta,
+                    epoch=epoch, trained_samples=(dropped + i + 1) * a.b * K, total_samples=a.iters * a.b, lr=lr, loss=l, beta=beta,
                     gw=gw, gb=gb))
         if rank == 0:
             print(f"epoch {epoch}: loss {loss.item():.4f}  lr {sched.get_last_lr()[0]:.6f}  "

@@ -598,6 +598,20 @@ int cvk_adamw_step_ranges_clip_dev(float* param, const float* grad, float* exp_a
 int cvk_step_log_norm(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb,
                       const float* record, float* ring, int capacity, int64_t* counter, void* stream);
 
+/* ---- gradient accumulation over micro-batches (GradAccumulator) -------------------------------------------------------------------
+ * One streaming launch over a planned segment table (cvk_grad_norm_plan: the same table type and the same workgroup walk as the norm)
+ * that folds one flat gradient buffer into another.  dst and src are two DEVICE buffers of n floats with the same layout; the table's
+ * offsets apply to both.  Elements outside the table (alignment padding, frozen parameters) are neither read nor written.
+ *   mode 0: dst = src                    (first micro-step of a window: initialises the accumulator, which never needs zeroing)
+ *   mode 1: dst = dst + src              (middle micro-steps)
+ *   mode 2: dst = (dst + src) * scale    (closing micro-step: dst is the fresh gradient buffer of the pass, src the accumulator)
+ * Every element is one correctly rounded fp32 add and, in mode 2, one separately rounded fp32 multiply, in that order; no atomics:
+ * the result is bitwise the same expression evaluated in IEEE fp32, run to run, eager or captured.  16-byte loads and stores in the
+ * body of a segment, scalar heads and tails.  A table over a sub-range of the buffer (one data-parallel bucket) is planned like any
+ * other table.  scale must be finite, both bases 16-byte aligned, dst != src; mode outside 0..2 is refused. */
+int cvk_grad_accumulate(float* dst, const float* src, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks,
+                        int mode, float scale, void* stream);
+
 
 /* ================================================================================================================
  * bf16-storage path (BASELINE.json configs[3] "bf16 + MFMA im2col path"; set_conv_precision(net, "bf16")).

@@ -805,6 +805,60 @@ __global__ __launch_bounds__(NORM_THREADS) void k_grad_scale(float* __restrict__
     }
 }
 
+// ---- gradient accumulation over micro-batches (cvk_grad_accumulate) ----------------------------------------------------------------
+// One element of the fold.  MODE 0: dst = src; 1: dst = dst + src; 2: dst = (dst + src) * scale.  One correctly rounded fp32 add, then
+// (mode 2) one separately rounded multiply: an add feeding a multiply has no fused form, and the file is built without fast-math, so
+// the result is bitwise `(d + s) * scale` of IEEE fp32 whatever the vector width.
+template <int MODE>
+__device__ __forceinline__ float acc_one(float d, float s, float scale) {
+    if (MODE == 0) return s;
+    if (MODE == 1) return d + s;
+    return (d + s) * scale;
+}
+
+// dst and src share the table (same offsets in both buffers) and both bases are 16-byte aligned (checked by the entry point), so the
+// head / vector / tail split of a segment is the same on both sides.  Elements outside the table are neither read nor written.
+template <int MODE>
+__global__ __launch_bounds__(NORM_THREADS) void k_grad_accumulate(float* __restrict__ dst, const float* __restrict__ src, int64_t n,
+                                                                  const cvk_norm_segment* __restrict__ st, int ns, float scale) {
+    int64_t off, len;
+    int rank, nb;
+    if (!norm_segment_of(st, ns, n, &off, &len, &rank, &nb)) return;
+    const int64_t head = norm_head(dst, off, len);
+    const int64_t nvec = (len - head) >> 2;
+    f32x4* __restrict__ dv = reinterpret_cast<f32x4*>(dst + off + head);
+    const f32x4* __restrict__ sv = reinterpret_cast<const f32x4*>(src + off + head);
+    const int64_t tid = (int64_t)rank * NORM_THREADS + threadIdx.x, stride = (int64_t)nb * NORM_THREADS;
+    int64_t i = tid;
+    for (; i + (NORM_UNROLL - 1) * stride < nvec; i += NORM_UNROLL * stride) {
+        f32x4 s[NORM_UNROLL], d[NORM_UNROLL];
+#pragma unroll
+        for (int u = 0; u < NORM_UNROLL; ++u) {
+            s[u] = sv[i + u * stride];
+            if (MODE != 0) d[u] = dv[i + u * stride];
+        }
+#pragma unroll
+        for (int u = 0; u < NORM_UNROLL; ++u) {
+            f32x4 r;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k] = acc_one<MODE>(MODE != 0 ? d[u][k] : 0.f, s[u][k], scale);
+            dv[i + u * stride] = r;
+        }
+    }
+    for (; i < nvec; i += stride) {
+        const f32x4 s = sv[i];
+        f32x4 r;
+        if (MODE != 0) r = dv[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = acc_one<MODE>(MODE != 0 ? r[k] : 0.f, s[k], scale);
+        dv[i] = r;
+    }
+    if (tid == 0) {         // the at most 3 + 3 elements around the vectors: the segment's first thread
+        for (int64_t j = 0; j < head; ++j) dst[off + j] = acc_one<MODE>(MODE != 0 ? dst[off + j] : 0.f, src[off + j], scale);
+        for (int64_t j = head + 4 * nvec; j < len; ++j) dst[off + j] = acc_one<MODE>(MODE != 0 ? dst[off + j] : 0.f, src[off + j], scale);
+    }
+}
+
 // uint8 HWC (cv2 BGR order kept) -> float32 NHWC, 4 channels per pixel (3 valid + zero pad): (v/255 - mean[c]) / std[c]
 // = reference transforms.ToTensor + Normalize (transforms.py:485-538) with conf/settings.py:8-9 MEAN/STD passed in.
 __global__ void k_preprocess_u8(const uint8_t* __restrict__ src, float* __restrict__ dst, long npix, float m0, float m1,
@@ -1266,6 +1320,26 @@ extern "C" int cvk_grad_scale(float* grad, int64_t n, const cvk_norm_segment* se
     CVK_CHECK_ARG((((uintptr_t)grad) & 3u) == 0, "cvk_grad_scale: misaligned buffer");
     hipLaunchKernelGGL(k_grad_scale, dim3(nblocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, grad, n, segments, nsegments, record);
     CVK_LAUNCH_RETURN("cvk_grad_scale");
+}
+
+extern "C" int cvk_grad_accumulate(float* dst, const float* src, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks,
+                                   int mode, float scale, void* stream) {
+    CVK_CHECK_ARG(dst && src && segments, "cvk_grad_accumulate: null pointer");
+    CVK_CHECK_ARG(dst != src, "cvk_grad_accumulate: dst and src are the same buffer");
+    CVK_CHECK_ARG(n > 0 && nsegments > 0 && nblocks >= nsegments, "cvk_grad_accumulate: empty table or buffer (%d segments, %d workgroups)",
+                  nsegments, nblocks);
+    CVK_CHECK_ARG(mode >= 0 && mode <= 2, "cvk_grad_accumulate: mode %d (0: copy, 1: add, 2: add and scale)", mode);
+    CVK_CHECK_ARG(scale - scale == 0.f, "cvk_grad_accumulate: scale %g is not finite", (double)scale);
+    CVK_CHECK_ARG((((uintptr_t)dst) & 15u) == 0 && (((uintptr_t)src) & 15u) == 0,
+                  "cvk_grad_accumulate: misaligned buffer (both bases must be 16-byte aligned)");
+    const dim3 grid(nblocks), block(NORM_THREADS);
+    if (mode == 0)
+        hipLaunchKernelGGL(k_grad_accumulate<0>, grid, block, 0, (hipStream_t)stream, dst, src, n, segments, nsegments, scale);
+    else if (mode == 1)
+        hipLaunchKernelGGL(k_grad_accumulate<1>, grid, block, 0, (hipStream_t)stream, dst, src, n, segments, nsegments, scale);
+    else
+        hipLaunchKernelGGL(k_grad_accumulate<2>, grid, block, 0, (hipStream_t)stream, dst, src, n, segments, nsegments, scale);
+    CVK_LAUNCH_RETURN("cvk_grad_accumulate");
 }
 
 extern "C" int cvk_adamw_step_ranges_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,

@@ -15,6 +15,7 @@ xGMI is point-to-point (7 links x ~153 GB/s per GPU): a ring all-reduce of the f
 per-link bound at ~1.6 ms, so a handful of ~25-50 MB buckets keeps each collective bandwidth-bound rather than
 latency-bound while still starting early.
 """
+import contextlib
 import os
 
 import torch
@@ -143,6 +144,9 @@ class _SyncCall:
         done_upto = self.ranges[self.layers_done - 1][1]
         while self.next_bucket < len(self.buckets) and self.buckets[self.next_bucket][1] <= done_upto:
             lo, hi, _ = self.buckets[self.next_bucket]
+            fold = getattr(st, "fold", None)        # engine.RunState always has it; the host-side tests drive this class with bare states
+            if fold is not None:        # closing micro-step of an accumulation window: the bucket leaves as the window's mean (or sum)
+                fold.bucket(st, lo, hi)
             self.owner._issue(self, st.gflat[lo:hi])
             self.launched.append((lo, hi))
             self.next_bucket += 1
@@ -178,6 +182,7 @@ class GradSync:
         self.world = dist.get_world_size(process_group)
         self._native_avg = dist.get_backend(process_group) == "nccl"
         self.launched = []       # (begin, end) of the buckets issued during the last finished backward (introspection/tests)
+        self.enabled = True      # False inside DataParallel.no_sync(): engine.Runner.backward then creates no _SyncCall
         self.wait_events = None  # a list while bench.py collects (start, end) HIP events around finish()'s stream waits
 
     def begin(self, st, plan=None):
@@ -227,3 +232,17 @@ class DataParallel(nn.Module):
 
     def forward(self, x):
         return self.module(x)
+
+    @contextlib.contextmanager
+    def no_sync(self):
+        """torch.nn.parallel.DistributedDataParallel.no_sync's contract: a backward pass inside the context issues no collective (and no
+        division); `sync.launched` is then empty.  The gradients it leaves are this rank's own.  Unlike torch's wrapper, the exchange of a
+        later backward covers that pass's fresh flat buffer only, not what autograd accumulated into `.grad` before it: to train on
+        several micro-batches per update use `GradAccumulator`, which folds the window into the fresh buffer before each bucket leaves
+        and skips the exchange on the other micro-steps through this same switch."""
+        prev = self.sync.enabled
+        self.sync.enabled = False
+        try:
+            yield self
+        finally:
+            self.sync.enabled = prev

@@ -97,6 +97,7 @@ class RunState:
                                     # that write it (opt-in fp16 split-operand layers scale by it: Runner.plan_amax)
         self.amax_spare = []        # zeroed amax blocks for the backward pass (|dy| maxima)
         self.scratch = []           # dgamma / dbeta temporaries of blocks with frozen BatchNorm parameters (ConvBnRelu._grad_targets)
+        self.fold = None            # the gradient-accumulation fold of this backward pass (accumulate.GradAccumulator), or None
 
 
 def _empty(n, dev, dtype=_F32):
@@ -1369,6 +1370,7 @@ class Runner:
         self._dp_wgs = None
         self._collectives_in_flight = False     # a gradient bucket's all-reduce has been issued and backward is still running
         self.grad_sync = None       # set by ddp.DataParallel
+        self.accumulator = None     # set by accumulate.GradAccumulator: folds the flat gradient buffers of a window of micro-batches
         self.wino = WINO_DEFAULT
         self.wino4 = WINO4_DEFAULT
         self.wino4f = WINO4F_DEFAULT
@@ -1548,6 +1550,18 @@ class Runner:
             st.sync.layer_done(st, slot)
             self._collectives_in_flight = st.sync.in_flight()
 
+    def begin_sync(self, st, plan, fold=None):
+        """The gradient synchroniser's per-call state for this backward pass, or None: no synchroniser, one switched off
+        (ddp.DataParallel.no_sync), or a micro-step that does not close its accumulation window.  A skipped pass issues no collective and
+        leaves `grad_sync.launched` empty."""
+        gs = self.grad_sync
+        if gs is None:
+            return None
+        if not gs.enabled or (fold is not None and not fold.closing):
+            gs.launched = []
+            return None
+        return gs.begin(st, plan)
+
     # ---- forward / backward -------------------------------------------------------------------------------------
     def plan_amax(self, plan, st):
         """fp16 split-operand mode (w2d_split = 2): the transforms of a split layer scale by the EXACT largest magnitude of the tensor they
@@ -1675,7 +1689,12 @@ class Runner:
         # second pass through the same network inside one graph, torch.autograd.grad results the caller keeps, manual
         # accumulation across zero_grad(set_to_none=True)): no later backward ever writes into memory handed out here.
         st.gflat = torch.empty(total, device=dev, dtype=_F32)
-        st.sync = self.grad_sync.begin(st, plan) if self.grad_sync is not None else None
+        # Gradient accumulation (accumulate.GradAccumulator, steps > 1): the micro-steps before the last of a window fold this pass's buffer
+        # into the accumulator's own and hand out nothing; the last one folds the accumulator into this pass's fresh buffer, bucket by
+        # bucket before each leaves for the all-reduce (ddp._SyncCall.layer_done) or in one launch at the end.  The accumulator's buffer is
+        # never handed to autograd, so the promise above holds.
+        fold = st.fold = self.accumulator.open_pass(st, plan, total) if self.accumulator is not None else None
+        st.sync = self.begin_sync(st, plan, fold)
         self._collectives_in_flight = False
         ob = plan.output.buf
         gp = gout.permute(0, 2, 3, 1)
@@ -1694,6 +1713,8 @@ class Runner:
         _CUR_OP[0] = None
         self.flush_colsums(st)
         self.flush_wreduces(st)
+        if fold is not None and st.sync is None:        # with a synchroniser every bucket was folded before it left
+            fold.whole(st)
         dx = None
         if plan.input_needs_grad:
             gi = st.grad[plan.input.id]
@@ -1701,9 +1722,10 @@ class Runner:
             if plan.bf16:                   # the stem's data-grad is stored as bf16 like every other dX; x.grad is fp32 like x
                 dx = dx.float()
         grads = []
+        hand_out = fold is None or fold.closing
         for i, p in enumerate(params):
             op = plan.convs[i // 4]
-            if not (op.w_req, op.b_req, op.g_req, op.be_req)[i % 4]:
+            if not hand_out or not (op.w_req, op.b_req, op.g_req, op.be_req)[i % 4]:
                 grads.append(None)          # frozen when the plan was recorded: its segment was never written
                 continue
             n = p.numel()
@@ -1718,6 +1740,11 @@ class Runner:
             st.sync.finish(st)
         self._collectives_in_flight = False
         st.act.clear(); st.saved.clear(); st.grad.clear(); st.scratch.clear()
+        if fold is not None:
+            fold.done()
+            st.fold = None
+            if not hand_out:        # nothing views this pass's buffer: it goes back to the allocator now
+                st.gflat = None
         return dx, grads
 
 

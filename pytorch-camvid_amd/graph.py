@@ -35,6 +35,12 @@ they are when the GraphedStep is built; replay() refuses to run after any of tha
         for xb, tb in loader:
             step.replay(xb, tb)                # one graph launch per iteration, no host sync
         rows, dropped = step.log()             # one D2H copy per epoch
+
+Gradient accumulation: with `accumulator=` (the GradAccumulator attached to the network) the graph holds a whole window.  `x` and `t`
+carry a leading window axis (`x: [steps, N, 3, H, W]`, `t: [steps, N, H, W]`); the capture runs the `steps` forward / loss / backward
+passes back to back (each with its cvk_grad_accumulate launch), then the tail above once.  `step.loss` and the log row's loss column
+are `torch.stack(micro_losses).mean()`, computed on the device inside the graph; the log gets one row per update and the scheduler
+steps once per replay.  The accumulator's identity, `steps` and `mean` are baked in.  Not together with allow_grad_sync=True.
 """
 import torch
 
@@ -59,7 +65,7 @@ def last_layer_params(net):
 
 
 class GraphedStep:
-    def __init__(self, net, lossf, x, t, warmup=2, allow_grad_sync=False, *, optimizer=None, scheduler=None, log_capacity=0):
+    def __init__(self, net, lossf, x, t, warmup=2, allow_grad_sync=False, *, optimizer=None, scheduler=None, log_capacity=0, accumulator=None):
         from .modules import runner_of
         from .optim import FlatAdamW
         if optimizer is not None and not isinstance(optimizer, FlatAdamW):
@@ -79,6 +85,21 @@ class GraphedStep:
                 raise ValueError("GraphedStep: the optimizer was built for another network")
             optimizer._check_homes()
         R = runner_of(net)
+        if accumulator is not None:
+            if allow_grad_sync:
+                raise NotImplementedError("GraphedStep: accumulator= together with allow_grad_sync=True is not supported (a window with "
+                                          "captured collectives); run data-parallel accumulation in eager mode")
+            if R.accumulator is not accumulator:
+                raise ValueError("GraphedStep: accumulator= must be the GradAccumulator attached to this network")
+            if accumulator.micro_step:
+                raise RuntimeError("GraphedStep: the accumulator is in the middle of a window; reset() it or finish the window first")
+            if x.dim() != 5 or t.dim() != 4 or x.shape[0] != accumulator.steps or t.shape[0] != accumulator.steps:
+                raise ValueError(f"GraphedStep: with accumulator= the batch carries a leading window axis: x [steps, N, C, H, W], "
+                                 f"t [steps, N, H, W] with steps = {accumulator.steps}; got {tuple(x.shape)}, {tuple(t.shape)}")
+        elif R.accumulator is not None and R.accumulator.steps > 1:
+            raise RuntimeError("GraphedStep: the network accumulates gradients over micro-batches (GradAccumulator); pass accumulator= to "
+                               "capture a whole window")
+        self.accumulator = accumulator
         if R.grad_sync is not None:
             if not allow_grad_sync:
                 raise RuntimeError("GraphedStep: the network synchronises gradients (ddp.DataParallel); pass allow_grad_sync=True to "
@@ -122,7 +143,7 @@ class GraphedStep:
         with torch.cuda.stream(side):               # warm-up off the capture: plans, workspace, allocator pools
             for _ in range(max(1, warmup)):
                 self._zero()
-                lossf(net(self.x), self.t).backward()
+                self._passes()
         cur.wait_stream(side)
         torch.cuda.synchronize(x.device)
         self._zero()
@@ -140,14 +161,27 @@ class GraphedStep:
             import time
             time.sleep(0.35)
         with torch.cuda.graph(self.graph, capture_error_mode=mode):
-            self.loss = lossf(net(self.x), self.t)
-            self.loss.backward()
+            self.loss = self._passes()
             if optimizer is not None or log_capacity:
                 self._capture_tail(x.device)
         # every tensor a replay writes must stay alive as long as the graph: the gradients (views of the flat buffer the
         # capture allocated) and the runner's workspace (a later, larger eager call would otherwise release it)
         self.grads = [p.grad for p in self.params]
         self._keep = R._ws
+
+    def _passes(self):
+        """Forward, loss and backward of one iteration; returns the loss.  With an accumulator: the window's `steps` passes back to back and
+        the mean of the micro-batch losses (device, fp32)."""
+        if self.accumulator is None:
+            loss = self.lossf(self.net(self.x), self.t)
+            loss.backward()
+            return loss
+        losses = []
+        for k in range(self.accumulator.steps):
+            loss = self.lossf(self.net(self.x[k]), self.t[k])
+            loss.backward()
+            losses.append(loss.detach())
+        return torch.stack(losses).mean()
 
     def _capture_tail(self, device):
         """Inside the capture, after backward (and after the stream's waits for the all-reduces): the AdamW step, then the log row."""
@@ -233,8 +267,9 @@ class GraphedStep:
         from .modules import plan_key_blocks
         R = self._runner
         # plan_key_blocks: every block's identity, BatchNorm mode and requires-grad pattern (what the captured plan and range table fixed)
+        acc = R.accumulator
         return (id(R.grad_sync), bool(self.net.training), bool(R.bf16), R.persistent_wgs()) + R.kernel_config() + self._optimizer_signature() \
-            + (plan_key_blocks(self.net),)
+            + (plan_key_blocks(self.net),) + ((id(acc), acc.steps, acc.mean) if acc is not None else (None, 1, True))
 
     def _optimizer_signature(self):
         """The captured AdamW step writes the optimizer's flat buffers through raw pointers: the same optimizer, one parameter group, the
@@ -252,10 +287,15 @@ class GraphedStep:
         if self._signature() != self._sig:
             raise RuntimeError("GraphedStep.replay: the network changed since the capture (train/eval mode of the network or of a "
                                "block's BatchNorm, a parameter's requires_grad, a swapped block, conv precision, a kernel "
-                               "knob, it was wrapped in / unwrapped from ddp.DataParallel, or the captured FlatAdamW was rebuilt, re-homed, "
+                               "knob, it was wrapped in / unwrapped from ddp.DataParallel, a GradAccumulator was attached, detached or given other "
+                               "steps / mean, or the captured FlatAdamW was rebuilt, re-homed, "
                                "regrouped or given another max_grad_norm / norm_type): the "
                                "captured graph would silently run the "
                                "old configuration — build a new GraphedStep")
+        if self.accumulator is not None and self.accumulator.micro_step:
+            raise RuntimeError("GraphedStep.replay: the accumulator is in the middle of an eager window (micro-step "
+                               f"{self.accumulator.micro_step} of {self.accumulator.steps}); the captured window starts at micro-step 0 — "
+                               "finish the window or reset() the accumulator first")
         if x is not None:
             self.x.copy_(x, non_blocking=True)
         if t is not None:
