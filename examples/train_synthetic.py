@@ -35,6 +35,10 @@ def main():
     ap.add_argument("--class-weights", default="none", choices=["none", "median_frequency", "enet"],
                     help="class-weighted loss, weights from the training masks (cvk.class_weights)")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
+    ap.add_argument("--loss", default="ce", choices=["ce", "focal", "dice", "ce+dice"],
+                    help="ce: cvk.CrossEntropyLoss (the reference's loss); the others: cvk.SegmentationLoss, one fused pass")
+    ap.add_argument("--focal-gamma", type=float, default=2.0, help="--loss focal: the focusing exponent")
+    ap.add_argument("--dice-weight", type=float, default=0.5, help="--loss ce+dice: the Dice term's coefficient")
     ap.add_argument("--split-operands", type=int, default=0, choices=[0, 2, 3],
                     help="opt-in for fp32: matrix products on the 16-bit matrix pipe with split fp32 operands (cvk.set_split_operands; 2 = fp16 x 2)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
@@ -73,7 +77,13 @@ def main():
     base = torch.rand(a.iters, a.b, 45, 60, generator=g)
     masks = torch.nn.functional.interpolate((base * 12).floor().clamp(0, 11), size=(360, 480), mode="nearest").long()
     weight = None if a.class_weights == "none" else cvk.class_weights(masks, 12, method=a.class_weights, device=dev)
-    loss_fn = cvk.CrossEntropyLoss(weight=weight, label_smoothing=a.label_smoothing)   # train.py:105
+    if a.loss == "ce":
+        loss_fn = cvk.CrossEntropyLoss(weight=weight, label_smoothing=a.label_smoothing)   # train.py:105
+    else:
+        if a.label_smoothing:
+            raise SystemExit("--label-smoothing belongs to --loss ce")
+        ce, dice = {"focal": (1.0, 0.0), "dice": (0.0, 1.0), "ce+dice": (1.0, a.dice_weight)}[a.loss]
+        loss_fn = cvk.SegmentationLoss(ce, dice, focal_gamma=a.focal_gamma if a.loss == "focal" else 0.0, weight=weight)
     step = None
     for epoch in range(1, a.epochs + 1):
         net.train()

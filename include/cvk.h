@@ -463,6 +463,35 @@ int cvk_softmax_ce_bwd_ex(const float* logits, int ld, const int64_t* target, co
                           int reduction, const float* loss4, const float* grad_out, float scale, float* dlogits, int ld_d,
                           int M, int C, int ignore_index, void* stream);
 
+/* ---- fused focal + soft-Dice segmentation loss, L = ce F + dice D ------------------------------------------------------------
+ * logits: dense NHWC rows [M][ld] (ld >= C, 0 < C <= 128), target int64 [M], weight float [C] nullable (all ones): all DEVICE.
+ * ce, dice >= 0 and not both 0, focal_gamma >= 0, dice_smooth s >= 0 (all finite); dice_average CVK_DICE_*.  With p = softmax(x),
+ * t = target and every sum over the valid pixels (t != ignore_index) of the call:
+ *   F = sum w[t] (1 - p[t])^gamma (lse - x[t]) / sum w[t]          (gamma = 0: the weighted mean of cvk_softmax_ce_fwd_ex; 0/0 = NaN)
+ *   I_c = sum p[c] [t = c], P_c = sum p[c], T_c = sum [t = c], dice_c = (2 I_c + s) / (P_c + T_c + s)
+ *   D = 1 - (1 / K) sum_{c in S} dice_c, S = the classes with T_c > 0 (CVK_DICE_PRESENT) or every class (CVK_DICE_ALL), K = |S|;
+ *   K = 0 gives D = 0; a class with P_c + T_c + s = 0 counts as dice_c = 1 with a zero gradient.  Class weights do not enter D.
+ * A term whose coefficient is 0 is not computed and cannot make L NaN.  Any target outside [0, C) other than ignore_index makes L
+ * NaN and is counted, as in cvk_softmax_ce_fwd.
+ * fwd: `part` is DEVICE scratch of cvk_seg_loss_part_floats(M, C) floats; `record` is DEVICE float[cvk_seg_loss_record_floats(C)]:
+ * record[0] = L, [1] = valid pixels, [2] = out-of-range targets, [3] = sum w[t], [4] = F (0 when ce = 0), [5] = D (0 when dice = 0),
+ * [6] = K, then dice_c[C] (0 outside S), a_c[C] = -2 / (K den_c) and b_c[C] = (2 I_c + s) / (K den_c^2), den_c = P_c + T_c + s (0
+ * outside S).  Two launches (one pass over the logits, a one-workgroup fp64 finish); no allocation, no float atomics (every sum in
+ * one fixed order: bitwise reproducible), no host sync.
+ * bwd: record is fwd's; one pass, dlogits [M][ld_d] =
+ *   g (ce w[t] / record[3] B ([k = t] - p[k]) + dice p[k] (g_k - sum_c g_c p[c])),  g_c = b_c + a_c [t = c],
+ *   B = gamma p[t] (1 - p[t])^(gamma - 1) log p[t] - (1 - p[t])^gamma (finite when p[t] rounds to 1),  g = grad_out * scale;
+ * grad_out: one DEVICE float, nullable (1).  Rows of ignored or out-of-range targets and columns [C, ld_d) are written as zeros. */
+#define CVK_DICE_PRESENT 0
+#define CVK_DICE_ALL 1
+int cvk_seg_loss_part_floats(int M, int C);
+int cvk_seg_loss_record_floats(int C);
+int cvk_seg_loss_fwd(const float* logits, int ld, const int64_t* target, const float* weight, float ce, float dice, float focal_gamma,
+                     float dice_smooth, int dice_average, float* part, float* record, int M, int C, int ignore_index, void* stream);
+int cvk_seg_loss_bwd(const float* logits, int ld, const int64_t* target, const float* weight, float ce, float dice, float focal_gamma,
+                     const float* record, const float* grad_out, float scale, float* dlogits, int ld_d, int M, int C, int ignore_index,
+                     void* stream);
+
 /* ---- class statistics of label masks (class weights for the loss above; SegNet's median-frequency balancing) ----------
  * masks: DEVICE [N][HW] of mask_bytes = 1 (uint8) or 8 (int64) per label (cvk_augment_u8's convention); 0 < num_classes <= 256.
  * Accumulates into DEVICE int64 hist[2 * num_classes + 1] (the caller zeroes it once): hist[c] += pixels of class c,

@@ -181,6 +181,11 @@ SIGNATURES = {
     "cvk_softmax_ce_fwd_ex": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "cvk_softmax_ce_bwd_ex": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_int, c_vp, c_vp, c_float, c_vp, c_int, c_int, c_int, c_int,
                                       c_vp]),
+    "cvk_seg_loss_part_floats": (c_int, [c_int, c_int]),
+    "cvk_seg_loss_record_floats": (c_int, [c_int]),
+    "cvk_seg_loss_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_float, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "cvk_seg_loss_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_vp, c_vp, c_float, c_vp, c_int, c_int, c_int, c_int,
+                                 c_vp]),
     "cvk_class_histogram": (c_int, [c_vp, c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp]),
     "cvk_argmax_channels": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp]),
     "cvk_confusion_accumulate": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

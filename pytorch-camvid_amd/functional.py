@@ -2,6 +2,8 @@
 
   CrossEntropyLoss  <- nn.CrossEntropyLoss() of reference train.py:105 (mean over N*H*W, no ignored class); also torch's
                        weight / reduction / label_smoothing options
+  SegmentationLoss, FocalLoss, DiceLoss, segmentation_loss
+                    <- ce * focal + dice * soft Dice, one fused pass over the logits each way (not in the reference)
   ClassFrequencyMeter, class_weights
                     <- median-frequency (SegNet) / ENet class weights from device-side class histograms of the masks
   argmax_channels   <- preds.argmax(dim=1) of train.py:191
@@ -181,6 +183,157 @@ def cross_entropy(logits, target, weight=None, ignore_index=-100, reduction="mea
         weight, ignore_index = None, weight
     _check_ce_options(weight, reduction, label_smoothing)
     return _ce(logits, target, weight, 1.0, ignore_index, reduction, label_smoothing)
+
+
+DICE_AVERAGES = {"present": 0, "all": 1}           # include/cvk.h CVK_DICE_*
+SEG_RECORD_HEAD = 7                                # loss | valid | out of range | sum w[t] | F | D | K, then dice_c, a_c, b_c
+
+
+class _SegLoss(torch.autograd.Function):
+    """ce * focal + dice * soft Dice in one forward and one backward pass over the logits (cvk_seg_loss_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, opts):
+        ce, dice, gamma, smooth, average, ignore_index, grad_scale = opts
+        lib = _lib.load()
+        if not logits.is_cuda:
+            raise RuntimeError("pytorch_camvid_amd.SegmentationLoss needs HIP tensors (no CPU fallback)")
+        if logits.dtype != torch.float32 or target.dtype != torch.int64:
+            raise RuntimeError(f"expected float32 logits and int64 target, got {logits.dtype} / {target.dtype}")
+        N, C, H, W = logits.shape
+        if tuple(target.shape) != (N, H, W):
+            raise ValueError(f"Expected target size {[N, H, W]}, got {list(target.shape)}")
+        if weight is not None:
+            if weight.dim() != 1 or weight.numel() != C:
+                raise RuntimeError(f"weight tensor should be defined either for all {C} classes or no classes but got weight tensor "
+                                   f"of shape: {list(weight.shape)}")
+            if weight.device != logits.device:
+                raise RuntimeError(f"weight is on {weight.device} but the logits are on {logits.device} (no implicit copy: the loss "
+                                   "stays capturable); move the loss module with .to(device)")
+            if weight.dtype != torch.float32:
+                raise RuntimeError(f"expected a float32 weight, got {weight.dtype}")
+            weight = weight.detach().contiguous()
+        lg, ld = _as_nhwc(logits)
+        tg = target.contiguous()
+        M = N * H * W
+        nfloats = lib.cvk_seg_loss_part_floats(M, C)
+        if nfloats <= 0:
+            raise RuntimeError(f"pytorch_camvid_amd.SegmentationLoss serves 1 to 128 classes and a non-empty batch, got C = {C}, M = {M}")
+        part = torch.empty(nfloats, device=logits.device, dtype=torch.float32)
+        rec = torch.empty(lib.cvk_seg_loss_record_floats(C), device=logits.device, dtype=torch.float32)
+        wp = weight.data_ptr() if weight is not None else None
+        from . import engine
+        engine._timed(None, "k_seg_fwd", 4.0 * M * ld + 8.0 * M, lambda: check(
+            lib.cvk_seg_loss_fwd(lg.data_ptr(), ld, tg.data_ptr(), wp, ce, dice, gamma, smooth, DICE_AVERAGES[average], part.data_ptr(),
+                                 rec.data_ptr(), M, C, int(ignore_index), _stream(logits)), "cvk_seg_loss_fwd"), "byte")
+        ctx.save_for_backward(lg, tg, rec, weight)
+        ctx.meta = (N, C, H, W, ld, ce, dice, gamma, float(grad_scale), int(ignore_index))
+        _CrossEntropy.last_status = rec
+        return rec[0].clone()           # not a view: rec is saved for backward (divisor, a_c, b_c) and published as the status
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        lg, tg, rec, weight = ctx.saved_tensors
+        N, C, H, W, ld, ce, dice, gamma, grad_scale, ignore_index = ctx.meta
+        M = N * H * W
+        d = torch.empty((N, H, W, C), device=lg.device, dtype=torch.float32)
+        g = gout.contiguous()
+        wp = weight.data_ptr() if weight is not None else None
+        from . import engine
+        engine._timed(None, "k_seg_bwd", 4.0 * M * ld + 8.0 * M + 4.0 * M * C, lambda: check(
+            lib.cvk_seg_loss_bwd(lg.data_ptr(), ld, tg.data_ptr(), wp, ce, dice, gamma, rec.data_ptr(), g.data_ptr(), grad_scale,
+                                 d.data_ptr(), C, M, C, ignore_index, _stream(lg)), "cvk_seg_loss_bwd"), "byte")
+        return d.permute(0, 3, 1, 2), None, None, None
+
+
+def _nonneg(name, v):
+    v = float(v)
+    if not 0.0 <= v < float("inf"):
+        raise ValueError(f"{name} must be a finite number >= 0. Got: {v}")
+    return v
+
+
+def _check_seg_options(ce, dice, focal_gamma, weight, dice_smooth, dice_average):
+    ce, dice = _nonneg("ce", ce), _nonneg("dice", dice)
+    if ce == 0.0 and dice == 0.0:
+        raise ValueError("ce and dice must not both be 0")
+    if dice_average not in DICE_AVERAGES:
+        raise ValueError(f"{dice_average} is not a valid value for dice_average (one of {sorted(DICE_AVERAGES)})")
+    if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dim() != 1):
+        raise ValueError("weight must be a 1-D tensor of one value per class")
+    return ce, dice, _nonneg("focal_gamma", focal_gamma), _nonneg("dice_smooth", dice_smooth)
+
+
+class SegmentationLoss(nn.Module):
+    """`ce * Focal_gamma + dice * Dice` as one autograd node: one HIP pass over the logits forward (plus a one-workgroup finish), one
+    backward.  With p = softmax(logits) over the classes and every sum over the pixels of the whole batch whose target is not
+    `ignore_index`:
+      focal  F = sum w[t] (1 - p[t])^focal_gamma (-log p[t]) / sum w[t]      (focal_gamma = 0: torch's weighted mean cross-entropy)
+      Dice   D = 1 - mean over S of (2 I_c + s) / (P_c + T_c + s), I_c = sum p[c] [t = c], P_c = sum p[c], T_c = sum [t = c],
+             s = `dice_smooth`; S = the classes that occur in the batch (`dice_average="present"`) or all of them (`"all"`)
+    `weight` (float32 [C] on the logits' device, a registered buffer as in CrossEntropyLoss) enters the focal term only.  A term whose
+    coefficient is 0 is not computed.  Conventions of CrossEntropyLoss hold: float32 logits [N, C, H, W] (C <= 128) and int64 targets
+    [N, H, W] on the GPU, a 0-dim loss, an out-of-range target makes the loss NaN and `last_ce_status()` reports it, with every pixel
+    ignored the focal term is 0/0 = NaN and the Dice term 0; `grad_scale` multiplies the backward only.  All sums run in a fixed order
+    without float atomics: the loss and its gradient are bitwise reproducible.
+    After a forward, `last_terms` ([F, D]) and `last_dice` (per class, 0 outside S) are views of the device record, read without a
+    sync (a module captured by `GraphedStep` keeps viewing the record the replays rewrite, until it is called eagerly again).  Under `ddp.DataParallel` every rank takes the Dice sums I_c, P_c, T_c (and the focal divisor) over its own part of the
+    batch: the averaged gradient is the mean of the per-rank losses' gradients, not the gradient of a Dice over the global batch."""
+
+    def __init__(self, ce=1.0, dice=0.0, *, focal_gamma=0.0, weight=None, ignore_index=-100, dice_smooth=1.0, dice_average="present",
+                 grad_scale=1.0):
+        super().__init__()
+        self.ce, self.dice, self.focal_gamma, self.dice_smooth = _check_seg_options(ce, dice, focal_gamma, weight, dice_smooth,
+                                                                                    dice_average)
+        self.dice_average = dice_average
+        self.ignore_index = ignore_index
+        self.grad_scale = grad_scale
+        self.register_buffer("weight", weight)
+        self._record = None
+
+    def forward(self, logits, target):
+        loss = _SegLoss.apply(logits, target, self.weight, (self.ce, self.dice, self.focal_gamma, self.dice_smooth, self.dice_average,
+                                                            self.ignore_index, self.grad_scale))
+        self._record = _CrossEntropy.last_status
+        return loss
+
+    def _rec(self):
+        if self._record is None:
+            raise RuntimeError("no forward has run yet")
+        return self._record
+
+    @property
+    def last_terms(self):
+        """[F, D] of the most recent forward (device tensor, no sync)."""
+        return self._rec()[4:6]
+
+    @property
+    def last_dice(self):
+        """dice_c of the most recent forward, [C], 0 for the classes outside S (device tensor, no sync)."""
+        r = self._rec()
+        return r[SEG_RECORD_HEAD:SEG_RECORD_HEAD + (r.numel() - SEG_RECORD_HEAD) // 3]
+
+
+class FocalLoss(SegmentationLoss):
+    """SegmentationLoss(1.0, 0.0, focal_gamma=gamma): the class-weighted focal loss (Lin et al.), mean over the valid pixels."""
+
+    def __init__(self, gamma=2.0, weight=None, ignore_index=-100):
+        super().__init__(1.0, 0.0, focal_gamma=gamma, weight=weight, ignore_index=ignore_index)
+
+
+class DiceLoss(SegmentationLoss):
+    """SegmentationLoss(0.0, 1.0): the soft Dice loss over the whole batch."""
+
+    def __init__(self, smooth=1.0, average="present", ignore_index=-100):
+        super().__init__(0.0, 1.0, dice_smooth=smooth, dice_average=average, ignore_index=ignore_index)
+
+
+def segmentation_loss(logits, target, ce=1.0, dice=0.0, *, focal_gamma=0.0, weight=None, ignore_index=-100, dice_smooth=1.0,
+                      dice_average="present"):
+    """Functional form of SegmentationLoss (same kernels)."""
+    opts = _check_seg_options(ce, dice, focal_gamma, weight, dice_smooth, dice_average)
+    return _SegLoss.apply(logits, target, weight, (opts[0], opts[1], opts[2], opts[3], dice_average, ignore_index, 1.0))
 
 
 def last_ce_status():
