@@ -1,7 +1,7 @@
 """Kernel selection for the fp32 conv blocks: which kernels run a layer's forward pass, data-grad, BatchNorm backward and weight-grad.
 
 `conv_route` decides all of it in one place from the layer geometry, the runner's switches (Runner.kernel_config) and the pass kind, and
-returns a frozen ConvRoute; engine.py launches what the route names.  Nothing here launches a kernel or allocates device memory: the
+returns a frozen ConvRoute; conv_fp32.py launches what the route names.  Nothing here launches a kernel or allocates device memory: the
 library is only asked host-side questions (cvk_thin_*_supported, cvk_wgradp_plane_rows).
 """
 from dataclasses import dataclass
@@ -140,7 +140,7 @@ def _wino_1d(R, N, H, W, k_ch, cout, ldy, fused_ok, h2):
 
 
 def conv_route(R, op, training, need_grad):
-    """The route of conv block `op` (engine.ConvBnRelu) of a plan whose 2-D tiles are R.w2tile / R.w2tile_dgrad (Runner.tile_for).  The block's
+    """The route of conv block `op` (conv_fp32.ConvBnRelu) of a plan whose 2-D tiles are R.w2tile / R.w2tile_dgrad (Runner.tile_for).  The block's
     own flags decide its backward: no backward route when it is frozen with nothing upstream needing a gradient (op.active), no weight-grad
     (and no V kept by the forward pass) when its conv weight is frozen (op.w_req), no data-grad when nothing upstream needs one."""
     lib, src = R.lib, op.src

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-layer timing at the UNet batch-8 shapes: fused 1-D F(4,3) (cvk_conv3x3_wino4f) vs the 2-D pipelines F(4x4,3x3) (cvk_w2d_*)
 and F(6x6,3x3) (cvk_w6_*) for forward / data-grad, and transposed F(4,3) (cvk_conv3x3_wgrad_wino4) vs the 2-D weight-grads.
-Feeds engine.py wino2d_pays / wgrad2d_pays.       usage (GPU box): python tools/bench_w6.py [fwd] [rev] [wgrad]"""
+Feeds route.py wino2d_pays / wgrad2d_pays.       usage (GPU box): python tools/bench_w6.py [fwd] [rev] [wgrad]"""
 import os
 import sys
 
