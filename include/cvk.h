@@ -720,8 +720,9 @@ int cvk_import_nchw_bf16(const float* src, int64_t sN, int64_t sC, int64_t sH, i
 int cvk_bn_relu_apply_bf16(const void* y, int ldy, const float* scale, const float* shift, cvk_viewh out, int out_f32,
                            void* pool, int N, int H, int W, int C, void* stream);
 /* BatchNorm+ReLU backward on bf16 tensors; dout is a bf16 view, or fp32 (dout_f32 = 1: the loss gradient).
- * part: 2 * cvk_bn_bwd_blocks_bf16(M) * C floats (reduce) / cvk_bn_bwd_blocks_bf16(M) * C floats (dx: column sums of dy,
- * the conv bias gradient) -> cvk_colsum_finalize.  dy rows have pitch ld_dy >= C, pad columns are written as 0. */
+ * part: 2 * cvk_bn_bwd_blocks_bf16(M) * C floats (reduce) / cvk_bn_bwd_blocks_bf16(M) * C floats (dx: column sums of the
+ * fp32 dy BEFORE its rounding to bf16, the conv bias gradient; NULL: dy only) -> cvk_colsum_finalize.  dy rows have pitch
+ * ld_dy >= C, pad columns are written as 0. */
 int cvk_bn_bwd_blocks_bf16(int M);
 int cvk_bn_bwd_reduce_bf16(cvk_viewh dout, int dout_f32, const void* y, int ldy, const float* scale, const float* shift,
                            const float* mean, const float* rstd, float* part, int N, int H, int W, int C, void* stream);
