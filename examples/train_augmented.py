@@ -7,6 +7,7 @@ package); random.seed makes the augmentation decisions of the reference's Compos
 
   python examples/train_augmented.py --epochs 2 --iters 20 -b 8
   python examples/train_augmented.py --graphed --clip-grad-norm 1.0    # FlatAdamW with global-norm clipping, one graph replay per iteration
+  python examples/train_augmented.py --graphed --ema-decay 0.999 --ema-warmup   # weight EMA inside the captured step, validated too
 """
 import argparse
 import os
@@ -54,7 +55,15 @@ def main():
     ap.add_argument("--accumulate", type=int, default=1, metavar="K",
                     help="gradient accumulation: one optimizer update per K batches on their mean gradient (cvk.GradAccumulator; with --graphed "
                     "the whole window of K batches is one captured graph).  --iters must be a multiple of K")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="X",
+                    help="keep an exponential moving average of the weights inside the fused step (FlatAdamW(ema_decay=X); needs --graphed); "
+                    "every epoch validates the live and, inside opt.swap_ema(), the averaged weights")
+    ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: decay min(X, (1 + k) / (10 + k)) at the k-th update")
     a = ap.parse_args()
+    if (a.ema_decay is not None or a.ema_warmup) and not a.graphed:
+        ap.error("--ema-decay / --ema-warmup need --graphed (the average lives in FlatAdamW's flat buffers)")
+    if a.ema_warmup and a.ema_decay is None:
+        ap.error("--ema-warmup needs --ema-decay")
     K = a.accumulate
     if K < 1 or a.iters % K:
         ap.error("--accumulate K needs K >= 1 and --iters a multiple of K")
@@ -63,7 +72,8 @@ def main():
     torch.manual_seed(0)
     random.seed(a.seed)
     net = cvk.get_model(a.net, 3, 12).to(dev)
-    opt = cvk.FlatAdamW(net, lr=a.lr, max_grad_norm=a.clip_grad_norm) if a.graphed else torch.optim.AdamW(net.parameters(), lr=a.lr)
+    opt = cvk.FlatAdamW(net, lr=a.lr, max_grad_norm=a.clip_grad_norm, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup) if a.graphed else \
+        torch.optim.AdamW(net.parameters(), lr=a.lr)
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=updates, epochs=a.epochs)
     accum = cvk.GradAccumulator(net, steps=K) if K > 1 else None
     weight = None
@@ -118,6 +128,11 @@ def main():
         val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
         acc, iou, miou = cvk.evaluate(net, val, num_classes=12, ignore_index=11)
         print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}")
+        if a.ema_decay is not None:
+            with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
+                val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)    # the same frames again
+                acc_e, _, miou_e = cvk.evaluate(net, val, num_classes=12, ignore_index=11)
+            print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ augmentation of 960x720 frames on the device see examples/train_augmented.py.  E
   python examples/train_synthetic.py --net unet --epochs 2 --iters 20 -b 8
   python examples/train_synthetic.py --graphed      # each iteration (step, AdamW, log line) as ONE graph replay
   python examples/train_synthetic.py --graphed --clip-grad-norm 1.0     # global-norm clipping inside the captured AdamW step
+  python examples/train_synthetic.py --graphed --ema-decay 0.999 --ema-warmup   # weight EMA inside the captured AdamW step, validated too
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_synthetic.py   # data parallel
 """
 import argparse
@@ -47,8 +48,16 @@ def main():
     ap.add_argument("--accumulate", type=int, default=1, metavar="K",
                     help="gradient accumulation: one optimizer update per K batches on their mean gradient (cvk.GradAccumulator; with --graphed "
                     "the whole window of K batches is one captured graph).  --iters must be a multiple of K")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="X",
+                    help="keep an exponential moving average of the weights inside the fused step (FlatAdamW(ema_decay=X); needs --flat-adamw or "
+                    "--graphed); every epoch validates the live and, inside opt.swap_ema(), the averaged weights")
+    ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: decay min(X, (1 + k) / (10 + k)) at the k-th update")
     a = ap.parse_args()
     a.flat_adamw = a.flat_adamw or a.graphed
+    if (a.ema_decay is not None or a.ema_warmup) and not a.flat_adamw:
+        ap.error("--ema-decay / --ema-warmup need --flat-adamw or --graphed (the average lives in FlatAdamW's flat buffers)")
+    if a.ema_warmup and a.ema_decay is None:
+        ap.error("--ema-warmup needs --ema-decay")
     K = a.accumulate
     if K < 1 or a.iters % K:
         ap.error("--accumulate K needs K >= 1 and --iters a multiple of K")
@@ -66,7 +75,8 @@ def main():
     cvk.set_conv_precision(net, a.precision)
     cvk.set_split_operands(net, a.split_operands)
     model = cvk.ddp.DataParallel(net) if world > 1 else net
-    opt = cvk.FlatAdamW(net, lr=a.lr, weight_decay=a.wd, max_grad_norm=a.clip_grad_norm) if a.flat_adamw else \
+    opt = cvk.FlatAdamW(net, lr=a.lr, weight_decay=a.wd, max_grad_norm=a.clip_grad_norm, ema_decay=a.ema_decay,
+                        ema_warmup=a.ema_warmup) if a.flat_adamw else \
         torch.optim.AdamW(net.parameters(), lr=a.lr, weight_decay=a.wd)     # train.py:100
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=updates, epochs=a.epochs)  # :103-104
     if K > 1 and a.graphed and world > 1:
@@ -146,8 +156,15 @@ def main():
         acc, iou, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11)
         if rank == 0:
             print(f"          val acc {acc:.4f}  mIoU(11 classes) {miou:.4f}")
+        if a.ema_decay is not None:
+            with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
+                acc_e, _, miou_e = cvk.evaluate(net, batches, num_classes=12, ignore_index=11)
+            if rank == 0:
+                print(f"          EMA acc {acc_e:.4f}  mIoU(11 classes) {miou_e:.4f}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
     if rank == 0:
         torch.save(net.state_dict(), "/tmp/cvk_synthetic.pth")             # train.py:232-240; loads into the reference too
+        if a.ema_decay is not None:
+            torch.save(opt.ema_state_dict(), "/tmp/cvk_synthetic_ema.pth")  # the averaged weights, same keys and layout
     if world > 1:
         dist.destroy_process_group()
 

@@ -627,6 +627,22 @@ int cvk_adamw_step_ranges_clip_dev(float* param, const float* grad, float* exp_a
 int cvk_step_log_norm(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb,
                       const float* record, float* ring, int capacity, int64_t* counter, void* stream);
 
+/* ---- an exponential moving average of the weights inside the AdamW step (cvk.FlatAdamW(net, ema_decay=...)) ---------------------------
+ * cvk_adamw_step_ranges_ema / _ema_dev: cvk_adamw_step_ranges / _dev with one more buffer `ema` (fp32, laid out like param).  The thread
+ * that has stored the new parameter value p_new of an element goes on with it in the register: ema[i] += alpha * (p_new - ema[i]); param
+ * is not read again.  param, exp_avg and exp_avg_sq come out bitwise as from cvk_adamw_step_ranges (record null) or
+ * cvk_adamw_step_ranges_clip (record non-null: the {total_norm, clip_coef} record of cvk_grad_norm, as there).  Elements outside every
+ * range are neither read nor written in ema either.  0 < alpha <= 1 (alpha = 1 - decay).
+ *   _ema: records as kernel arguments (nhyper <= CVK_ADAMW_ARG_RECORDS, host array), alpha as an argument.
+ *   _ema_dev: records and alpha (one float) in DEVICE memory, rewritten by the host between graph replays; alpha_host is the value the host
+ *     uploads there next (at a capture: the first one) and is only checked, since the device value cannot be. */
+int cvk_adamw_step_ranges_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                              const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                              const float* record, float alpha, void* stream);
+int cvk_adamw_step_ranges_ema_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                  const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                                  const float* record, const float* alpha, float alpha_host, void* stream);
+
 /* ---- gradient accumulation over micro-batches (GradAccumulator) -------------------------------------------------------------------
  * One streaming launch over a planned segment table (cvk_grad_norm_plan: the same table type and the same workgroup walk as the norm)
  * that folds one flat gradient buffer into another.  dst and src are two DEVICE buffers of n floats with the same layout; the table's

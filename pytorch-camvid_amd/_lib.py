@@ -241,6 +241,8 @@ SIGNATURES = {
     "cvk_adamw_step_ranges_clip": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),   # HOST AdamwHyper array
     "cvk_adamw_step_ranges_clip_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
     "cvk_step_log_norm": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
+    "cvk_adamw_step_ranges_ema": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_float, c_vp]),   # HOST AdamwHyper array
+    "cvk_adamw_step_ranges_ema_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_float, c_vp]),
     "cvk_grad_accumulate": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_float, c_vp]),
 }
 

@@ -811,9 +811,10 @@ __global__ __launch_bounds__(256) void k_confusion(const int64_t* __restrict__ p
 // k_adamw_dev (scalars from a device record) and the range-table kernels: one expression list, so they cannot round differently.
 // coef scales the gradient on its way in (global-norm clipping, cvk_adamw_step_ranges_clip*); the unclipped kernels pass the
 // literal 1.f, and x * 1.f is x.
-__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                             float* __restrict__ v, int64_t i, float lr, float b1, float b2, float eps, float wd,
-                                             float bc1, float bc2_sqrt, float coef) {
+// Returns the parameter value it stored, for the EMA form that goes on with it in the register.
+__device__ __forceinline__ float adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, int64_t i, float lr, float b1, float b2, float eps, float wd,
+                                              float bc1, float bc2_sqrt, float coef) {
     const float gi = g[i] * coef;
     float pi = p[i] * (1.f - lr * wd);
     const float mi = b1 * m[i] + (1.f - b1) * gi;
@@ -823,6 +824,7 @@ __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float*
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     pi -= (lr / bc1) * (mi / denom);
     p[i] = pi;
+    return pi;
 }
 
 __global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -893,6 +895,48 @@ __global__ void k_adamw_ranges_clip_dev(float* __restrict__ p, const float* __re
                                         int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
                                         const cvk_adamw_hyper* __restrict__ hyper, int nhyper, const float* __restrict__ clip) {
     adamw_ranges_body(p, g, m, v, n, rt, nr, hyper, nhyper, clip);
+}
+
+// The EMA forms (cvk_adamw_step_ranges_ema*): the walk of adamw_ranges_body and the same adamw_update, then the thread moves the average
+// towards the parameter value it has just stored, ema += alpha * (p_new - ema), from the register: param is not read again.  Elements
+// outside every range are not touched in ema either.  `clip` may be null (coefficient 1.f), so clipped and unclipped steps share a kernel.
+__device__ __forceinline__ void adamw_ranges_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ ema, int64_t n,
+                                                      const cvk_adamw_range* __restrict__ rt, int nr,
+                                                      const cvk_adamw_hyper* __restrict__ hyper, int nhyper,
+                                                      const float* __restrict__ clip, float alpha) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = nr - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rt[mid].block0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const int64_t off = rt[lo].offset, len = rt[lo].length;
+    const int hx = rt[lo].hyper, b0 = rt[lo].block0;
+    const int nb = (lo + 1 < nr ? rt[lo + 1].block0 : (int)gridDim.x) - b0;
+    if (off < 0 || len <= 0 || off + len > n || hx < 0 || hx >= nhyper || nb <= 0 || b < b0) return;
+    const float lr = hyper[hx].lr, b1 = hyper[hx].beta1, b2 = hyper[hx].beta2, eps = hyper[hx].eps, wd = hyper[hx].weight_decay;
+    const float bc1 = hyper[hx].bc1, bc2_sqrt = hyper[hx].bc2_sqrt;
+    const float coef = clip != nullptr ? clip[1] : 1.f;
+    for (int64_t i = off + (int64_t)(b - b0) * blockDim.x + threadIdx.x; i < off + len; i += (int64_t)nb * blockDim.x) {
+        const float pi = adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, coef);
+        const float e = ema[i];
+        ema[i] = e + alpha * (pi - e);
+    }
+}
+
+__global__ void k_adamw_ranges_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                   float* __restrict__ ema, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
+                                   AdamwArgRecords recs, int nhyper, const float* __restrict__ clip, float alpha) {
+    adamw_ranges_ema_body(p, g, m, v, ema, n, rt, nr, recs.r, nhyper, clip, alpha);
+}
+
+__global__ void k_adamw_ranges_ema_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                       float* __restrict__ ema, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
+                                       const cvk_adamw_hyper* __restrict__ hyper, int nhyper, const float* __restrict__ clip,
+                                       const float* __restrict__ alpha) {
+    adamw_ranges_ema_body(p, g, m, v, ema, n, rt, nr, hyper, nhyper, clip, *alpha);
 }
 
 // One row [loss, lr, beta1, ||gw||_2, ||gb||_2] of the per-iteration log into ring[(*counter % capacity) * 5 ..], then ++*counter.
@@ -1710,6 +1754,34 @@ extern "C" int cvk_adamw_step_ranges_clip_dev(float* param, const float* grad, f
     hipLaunchKernelGGL(k_adamw_ranges_clip_dev, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
                        ranges, nranges, hyper, nhyper, record);
     CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_clip_dev");
+}
+
+// The EMA forms.  `record` may be null: an unclipped step.
+extern "C" int cvk_adamw_step_ranges_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                         const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                                         const float* record, float alpha, void* stream) {
+    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ema && ranges && hyper, "cvk_adamw_step_ranges_ema: null pointer");
+    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
+                  "cvk_adamw_step_ranges_ema: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
+    CVK_CHECK_ARG(alpha > 0.f && alpha <= 1.f, "cvk_adamw_step_ranges_ema: alpha %g outside (0, 1]", (double)alpha);
+    AdamwArgRecords recs = {};
+    for (int i = 0; i < nhyper; ++i) recs.r[i] = hyper[i];
+    hipLaunchKernelGGL(k_adamw_ranges_ema, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, ema, n, ranges,
+                       nranges, recs, nhyper, record, alpha);
+    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_ema");
+}
+
+// alpha (DEVICE, one float) is what the kernel reads, rewritten by the host between graph replays; alpha_host is the value the host is
+// about to upload there (at a capture: the first one), checked here because the device value cannot be.
+extern "C" int cvk_adamw_step_ranges_ema_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                             const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper,
+                                             int nhyper, const float* record, const float* alpha, float alpha_host, void* stream) {
+    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ema && ranges && hyper && alpha, "cvk_adamw_step_ranges_ema_dev: null pointer");
+    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_adamw_step_ranges_ema_dev: bad arguments");
+    CVK_CHECK_ARG(alpha_host > 0.f && alpha_host <= 1.f, "cvk_adamw_step_ranges_ema_dev: alpha %g outside (0, 1]", (double)alpha_host);
+    hipLaunchKernelGGL(k_adamw_ranges_ema_dev, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, ema, n,
+                       ranges, nranges, hyper, nhyper, record, alpha);
+    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_ema_dev");
 }
 
 // ---- library-wide pieces ---------------------------------------------------------------------------------------

@@ -154,11 +154,11 @@ def amax_blocks(lib, n, dev):
 # changed.  A raw-pointer optimizer or a `p.data` write does not touch the parameter's version counter, so validity is
 # explicit: an entry is valid while (global optimizer epoch, runner epoch, storage pointer, tensor version) are unchanged.
 #   * any torch.optim optimizer step      -> global epoch (torch.optim.optimizer.register_optimizer_step_post_hook)
-#   * FlatAdamW.step, load_state_dict, ddp.DataParallel's broadcast, mark_weights_dirty(net) -> runner epoch
+#   * FlatAdamW.step, FlatAdamW.swap_ema (entry and exit), load_state_dict, ddp.DataParallel's broadcast, mark_weights_dirty(net) -> runner epoch
 #   * .to() / .cuda() / in-place autograd-visible ops -> storage pointer / version counter
 # FAIL-SAFE in training: a TRAINING pass (forward with a backward to follow) never trusts entries of earlier passes — its
 # signature carries a per-pass token, so the tensors are built once per pass (one batched launch in bf16 mode) and shared by that
-# pass's forward and backward only.  Writes nobody can see (`p.data.copy_()` of an EMA swap, manual re-initialisation, a foreign
+# pass's forward and backward only.  Writes nobody can see (`p.data.copy_()` of a hand-written EMA swap, manual re-initialisation, a foreign
 # kernel, a freed-and-reallocated parameter at the same address) are therefore always picked up in training, as stock torch
 # picks them up.  Only eval / no-grad passes reuse entries across calls; THERE an invisible in-place write needs
 # `mark_weights_dirty(net)`.

@@ -26,6 +26,9 @@ group and step count, cvk_adamw_step_ranges_dev; the log row reads param_groups[
 captured optimizer as it drives the eager one.  A FlatAdamW with `max_grad_norm` is captured with its norm reduction and finish between
 backward and the AdamW launch (after the stream's waits for the all-reduces: every rank reduces the same averaged buffer, so no extra
 collective), and the log rows gain the global norm and the clip coefficient; `max_grad_norm` / `norm_type` are baked into the graph.
+A FlatAdamW with `ema_decay` is captured with the EMA form of the step (cvk_adamw_step_ranges_ema_dev): the update's alpha travels with the
+hyper records, one float behind them, so the decay may change between replays and warm-up changes it on every one; whether an EMA exists
+is baked in.  Under `accumulator=` the average takes one update per window; under data parallel every rank averages the same parameters.
 Frozen parameters (requires_grad False, BatchNorm children in eval mode) are captured as
 they are when the GraphedStep is built; replay() refuses to run after any of that changes:
 
@@ -46,6 +49,7 @@ import torch
 
 from . import _lib, engine
 from ._lib import check
+from .optim import ema_alpha as _ema_alpha
 
 HYPER_FLOATS = 7                         # include/cvk.h cvk_adamw_hyper: lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt
 HYPER_BYTES = 4 * HYPER_FLOATS
@@ -124,8 +128,11 @@ class GraphedStep:
             self._opt_recs, self._opt_ranges = optimizer._ranges(self._opt_idx)
             self._table, self._table_blocks = optimizer._table(self._opt_ranges, len(self._opt_recs))   # uploaded before the capture
             nrec = 1 + len(self._opt_recs)
-            self._hyper = torch.zeros(nrec * HYPER_FLOATS, device=x.device, dtype=torch.float32)
-            self._hyper_pin = torch.zeros(HYPER_SLOTS, nrec * HYPER_FLOATS, dtype=torch.float32, pin_memory=True)
+            # with an EMA one more float behind the records: the update's alpha, uploaded by the same copy
+            self._ema = optimizer._ema_options() is not None
+            nfl = nrec * HYPER_FLOATS + (1 if self._ema else 0)
+            self._hyper = torch.zeros(nfl, device=x.device, dtype=torch.float32)
+            self._hyper_pin = torch.zeros(HYPER_SLOTS, nfl, dtype=torch.float32, pin_memory=True)
             self._hyper_busy = [None] * HYPER_SLOTS     # per slot: event after the H2D copy that READ it
             self._hyper_slot = 0
             # global-norm clipping (FlatAdamW(max_grad_norm=...)): the norm's segment table and partials are uploaded before the capture
@@ -192,6 +199,18 @@ class GraphedStep:
             if self._norm_plan is not None:
                 # reduction + finish into the optimizer's {total_norm, clip_coef} record, then the AdamW launch that scales by it
                 self._norm_plan.norm(self._gflat.data_ptr(), self._clip[1], self._clip[0], opt._clip_rec, stream)
+            if self._ema:
+                # the EMA form, clipped or not: alpha is read from the float behind the records; the host value is what the first replay uploads
+                nrec = 1 + len(self._opt_recs)
+                alpha0 = float(_ema_alpha(opt.ema_decay, opt.ema_warmup, opt._ema_updates + 1))
+                check(lib.cvk_adamw_step_ranges_ema_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
+                                                        opt._ema.data_ptr(), opt._flat.numel(), self._table.data_ptr(),
+                                                        len(self._opt_ranges), self._table_blocks, self._hyper.data_ptr() + HYPER_BYTES,
+                                                        len(self._opt_recs),
+                                                        opt._clip_rec.data_ptr() if self._norm_plan is not None else None,
+                                                        self._hyper.data_ptr() + nrec * HYPER_BYTES, alpha0, stream),
+                      "cvk_adamw_step_ranges_ema_dev")
+            elif self._norm_plan is not None:
                 check(lib.cvk_adamw_step_ranges_clip_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
                                                          opt._flat.numel(), self._table.data_ptr(), len(self._opt_ranges),
                                                          self._table_blocks, self._hyper.data_ptr() + HYPER_BYTES, len(self._opt_recs),
@@ -221,6 +240,8 @@ class GraphedStep:
         """Every group as the scheduler left it + the next step counts -> the device records, on the current stream (no host sync: the host
         waits only when it is HYPER_SLOTS replays ahead of the copies that read its pinned slots)."""
         opt = self.optimizer
+        if self._ema:
+            opt._ema_options()              # a decay outside [0, 1) is refused before anything is counted
         g = opt.param_groups[0]
         opt._step += 1
         for i in self._opt_idx:
@@ -233,6 +254,8 @@ class GraphedStep:
         check(_lib.load().cvk_adamw_hyper_fill(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                                                float(g["weight_decay"]), opt._step, pin.data_ptr()), "cvk_adamw_hyper_fill")
         opt._fill(self._opt_recs, pin[HYPER_FLOATS:])
+        if self._ema:
+            pin[-1] = float(opt._next_ema_alpha())
         self._hyper.copy_(pin, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -278,7 +301,7 @@ class GraphedStep:
         if opt is None:
             return ()
         return (id(opt), len(opt.param_groups), tuple(opt._group_of()), opt._flat.data_ptr(), tuple(p.data_ptr() for p in opt._plist),
-                opt.max_grad_norm, opt.norm_type)
+                opt.max_grad_norm, opt.norm_type, opt.ema_decay is not None)
 
     def replay(self, x=None, t=None):
         """Copy a new batch into the static input buffers (optional) and replay the step.  Returns the (static) loss tensor.
@@ -289,13 +312,15 @@ class GraphedStep:
                                "block's BatchNorm, a parameter's requires_grad, a swapped block, conv precision, a kernel "
                                "knob, it was wrapped in / unwrapped from ddp.DataParallel, a GradAccumulator was attached, detached or given other "
                                "steps / mean, or the captured FlatAdamW was rebuilt, re-homed, "
-                               "regrouped or given another max_grad_norm / norm_type): the "
+                               "regrouped, given another max_grad_norm / norm_type or its EMA switched on or off): the "
                                "captured graph would silently run the "
                                "old configuration — build a new GraphedStep")
         if self.accumulator is not None and self.accumulator.micro_step:
             raise RuntimeError("GraphedStep.replay: the accumulator is in the middle of an eager window (micro-step "
                                f"{self.accumulator.micro_step} of {self.accumulator.steps}); the captured window starts at micro-step 0 — "
                                "finish the window or reset() the accumulator first")
+        if self.optimizer is not None:
+            self.optimizer._refuse_swapped("GraphedStep.replay")
         if x is not None:
             self.x.copy_(x, non_blocking=True)
         if t is not None:

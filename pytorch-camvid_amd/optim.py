@@ -16,10 +16,22 @@ device record {total_norm, clip_coef}; the AdamW launch multiplies every gradien
 (cvk_adamw_step_ranges_clip).  `.grad` is NOT rescaled — the one difference from the two-call idiom `clip_grad_norm_(...); opt.step()`,
 which rewrites all gradients in place: after a clipped step `.grad` still holds what backward produced, `opt.grad_norm` its norm and
 `opt.clip_coef` the factor the update applied.  `clip_grad_norm_` below is the stand-alone form with torch's contract (scaled `.grad`s).
-Parameter gradients are fp32 in every mode (fp32, bf16 storage, split operands), so clipping is the same code under all of them."""
+Parameter gradients are fp32 in every mode (fp32, bf16 storage, split operands), so clipping is the same code under all of them.
+
+Weight averaging: `FlatAdamW(net, ema_decay=d, ema_warmup=False)` keeps an exponential moving average of the parameters in one more flat
+buffer, initialised to the weights the optimizer is built on (the convention of torch.optim.swa_utils.AveragedModel and timm).  The thread
+of the AdamW kernel that has just stored an element's new value goes on to `ema += alpha * (p_new - ema)` with it (cvk_adamw_step_ranges_ema:
+two more passes over the buffer instead of the three of a separate lerp, no launch, and inside the captured graph of GraphedStep).
+alpha = 1 - d, with warm-up 1 - min(d, (1 + k) / (10 + k)) at the k-th update (`ema_alpha`).  A parameter a step skips (frozen, no
+gradient) keeps its average: one frozen from the start has an average equal to itself.  `with opt.swap_ema():` exchanges the weights and
+the average for validation and saving (and tells the executor that its derived weights are stale); `opt.ema_state_dict()` is the
+network's state_dict() with the averaged parameters, without a swap.  BatchNorm running statistics are NOT averaged: inside swap_ema()
+and in ema_state_dict() they are the live ones, as with AveragedModel's default use_buffers=False; recomputing them is left to the user."""
+import contextlib
 import ctypes
 import math
 
+import numpy
 import torch
 
 from . import _lib, engine
@@ -49,6 +61,30 @@ def _check_clip_options(max_norm, norm_type, what):
     if not mx >= 0.0:
         raise ValueError(f"{what}: max_norm {max_norm!r} must be >= 0")
     return mx, nt
+
+
+def _check_ema_decay(decay, what):
+    """ema_decay as a float in [0, 1), or None; ValueError for anything else (NaN included)."""
+    if decay is None:
+        return None
+    try:
+        d = float(decay)
+    except (TypeError, ValueError):
+        d = float("nan")
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"{what}: ema_decay {decay!r} must be in [0, 1)")
+    return d
+
+
+def ema_alpha(decay, warmup, k):
+    """The weight 1 - d_k of the new parameters in the k-th EMA update (k counts the updates including this one, from 1), as the
+    numpy.float32 the kernel takes: d_k = decay, with warm-up min(decay, (1 + k) / (10 + k)) so that the average follows the weights
+    through the first steps.  Evaluated in double precision and rounded once."""
+    d = float(decay)
+    if warmup:
+        k = int(k)
+        d = min(d, (1.0 + k) / (10.0 + k))
+    return numpy.float32(1.0 - d)
 
 
 def norm_segments(pairs):
@@ -143,8 +179,10 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
 
 
 class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, groups=None, max_grad_norm=None, norm_type=2.0):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, groups=None, max_grad_norm=None, norm_type=2.0,
+                 ema_decay=None, ema_warmup=False):
         self.max_grad_norm, self.norm_type = _check_clip_options(max_grad_norm, norm_type, "FlatAdamW")
+        self.ema_decay, self.ema_warmup = _check_ema_decay(ema_decay, "FlatAdamW"), bool(ema_warmup)
         params = _block_params(net)                       # execution order == the executor's flat parameter list
         if len(params) != len(list(net.parameters())):
             raise ValueError("FlatAdamW needs a network made only of conv+BN blocks (UNet / SegNet)")
@@ -185,6 +223,10 @@ class FlatAdamW(torch.optim.Optimizer):
         self._tables = {}                                 # range table (host tuple) -> (device table, workgroups)
         self._clip_rec = torch.zeros(2, device=dev, dtype=torch.float32)    # {total_norm, clip_coef} of the last clipped step
         self._norm_plans = {}                             # segment table (host tuple) -> _NormPlan
+        self._net = net
+        self._ema = self._flat.clone() if self.ema_decay is not None else None    # the average starts at the initial weights
+        self._ema_updates = 0                             # EMA updates made: its own counter (a resumed scheduler may set _step)
+        self._swapped = False                             # inside swap_ema(): the flat buffer holds the average
 
     @property
     def grad_norm(self):
@@ -206,6 +248,79 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def _clip_options(self):
         return _check_clip_options(self.max_grad_norm, self.norm_type, "FlatAdamW")
+
+    @property
+    def ema_updates(self):
+        """EMA updates made so far (steps in which something had a gradient, since construction or the loaded state)."""
+        return self._ema_updates
+
+    def _ema_options(self):
+        """ema_decay as it is now (None without an EMA), checked; switching an EMA on or off after construction is refused."""
+        d = _check_ema_decay(self.ema_decay, "FlatAdamW")
+        if (d is None) != (self._ema is None):
+            raise RuntimeError("FlatAdamW: ema_decay was switched " + ("off" if d is None else "on") + " after construction; the EMA buffer "
+                               + ("exists" if d is None else "was never allocated") + " — build the optimizer with the ema_decay it is to have "
+                               "(the value itself may change between steps)")
+        return d
+
+    def _refuse_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError(f"{what}: inside FlatAdamW.swap_ema() the network holds the averaged weights; leave the context before "
+                               "training on")
+
+    def _next_ema_alpha(self):
+        """Count one EMA update and return its alpha (numpy.float32)."""
+        self._ema_updates += 1
+        return ema_alpha(self.ema_decay, self.ema_warmup, self._ema_updates)
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Validate or save with the averaged weights: on entry the contents of the flat parameter buffer and of the EMA buffer are
+        exchanged (the parameters stay views of the same memory, so net.parameters(), state_dict(), evaluate, predict, save_checkpoint
+        all see the average) and the executor's derived weights are invalidated; on exit the same again.  BatchNorm running statistics
+        are the live ones, not averaged.  step() and GraphedStep.replay() raise inside; nesting is refused."""
+        if self._ema_options() is None:
+            raise RuntimeError("FlatAdamW.swap_ema(): the optimizer keeps no EMA (ema_decay=None)")
+        if self._swapped:
+            raise RuntimeError("FlatAdamW.swap_ema(): already inside swap_ema()")
+        self._check_homes()
+        self._exchange_ema()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange_ema()
+            self._swapped = False
+
+    @torch.no_grad()
+    def _exchange_ema(self):
+        tmp = self._flat.clone()
+        self._flat.copy_(self._ema)
+        self._ema.copy_(tmp)
+        engine._bump_epoch()          # the parameters changed behind the executor's back: derived weight tensors are stale
+
+    @torch.no_grad()
+    def ema_state_dict(self):
+        """The network's state_dict() (same keys, shapes and memory layout) with every parameter replaced by a clone of its average.
+        Buffers (BatchNorm running statistics) are the live ones.  No swap: safe between training steps."""
+        if self._ema_options() is None:
+            raise RuntimeError("FlatAdamW.ema_state_dict(): the optimizer keeps no EMA (ema_decay=None)")
+        avg = self._flat if self._swapped else self._ema          # inside swap_ema() the average lives in the parameter buffer
+        index = {id(p): i for i, p in enumerate(self._plist)}
+        names = {name: index[id(p)] for name, p in self._net.named_parameters(remove_duplicate=False)}
+        sd = self._net.state_dict()
+        for k in sd:
+            i = names.get(k)
+            if i is None:
+                continue
+            p, o = self._plist[i], self._offs[i]
+            seg = avg[o:o + p.numel()]
+            if p.dim() == 4:
+                co, ci, kh, kw = p.shape
+                sd[k] = seg.view(co, kh, kw, ci).permute(0, 3, 1, 2).clone()     # preserve_format: channels_last, like the parameter
+            else:
+                sd[k] = seg.view(p.shape).clone()
+        return sd
 
     def _group_of(self):
         ids = {}
@@ -298,9 +413,16 @@ class FlatAdamW(torch.optim.Optimizer):
         sd = super().state_dict()           # param_groups: every group's options and its members
         sd["flat_adamw"] = {"step": self._step, "steps": list(self._steps), "exp_avg": self._m.clone(), "exp_avg_sq": self._v.clone(),
                             "offsets": list(self._offs), "max_grad_norm": self.max_grad_norm, "norm_type": self.norm_type}
+        if self._ema is not None:
+            self._refuse_swapped("FlatAdamW.state_dict()")
+            sd["flat_adamw"].update(ema=self._ema.clone(), ema_decay=self.ema_decay, ema_warmup=self.ema_warmup,
+                                    ema_updates=self._ema_updates)
         return sd
 
     def load_state_dict(self, state_dict):
+        """With an EMA: the saved average, decay, warm-up flag and update count are restored; a state saved without them re-initialises the
+        average from the parameters as they are now (load the network first) and sets the count to 0.  Without one they are ignored."""
+        self._refuse_swapped("FlatAdamW.load_state_dict()")
         state_dict = dict(state_dict)
         extra = state_dict.pop("flat_adamw", None)
         super().load_state_dict(state_dict)
@@ -316,13 +438,27 @@ class FlatAdamW(torch.optim.Optimizer):
             if "max_grad_norm" in extra:    # absent in a state dict saved before clipping existed: the constructor's options stay
                 self.max_grad_norm, self.norm_type = _check_clip_options(extra["max_grad_norm"], extra.get("norm_type", 2.0),
                                                                          "FlatAdamW.load_state_dict")
+        if self._ema is not None:
+            if extra is not None and "ema" in extra:
+                if extra["ema"].numel() != self._ema.numel():
+                    raise ValueError("FlatAdamW.load_state_dict: the saved EMA belongs to a different network layout")
+                self._ema.copy_(extra["ema"])
+                self.ema_decay = _check_ema_decay(extra["ema_decay"], "FlatAdamW.load_state_dict")
+                if self.ema_decay is None:
+                    raise ValueError("FlatAdamW.load_state_dict: the saved state carries an EMA without a decay")
+                self.ema_warmup, self._ema_updates = bool(extra["ema_warmup"]), int(extra["ema_updates"])
+            else:
+                self._ema.copy_(self._flat)
+                self._ema_updates = 0
 
     @torch.no_grad()
     def step(self, closure=None):
+        self._refuse_swapped("FlatAdamW.step()")
         loss = closure() if closure is not None else None
         self._check_homes()
+        ema = self._ema_options()
         idx = self._trainable()
-        if not idx:                   # torch.optim.AdamW: nothing has a gradient, nothing changes
+        if not idx:                   # torch.optim.AdamW: nothing has a gradient, nothing changes (and the EMA counts no update)
             return loss
         max_norm, norm_type = self._clip_options()
         self._step += 1
@@ -332,6 +468,7 @@ class FlatAdamW(torch.optim.Optimizer):
         lib = _lib.load()
         stream = torch.cuda.current_stream(self._flat.device).cuda_stream
         recs, ranges = self._ranges(idx)
+        alpha = self._next_ema_alpha() if ema is not None else None
         if max_norm is not None:      # one norm over everything that takes this step, all groups together: reduction + finish
             self._norm_plan(idx).norm(grad.data_ptr(), norm_type, max_norm, self._clip_rec, stream)
         # the records travel as kernel arguments: one launch per CVK_ADAMW_ARG_RECORDS distinct (group, step count) pairs
@@ -341,6 +478,13 @@ class FlatAdamW(torch.optim.Optimizer):
             hyper = (_lib.AdamwHyper * len(crecs))()
             self._fill(crecs, hyper)
             table, nb = self._table(cranges, len(crecs))
+            if ema is not None:       # the EMA form: the clip record or null, every chunk with the update's one alpha
+                check(lib.cvk_adamw_step_ranges_ema(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                                                    self._ema.data_ptr(), self._flat.numel(), table.data_ptr(), len(cranges), nb,
+                                                    ctypes.addressof(hyper), len(crecs),
+                                                    self._clip_rec.data_ptr() if max_norm is not None else None, float(alpha), stream),
+                      "cvk_adamw_step_ranges_ema")
+                continue
             if max_norm is not None:
                 check(lib.cvk_adamw_step_ranges_clip(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
                                                      self._flat.numel(), table.data_ptr(), len(cranges), nb, ctypes.addressof(hyper),
