@@ -538,30 +538,37 @@ int cvk_augment_u8(const uint8_t* frames, const void* masks, int mask_bytes, int
 int cvk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 
-/* The same step with its scalars read from DEVICE memory, so that a captured graph (GraphedStep(optimizer=...)) picks up the
- * scheduler's lr / beta1 of every replay: the host fills a cvk_adamw_hyper with cvk_adamw_hyper_fill (host function, no launch;
- * the bias corrections bc1 = 1 - beta1^step and bc2_sqrt = sqrt(1 - beta2^step) come from the same host expressions
- * cvk_adamw_step evaluates) and copies it to the device outside the graph.  cvk_adamw_step_dev has k_adamw's arithmetic in its
- * operation order: the update is bitwise the one cvk_adamw_step makes with the same values. */
+/* One hyper-parameter record: a group's lr / betas / eps / weight decay and the bias corrections of one step count.
+ * cvk_adamw_hyper_fill (host function, no launch) fills one; bc1 = 1 - beta1^step and bc2_sqrt = sqrt(1 - beta2^step) come from the
+ * same host expressions cvk_adamw_step evaluates. */
 typedef struct cvk_adamw_hyper {
     float lr, beta1, beta2, eps, weight_decay;
     float bc1;                   /* 1 - beta1^step */
     float bc2_sqrt;              /* sqrt(1 - beta2^step) */
 } cvk_adamw_hyper;
 int cvk_adamw_hyper_fill(float lr, float beta1, float beta2, float eps, float weight_decay, int step, cvk_adamw_hyper* out);
-int cvk_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                       const cvk_adamw_hyper* hyper, void* stream);
 
-/* AdamW over a RANGE TABLE of the flat buffers (fine-tuning: frozen parameters, parameter groups, a step count per parameter).  `ranges`
- * (DEVICE, nranges entries) lists the trainable ranges [offset, offset + length) of param / grad / exp_avg / exp_avg_sq, each with the
- * index of the cvk_adamw_hyper record (one group's lr / betas / eps / weight decay and the bias corrections of one step count) that updates
- * it; elements outside every range (frozen parameters and their moments) are neither read nor written.  The same element update as
- * cvk_adamw_step in the same operation order: one range over the whole buffer with one record is bitwise cvk_adamw_step.
- * cvk_adamw_plan_ranges (host function, no launch) checks a HOST copy of the table against the buffer length n and the record count and
- * fills every block0 (the range's first workgroup); it returns the workgroup count the launches take as nblocks, or a negative error.
- * The table uploaded to the device must be the planned one.
- * cvk_adamw_step_ranges: the records as kernel arguments (eager; nhyper <= CVK_ADAMW_ARG_RECORDS, host array).
- * cvk_adamw_step_ranges_dev: the records in DEVICE memory (nhyper of them), rewritten by the host between graph replays. */
+/* AdamW over a RANGE TABLE of the flat buffers (fine-tuning: frozen parameters, parameter groups, a step count per parameter), with
+ * optional global-norm clipping and an optional moving average of the weights, in one launch.
+ *   ranges (DEVICE, nranges entries): the trainable ranges [offset, offset + length) of param / grad / exp_avg / exp_avg_sq (and ema),
+ *     each with the index of the cvk_adamw_hyper record that updates it.  Elements outside every range (frozen parameters and their
+ *     moments) are neither read nor written, in any buffer.  cvk_adamw_plan_ranges (host function, no launch) checks a HOST copy of the
+ *     table against the buffer length n and the record count, fills every block0 (the range's first workgroup) and returns the workgroup
+ *     count the launches take as nblocks, or a negative error.  The table uploaded to the device must be the planned one.
+ *   The element update is cvk_adamw_step's, in the same operation order: one range over the whole buffer with one record, record and
+ *     ema null, is bitwise cvk_adamw_step.
+ *   record (DEVICE, may be null): the {total_norm, clip_coef} record of cvk_grad_norm.  Every gradient element is multiplied by record[1]
+ *     on its way into the update (one more operand of the same expression list); the gradient buffer is not rewritten.  Null means
+ *     coefficient 1.0f, and a step with a coefficient of 1.0f is bitwise the step with a null record.
+ *   ema (DEVICE, may be null): one more fp32 buffer laid out like param.  The thread that has stored the new value p_new of an element
+ *     goes on with it in the register: ema[i] += alpha * (p_new - ema[i]); param is not read again.  param, exp_avg and exp_avg_sq come
+ *     out bitwise as with ema null.  0 < alpha <= 1 (alpha = 1 - decay).  With ema null no average is kept and alpha is ignored.
+ * cvk_adamw_step_ranges (eager): hyper is a HOST array of nhyper <= CVK_ADAMW_ARG_RECORDS records; they and alpha travel as kernel
+ *   arguments.
+ * cvk_adamw_step_ranges_dev (captured graphs, GraphedStep(optimizer=...)): hyper (nhyper records) and alpha (one float) are in DEVICE
+ *   memory, rewritten by the host between graph replays, so a replay picks up the scheduler's lr / beta1 and the update's alpha.
+ *   alpha_host is the value the host uploads there next (at a capture: the first one) and is only checked, since the device value
+ *   cannot be.  With ema null, alpha may be null and alpha_host is ignored. */
 #define CVK_ADAMW_ARG_RECORDS 16
 typedef struct cvk_adamw_range {
     int64_t offset;              /* first element of the range in the flat buffers */
@@ -570,25 +577,29 @@ typedef struct cvk_adamw_range {
     int32_t block0;              /* first workgroup of the range (cvk_adamw_plan_ranges) */
 } cvk_adamw_range;
 int cvk_adamw_plan_ranges(cvk_adamw_range* ranges, int nranges, int64_t n, int nhyper);
-int cvk_adamw_step_ranges(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const cvk_adamw_range* ranges,
-                          int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper, void* stream);
-int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const cvk_adamw_range* ranges,
-                              int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper, void* stream);
+int cvk_adamw_step_ranges(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                          const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                          const float* record, float alpha, void* stream);
+int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                              const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
+                              const float* record, const float* alpha, float alpha_host, void* stream);
 
 /* ---- the per-iteration training log (train.py:133-143 print of loss / lr / Beta1; utils.visulaize_lastlayer utils.py:33-36) -------
- * One single-workgroup launch appends the row [loss, lr, beta1, ||gw||_2, ||gb||_2] (fp32) to a DEVICE ring of `capacity` rows of 5
- * floats at row counter % capacity, then increments *counter (DEVICE int64).  loss: DEVICE scalar; hyper: DEVICE record (lr and
- * beta1 of the step); gw / gb: DEVICE gradients of nw / nb floats.  The norms are sums of squares in fp64 in a fixed order (no
- * atomics: bitwise reproducible), rounded to fp32 after the square root.  No allocation and no synchronisation: the call can be
- * captured in a graph. */
-int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb, float* ring,
-                 int capacity, int64_t* counter, void* stream);
+ * One single-workgroup launch appends the row [loss, lr, beta1, ||gw||_2, ||gb||_2] (fp32) to a DEVICE ring of `capacity` rows at row
+ * counter % capacity, then increments *counter (DEVICE int64).  loss: DEVICE scalar; hyper: DEVICE record (lr and beta1 of the step);
+ * gw / gb: DEVICE gradients of nw / nb floats.  record (DEVICE, may be null): the {total_norm, clip_coef} record of cvk_grad_norm.
+ * Null: rows of 5 floats.  Non-null: rows of 7 floats, the five columns, then record[0] and record[1].  The norms are sums of squares
+ * in fp64 in a fixed order (no atomics: bitwise reproducible), rounded to fp32 after the square root.  No allocation and no
+ * synchronisation: the call can be captured in a graph. */
+int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb, const float* record,
+                 float* ring, int capacity, int64_t* counter, void* stream);
 
 /* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) fused into the AdamW step ------------------------------------
  * The norm of the flat gradient buffer over a table of EXACT parameter segments, as a device record {total_norm, clip_coef} that the
- * clipped AdamW launches, the in-place scale and the log row read.  The flat gradient buffer is uninitialised between its segments
- * (16-byte alignment padding, frozen parameters): the table lists [offset, offset + length) per parameter that has a gradient,
- * neighbours merged only where no padding float lies between them.  No element outside the table is read.
+ * AdamW launches (cvk_adamw_step_ranges, cvk_adamw_step_ranges_dev), the in-place scale and the log row (cvk_step_log) read.  The
+ * flat gradient buffer is uninitialised between its segments (16-byte alignment padding, frozen parameters): the table lists
+ * [offset, offset + length) per parameter that has a gradient, neighbours merged only where no padding float lies between them.  No
+ * element outside the table is read.
  *
  * cvk_clip_coef (host function): torch's clip coefficient in fp32, max_norm / (total_norm + 1e-6f) clamped to at most 1 the way
  *   torch.clamp(max=1) clamps: a NaN norm gives NaN, an infinite norm gives 0.  The finish kernel evaluates the same expression.
@@ -601,11 +612,7 @@ int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* g
  *   bitwise reproducible from run to run, eager or captured.  partials: DEVICE, nblocks doubles.  record: DEVICE, 2 floats.
  *   max_norm >= 0; norm_type 2 or INFINITY, anything else is refused.
  * cvk_grad_scale: grad[i] *= record[1] over the same table, in place (what torch's clip_grad_norm_ leaves in .grad); a coefficient
- *   of exactly 1 leaves the buffer untouched.
- * cvk_adamw_step_ranges_clip / _clip_dev: cvk_adamw_step_ranges / _dev with every gradient element multiplied by record[1] on its way
- *   into the update (one more operand of the same expression list: with a coefficient of 1.0f the step is bitwise the unclipped one).
- *   The gradient buffer is not rewritten.
- * cvk_step_log_norm: cvk_step_log with rows of 7 floats: the five columns, then record[0] and record[1]. */
+ *   of exactly 1 leaves the buffer untouched. */
 typedef struct cvk_norm_segment {
     int64_t offset;              /* first element of the segment in the flat gradient buffer */
     int64_t length;              /* elements, > 0 */
@@ -618,30 +625,6 @@ int cvk_grad_norm(const float* grad, int64_t n, const cvk_norm_segment* segments
                   float max_norm, double* partials, float* record, void* stream);
 int cvk_grad_scale(float* grad, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks, const float* record,
                    void* stream);
-int cvk_adamw_step_ranges_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                               const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                               const float* record, void* stream);
-int cvk_adamw_step_ranges_clip_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                   const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                                   const float* record, void* stream);
-int cvk_step_log_norm(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb,
-                      const float* record, float* ring, int capacity, int64_t* counter, void* stream);
-
-/* ---- an exponential moving average of the weights inside the AdamW step (cvk.FlatAdamW(net, ema_decay=...)) ---------------------------
- * cvk_adamw_step_ranges_ema / _ema_dev: cvk_adamw_step_ranges / _dev with one more buffer `ema` (fp32, laid out like param).  The thread
- * that has stored the new parameter value p_new of an element goes on with it in the register: ema[i] += alpha * (p_new - ema[i]); param
- * is not read again.  param, exp_avg and exp_avg_sq come out bitwise as from cvk_adamw_step_ranges (record null) or
- * cvk_adamw_step_ranges_clip (record non-null: the {total_norm, clip_coef} record of cvk_grad_norm, as there).  Elements outside every
- * range are neither read nor written in ema either.  0 < alpha <= 1 (alpha = 1 - decay).
- *   _ema: records as kernel arguments (nhyper <= CVK_ADAMW_ARG_RECORDS, host array), alpha as an argument.
- *   _ema_dev: records and alpha (one float) in DEVICE memory, rewritten by the host between graph replays; alpha_host is the value the host
- *     uploads there next (at a capture: the first one) and is only checked, since the device value cannot be. */
-int cvk_adamw_step_ranges_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
-                              const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                              const float* record, float alpha, void* stream);
-int cvk_adamw_step_ranges_ema_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
-                                  const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                                  const float* record, const float* alpha, float alpha_host, void* stream);
 
 /* ---- gradient accumulation over micro-batches (GradAccumulator) -------------------------------------------------------------------
  * One streaming launch over a planned segment table (cvk_grad_norm_plan: the same table type and the same workgroup walk as the norm)

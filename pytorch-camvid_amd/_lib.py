@@ -229,20 +229,14 @@ SIGNATURES = {
     "cvk_zero_frame_bf16": (c_int, [ViewH, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "cvk_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_float, c_float, c_int, c_vp]),
     "cvk_adamw_hyper_fill": (c_int, [c_float, c_float, c_float, c_float, c_float, c_int, c_vp]),   # out: HOST AdamwHyper
-    "cvk_adamw_step_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "cvk_adamw_plan_ranges": (c_int, [c_vp, c_int, c_i64, c_int]),                                   # HOST table (AdamwRange)
-    "cvk_adamw_step_ranges": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp]),   # HOST AdamwHyper array
-    "cvk_adamw_step_ranges_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
-    "cvk_step_log": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp]),
+    "cvk_adamw_step_ranges": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_float, c_vp]),   # HOST AdamwHyper array
+    "cvk_adamw_step_ranges_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_float, c_vp]),
+    "cvk_step_log": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "cvk_clip_coef": (c_float, [c_float, c_float]),                                                  # host function
     "cvk_grad_norm_plan": (c_int, [c_vp, c_int, c_i64]),                                             # HOST table (NormSegment)
     "cvk_grad_norm": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_float, c_float, c_vp, c_vp, c_vp]),
     "cvk_grad_scale": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_vp]),
-    "cvk_adamw_step_ranges_clip": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),   # HOST AdamwHyper array
-    "cvk_adamw_step_ranges_clip_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
-    "cvk_step_log_norm": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
-    "cvk_adamw_step_ranges_ema": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_float, c_vp]),   # HOST AdamwHyper array
-    "cvk_adamw_step_ranges_ema_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_float, c_vp]),
     "cvk_grad_accumulate": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_float, c_vp]),
 }
 
@@ -265,8 +259,8 @@ class AdamwRange(ctypes.Structure):     # include/cvk.h cvk_adamw_range
 
 
 ADAMW_ARG_RECORDS = 16                  # include/cvk.h CVK_ADAMW_ARG_RECORDS: records cvk_adamw_step_ranges takes as kernel arguments
-STEP_LOG_COLUMNS = 5                    # cvk_step_log row: loss, lr, beta1, ||gw||_2, ||gb||_2
-STEP_LOG_NORM_COLUMNS = 7               # cvk_step_log_norm row: the five, then total_norm and clip_coef of the step
+STEP_LOG_COLUMNS = 5                    # cvk_step_log row without a clip record: loss, lr, beta1, ||gw||_2, ||gb||_2
+STEP_LOG_NORM_COLUMNS = 7               # cvk_step_log row with one: the five, then total_norm and clip_coef of the step
 
 
 class NormSegment(ctypes.Structure):    # include/cvk.h cvk_norm_segment

@@ -30,13 +30,11 @@ only); what trains may not: a requires_grad flip or a change of a block's BatchN
 set_split_operands, so the same code serves all three.  There is no state_dict(): take checkpoints between windows, where the
 accumulator holds nothing.  `steps=1` or `detach()` restores the executor's behaviour without an accumulator exactly (same launches,
 same buffers)."""
-import ctypes
-
 import torch
 
 from . import _lib
 from ._lib import check
-from .optim import norm_segments
+from .optim import norm_segments, plan_segments
 
 
 def fold_segments(plan, params, goffs):
@@ -91,11 +89,7 @@ def plan_table(segments, n):
     """(host NormSegment array with its workgroups assigned, workgroup count) of a fold over `segments` of a buffer of n floats."""
     if not segments:
         raise RuntimeError("GradAccumulator: no parameter of the network trains")
-    arr = (_lib.NormSegment * len(segments))(*[_lib.NormSegment(o, m, 0, 0) for o, m in segments])
-    nb = _lib.load().cvk_grad_norm_plan(ctypes.addressof(arr), len(segments), n)
-    if nb <= 0:
-        check(nb if nb < 0 else -1, "cvk_grad_norm_plan")
-    return arr, nb
+    return plan_segments(segments, n)
 
 
 class _Fold:

@@ -807,11 +807,11 @@ __global__ __launch_bounds__(256) void k_confusion(const int64_t* __restrict__ p
         if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
 }
 
-// One AdamW element update (torch.optim.AdamW, decoupled weight decay).  Shared by k_adamw (scalars as kernel arguments),
-// k_adamw_dev (scalars from a device record) and the range-table kernels: one expression list, so they cannot round differently.
-// coef scales the gradient on its way in (global-norm clipping, cvk_adamw_step_ranges_clip*); the unclipped kernels pass the
-// literal 1.f, and x * 1.f is x.
-// Returns the parameter value it stored, for the EMA form that goes on with it in the register.
+// One AdamW element update (torch.optim.AdamW, decoupled weight decay).  Shared by k_adamw (scalars as kernel arguments) and the
+// range-table kernel: one expression list, so they cannot round differently.
+// coef scales the gradient on its way in (global-norm clipping: the record of cvk_grad_norm); an unclipped step passes 1.f, and
+// x * 1.f is x.
+// Returns the parameter value it stored, for the EMA that goes on with it in the register.
 __device__ __forceinline__ float adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                               float* __restrict__ v, int64_t i, float lr, float b1, float b2, float eps, float wd,
                                               float bc1, float bc2_sqrt, float coef) {
@@ -833,28 +833,37 @@ __global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, floa
         adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, 1.f);
 }
 
-// The captured-graph form: the scalars come from a device record the host rewrites before every replay (uniform loads,
-// once per thread, before the loop).
-__global__ void k_adamw_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            int64_t n, const cvk_adamw_hyper* __restrict__ hyper) {
-    const float lr = hyper->lr, b1 = hyper->beta1, b2 = hyper->beta2, eps = hyper->eps, wd = hyper->weight_decay;
-    const float bc1 = hyper->bc1, bc2_sqrt = hyper->bc2_sqrt;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, 1.f);
-}
-
-// AdamW over a range table (cvk_adamw_step_ranges*): workgroup b serves the range whose block0 is the last one <= b (a uniform binary
-// search over the table) and strides over it with that range's workgroups.  Both entry points run this body; `hyper` points at the
-// kernel-argument records (eager) or at device memory (graph replays).  Ranges outside [0, n) or with a record index outside [0, nhyper)
-// are skipped (cvk_adamw_plan_ranges refuses them on the host).
+// AdamW over a range table (cvk_adamw_step_ranges, cvk_adamw_step_ranges_dev): workgroup b serves the range whose block0 is the last one
+// <= b (a uniform binary search over the table) and strides over it with that range's workgroups.  Ranges outside [0, n) or with a record
+// index outside [0, nhyper) are skipped (cvk_adamw_plan_ranges refuses them on the host).  One kernel template, two compile-time choices:
+//   SRC: where the hyper records and the EMA's alpha come from.  AdamwArgSource: kernel arguments (eager).  AdamwDevSource: device memory
+//        the host rewrites between graph replays (uniform loads, once per thread, before the loop).
+//   EMA: the thread that has stored an element's new value moves the average towards it, ema += alpha * (p_new - ema), from the
+//        register: param is not read again, and elements outside every range are not touched in ema either.  Without it `ema` and
+//        alpha are never read and the loop is the plain update.
+// `clip` is the {total_norm, clip_coef} record of cvk_grad_norm, read once per thread, or null: coefficient 1.f.
 struct AdamwArgRecords {
     cvk_adamw_hyper r[CVK_ADAMW_ARG_RECORDS];
 };
 
-__device__ __forceinline__ void adamw_ranges_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
-                                                  const cvk_adamw_hyper* __restrict__ hyper, int nhyper,
-                                                  const float* __restrict__ clip) {
+struct AdamwArgSource {
+    AdamwArgRecords recs;
+    float a;
+    __device__ __forceinline__ const cvk_adamw_hyper* records() const { return recs.r; }
+    __device__ __forceinline__ float alpha() const { return a; }
+};
+
+struct AdamwDevSource {
+    const cvk_adamw_hyper* recs;
+    const float* a;
+    __device__ __forceinline__ const cvk_adamw_hyper* records() const { return recs; }
+    __device__ __forceinline__ float alpha() const { return *a; }
+};
+
+template <class SRC, bool EMA>
+__global__ void k_adamw_ranges(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                               float* __restrict__ ema, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, const SRC src,
+                               int nhyper, const float* __restrict__ clip) {
     const int b = blockIdx.x;
     int lo = 0, hi = nr - 1;
     while (lo < hi) {
@@ -866,80 +875,23 @@ __device__ __forceinline__ void adamw_ranges_body(float* __restrict__ p, const f
     const int hx = rt[lo].hyper, b0 = rt[lo].block0;
     const int nb = (lo + 1 < nr ? rt[lo + 1].block0 : (int)gridDim.x) - b0;
     if (off < 0 || len <= 0 || off + len > n || hx < 0 || hx >= nhyper || nb <= 0 || b < b0) return;
-    const float lr = hyper[hx].lr, b1 = hyper[hx].beta1, b2 = hyper[hx].beta2, eps = hyper[hx].eps, wd = hyper[hx].weight_decay;
-    const float bc1 = hyper[hx].bc1, bc2_sqrt = hyper[hx].bc2_sqrt;
-    const float coef = clip != nullptr ? clip[1] : 1.f;           // the {total_norm, clip_coef} record of cvk_grad_norm, once per thread
-    for (int64_t i = off + (int64_t)(b - b0) * blockDim.x + threadIdx.x; i < off + len; i += (int64_t)nb * blockDim.x)
-        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, coef);
-}
-
-__global__ void k_adamw_ranges(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                               const cvk_adamw_range* __restrict__ rt, int nr, AdamwArgRecords recs, int nhyper) {
-    adamw_ranges_body(p, g, m, v, n, rt, nr, recs.r, nhyper, nullptr);
-}
-
-__global__ void k_adamw_ranges_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                   int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, const cvk_adamw_hyper* __restrict__ hyper,
-                                   int nhyper) {
-    adamw_ranges_body(p, g, m, v, n, rt, nr, hyper, nhyper, nullptr);
-}
-
-// The clipped forms (cvk_adamw_step_ranges_clip*): the same body, the gradient scaled by the clip coefficient of the device record.
-__global__ void k_adamw_ranges_clip(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                    int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, AdamwArgRecords recs, int nhyper,
-                                    const float* __restrict__ clip) {
-    adamw_ranges_body(p, g, m, v, n, rt, nr, recs.r, nhyper, clip);
-}
-
-__global__ void k_adamw_ranges_clip_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                        int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
-                                        const cvk_adamw_hyper* __restrict__ hyper, int nhyper, const float* __restrict__ clip) {
-    adamw_ranges_body(p, g, m, v, n, rt, nr, hyper, nhyper, clip);
-}
-
-// The EMA forms (cvk_adamw_step_ranges_ema*): the walk of adamw_ranges_body and the same adamw_update, then the thread moves the average
-// towards the parameter value it has just stored, ema += alpha * (p_new - ema), from the register: param is not read again.  Elements
-// outside every range are not touched in ema either.  `clip` may be null (coefficient 1.f), so clipped and unclipped steps share a kernel.
-__device__ __forceinline__ void adamw_ranges_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                      float* __restrict__ v, float* __restrict__ ema, int64_t n,
-                                                      const cvk_adamw_range* __restrict__ rt, int nr,
-                                                      const cvk_adamw_hyper* __restrict__ hyper, int nhyper,
-                                                      const float* __restrict__ clip, float alpha) {
-    const int b = blockIdx.x;
-    int lo = 0, hi = nr - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (rt[mid].block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    const int64_t off = rt[lo].offset, len = rt[lo].length;
-    const int hx = rt[lo].hyper, b0 = rt[lo].block0;
-    const int nb = (lo + 1 < nr ? rt[lo + 1].block0 : (int)gridDim.x) - b0;
-    if (off < 0 || len <= 0 || off + len > n || hx < 0 || hx >= nhyper || nb <= 0 || b < b0) return;
+    const cvk_adamw_hyper* __restrict__ hyper = src.records();
     const float lr = hyper[hx].lr, b1 = hyper[hx].beta1, b2 = hyper[hx].beta2, eps = hyper[hx].eps, wd = hyper[hx].weight_decay;
     const float bc1 = hyper[hx].bc1, bc2_sqrt = hyper[hx].bc2_sqrt;
     const float coef = clip != nullptr ? clip[1] : 1.f;
+    float alpha = 0.f;
+    if constexpr (EMA) alpha = src.alpha();
     for (int64_t i = off + (int64_t)(b - b0) * blockDim.x + threadIdx.x; i < off + len; i += (int64_t)nb * blockDim.x) {
         const float pi = adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, coef);
-        const float e = ema[i];
-        ema[i] = e + alpha * (pi - e);
+        if constexpr (EMA) {
+            const float e = ema[i];
+            ema[i] = e + alpha * (pi - e);
+        }
     }
 }
 
-__global__ void k_adamw_ranges_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                   float* __restrict__ ema, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
-                                   AdamwArgRecords recs, int nhyper, const float* __restrict__ clip, float alpha) {
-    adamw_ranges_ema_body(p, g, m, v, ema, n, rt, nr, recs.r, nhyper, clip, alpha);
-}
-
-__global__ void k_adamw_ranges_ema_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                       float* __restrict__ ema, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr,
-                                       const cvk_adamw_hyper* __restrict__ hyper, int nhyper, const float* __restrict__ clip,
-                                       const float* __restrict__ alpha) {
-    adamw_ranges_ema_body(p, g, m, v, ema, n, rt, nr, hyper, nhyper, clip, *alpha);
-}
-
-// One row [loss, lr, beta1, ||gw||_2, ||gb||_2] of the per-iteration log into ring[(*counter % capacity) * 5 ..], then ++*counter.
+// One row [loss, lr, beta1, ||gw||_2, ||gb||_2] of the per-iteration log, with `rec` (the {total_norm, clip_coef} record of cvk_grad_norm)
+// followed by its two floats, into ring[(*counter % capacity) * cols ..] (cols = 5 or 7), then ++*counter.
 // One workgroup of 256 threads: thread t sums the squares of elements t, t + 256, ... in fp64, then a fixed tree over LDS.
 constexpr int STEP_LOG_THREADS = 256;
 
@@ -960,43 +912,27 @@ __device__ __forceinline__ double block_sum_sq_f64(const float* __restrict__ x, 
     return r;
 }
 
-// COLS = 5: cvk_step_log; COLS = 7: cvk_step_log_norm, the row ends in the {total_norm, clip_coef} record of cvk_grad_norm.
-template <int COLS>
-__device__ __forceinline__ void step_log_body(const float* __restrict__ loss, const cvk_adamw_hyper* __restrict__ hyper,
-                                              const float* __restrict__ gw, int nw, const float* __restrict__ gb, int nb,
-                                              const float* __restrict__ rec, float* __restrict__ ring, int capacity,
-                                              int64_t* __restrict__ counter) {
+__global__ __launch_bounds__(STEP_LOG_THREADS) void k_step_log(const float* __restrict__ loss, const cvk_adamw_hyper* __restrict__ hyper,
+                                                               const float* __restrict__ gw, int nw, const float* __restrict__ gb, int nb,
+                                                               const float* __restrict__ rec, float* __restrict__ ring, int capacity,
+                                                               int64_t* __restrict__ counter) {
     __shared__ double red[STEP_LOG_THREADS];
     const double sw = block_sum_sq_f64(gw, nw, red);
     const double sb = block_sum_sq_f64(gb, nb, red);
     if (threadIdx.x == 0) {
         const int64_t c = *counter;
-        float* row = ring + (c % capacity) * COLS;
+        float* row = ring + (c % capacity) * (rec != nullptr ? 7 : 5);
         row[0] = *loss;
         row[1] = hyper->lr;
         row[2] = hyper->beta1;
         row[3] = (float)sqrt(sw);
         row[4] = (float)sqrt(sb);
-        if (COLS == 7) {
+        if (rec != nullptr) {
             row[5] = rec[0];
             row[6] = rec[1];
         }
         *counter = c + 1;
     }
-}
-
-__global__ __launch_bounds__(STEP_LOG_THREADS) void k_step_log(const float* __restrict__ loss, const cvk_adamw_hyper* __restrict__ hyper,
-                                                               const float* __restrict__ gw, int nw, const float* __restrict__ gb, int nb,
-                                                               float* __restrict__ ring, int capacity, int64_t* __restrict__ counter) {
-    step_log_body<5>(loss, hyper, gw, nw, gb, nb, nullptr, ring, capacity, counter);
-}
-
-__global__ __launch_bounds__(STEP_LOG_THREADS) void k_step_log_norm(const float* __restrict__ loss,
-                                                                    const cvk_adamw_hyper* __restrict__ hyper,
-                                                                    const float* __restrict__ gw, int nw, const float* __restrict__ gb,
-                                                                    int nb, const float* __restrict__ rec, float* __restrict__ ring,
-                                                                    int capacity, int64_t* __restrict__ counter) {
-    step_log_body<7>(loss, hyper, gw, nw, gb, nb, rec, ring, capacity, counter);
 }
 
 // ---- global-norm gradient clipping (cvk_grad_norm, cvk_grad_scale) -----------------------------------------------------------------
@@ -1011,7 +947,7 @@ constexpr int NORM_THREADS = 256;
 constexpr int NORM_UNROLL = 4;                  // independent 16-byte loads per lane and trip
 constexpr int NORM_MAX_BLOCKS = 2048;           // 8 workgroups per CU: a grid-stride streaming read
 
-// The workgroup's segment (uniform binary search over block0, as adamw_ranges_body) and its place among the segment's workgroups.
+// The workgroup's segment (uniform binary search over block0, as k_adamw_ranges) and its place among the segment's workgroups.
 // False when the table entry is unusable (cvk_grad_norm_plan refuses such a table on the host).
 __device__ __forceinline__ bool norm_segment_of(const cvk_norm_segment* __restrict__ st, int ns, int64_t n, int64_t* off, int64_t* len,
                                                 int* rank, int* nb) {
@@ -1575,16 +1511,27 @@ extern "C" int cvk_adamw_hyper_fill(float lr, float beta1, float beta2, float ep
     return CVK_OK;
 }
 
-extern "C" int cvk_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                  const cvk_adamw_hyper* hyper, void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && hyper, "cvk_adamw_step_dev: null pointer");
-    CVK_CHECK_ARG(n > 0, "cvk_adamw_step_dev: bad arguments");
-    hipLaunchKernelGGL(k_adamw_dev, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, hyper);
-    CVK_LAUNCH_RETURN("cvk_adamw_step_dev");
+// The planners' shared step: every entry's first workgroup (block0) and the total.  An entry of `length` elements gets one workgroup per
+// `per` elements, at most its share of the budget (one per `per` elements of the `total`, at most `cap`, shared in proportion to the
+// lengths), at least one.  Returns the workgroup count, or -1 as soon as it reaches 2^30.
+template <class ENTRY>
+static int64_t plan_block0(ENTRY* e, int count, int64_t total, int64_t per, int64_t cap) {
+    int64_t budget = (total + per - 1) / per;
+    if (budget > cap) budget = cap;
+    int64_t blocks = 0;
+    for (int r = 0; r < count; ++r) {
+        int64_t nb = (e[r].length + per - 1) / per;
+        const int64_t share = (int64_t)(((__int128)budget * e[r].length + total - 1) / total);
+        if (nb > share) nb = share;
+        if (nb < 1) nb = 1;
+        e[r].block0 = (int32_t)blocks;
+        blocks += nb;
+        if (blocks >= (1LL << 30)) return -1;
+    }
+    return blocks;
 }
 
-// Workgroups per range: as many as k_adamw would give the range's elements alone (one per 256, at most 8192 in all, shared in proportion to
-// the lengths), at least one.
+// Workgroups per range: as many as k_adamw would give the range's elements alone (one per 256, at most 8192 in all).
 extern "C" int cvk_adamw_plan_ranges(cvk_adamw_range* ranges, int nranges, int64_t n, int nhyper) {
     CVK_CHECK_ARG(ranges && nranges > 0 && n > 0 && nhyper > 0, "cvk_adamw_plan_ranges: bad arguments");
     int64_t total = 0;
@@ -1595,65 +1542,64 @@ extern "C" int cvk_adamw_plan_ranges(cvk_adamw_range* ranges, int nranges, int64
         CVK_CHECK_ARG(e.hyper >= 0 && e.hyper < nhyper, "cvk_adamw_plan_ranges: range %d names record %d of %d", r, e.hyper, nhyper);
         total += e.length;
     }
-    const int64_t budget = adamw_blocks(total);
-    int64_t blocks = 0;
-    for (int r = 0; r < nranges; ++r) {
-        int64_t nb = (ranges[r].length + 255) / 256;
-        const int64_t share = (budget * ranges[r].length + total - 1) / total;
-        if (nb > share) nb = share;
-        if (nb < 1) nb = 1;
-        ranges[r].block0 = (int32_t)blocks;
-        blocks += nb;
-    }
-    CVK_CHECK_ARG(blocks < (1LL << 30), "cvk_adamw_plan_ranges: too many workgroups");
+    const int64_t blocks = plan_block0(ranges, nranges, total, 256, 8192);
+    CVK_CHECK_ARG(blocks >= 0, "cvk_adamw_plan_ranges: too many workgroups");
     return (int)blocks;
 }
 
-extern "C" int cvk_adamw_step_ranges(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+// One launch of the range kernel: SRC and EMA pick the instantiation, the argument list is the same for all four.
+template <class SRC>
+static void adamw_ranges_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                const cvk_adamw_range* ranges, int nranges, int nblocks, const SRC& src, int nhyper, const float* record,
+                                void* stream) {
+    if (ema != nullptr)
+        hipLaunchKernelGGL((k_adamw_ranges<SRC, true>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                           ema, n, ranges, nranges, src, nhyper, record);
+    else
+        hipLaunchKernelGGL((k_adamw_ranges<SRC, false>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                           ema, n, ranges, nranges, src, nhyper, record);
+}
+
+extern "C" int cvk_adamw_step_ranges(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
                                      const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                                     void* stream) {
+                                     const float* record, float alpha, void* stream) {
     CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper, "cvk_adamw_step_ranges: null pointer");
+    CVK_CHECK_ARG(!ema || (alpha > 0.f && alpha <= 1.f), "cvk_adamw_step_ranges: alpha %g outside (0, 1]", (double)alpha);
     CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
                   "cvk_adamw_step_ranges: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
-    AdamwArgRecords recs = {};
-    for (int i = 0; i < nhyper; ++i) recs.r[i] = hyper[i];
-    hipLaunchKernelGGL(k_adamw_ranges, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, ranges, nranges,
-                       recs, nhyper);
+    AdamwArgSource src = {};
+    for (int i = 0; i < nhyper; ++i) src.recs.r[i] = hyper[i];
+    src.a = alpha;
+    adamw_ranges_launch(param, grad, exp_avg, exp_avg_sq, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
     CVK_LAUNCH_RETURN("cvk_adamw_step_ranges");
 }
 
-extern "C" int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+// alpha (DEVICE, one float) is what the kernel reads, rewritten by the host between graph replays; alpha_host is the value the host is
+// about to upload there (at a capture: the first one), checked here because the device value cannot be.
+extern "C" int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
                                          const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                                         void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper, "cvk_adamw_step_ranges_dev: null pointer");
+                                         const float* record, const float* alpha, float alpha_host, void* stream) {
+    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper && (!ema || alpha), "cvk_adamw_step_ranges_dev: null pointer");
+    CVK_CHECK_ARG(!ema || (alpha_host > 0.f && alpha_host <= 1.f), "cvk_adamw_step_ranges_dev: alpha %g outside (0, 1]", (double)alpha_host);
     CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_adamw_step_ranges_dev: bad arguments");
-    hipLaunchKernelGGL(k_adamw_ranges_dev, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, ranges,
-                       nranges, hyper, nhyper);
+    const AdamwDevSource src = {hyper, alpha};
+    adamw_ranges_launch(param, grad, exp_avg, exp_avg_sq, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
     CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_dev");
 }
 
-extern "C" int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb, float* ring,
-                            int capacity, int64_t* counter, void* stream) {
+// record (the {total_norm, clip_coef} record of cvk_grad_norm) may be null: rows of 5 floats; with it, rows of 7.
+extern "C" int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb,
+                            const float* record, float* ring, int capacity, int64_t* counter, void* stream) {
     CVK_CHECK_ARG(loss && hyper && gw && gb && ring && counter, "cvk_step_log: null pointer");
     CVK_CHECK_ARG(nw > 0 && nb > 0 && capacity > 0, "cvk_step_log: bad arguments");
-    hipLaunchKernelGGL(k_step_log, dim3(1), dim3(STEP_LOG_THREADS), 0, (hipStream_t)stream, loss, hyper, gw, nw, gb, nb, ring, capacity,
-                       counter);
-    CVK_LAUNCH_RETURN("cvk_step_log");
-}
-
-extern "C" int cvk_step_log_norm(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb,
-                                 const float* record, float* ring, int capacity, int64_t* counter, void* stream) {
-    CVK_CHECK_ARG(loss && hyper && gw && gb && record && ring && counter, "cvk_step_log_norm: null pointer");
-    CVK_CHECK_ARG(nw > 0 && nb > 0 && capacity > 0, "cvk_step_log_norm: bad arguments");
-    hipLaunchKernelGGL(k_step_log_norm, dim3(1), dim3(STEP_LOG_THREADS), 0, (hipStream_t)stream, loss, hyper, gw, nw, gb, nb, record, ring,
+    hipLaunchKernelGGL(k_step_log, dim3(1), dim3(STEP_LOG_THREADS), 0, (hipStream_t)stream, loss, hyper, gw, nw, gb, nb, record, ring,
                        capacity, counter);
-    CVK_LAUNCH_RETURN("cvk_step_log_norm");
+    CVK_LAUNCH_RETURN("cvk_step_log");
 }
 
 extern "C" float cvk_clip_coef(float max_norm, float total_norm) { return clip_coef_f32(max_norm, total_norm); }
 
-// Workgroups per segment: one per NORM_THREADS * NORM_UNROLL 16-byte vectors, at most NORM_MAX_BLOCKS in all (shared in proportion to
-// the lengths), at least one.
+// Workgroups per segment: one per NORM_THREADS * NORM_UNROLL 16-byte vectors, at most NORM_MAX_BLOCKS in all.
 extern "C" int cvk_grad_norm_plan(cvk_norm_segment* segments, int nsegments, int64_t n) {
     CVK_CHECK_ARG(segments, "cvk_grad_norm_plan: null pointer");
     CVK_CHECK_ARG(nsegments > 0 && n > 0, "cvk_grad_norm_plan: empty table or buffer (%d segments, %lld elements)", nsegments, (long long)n);
@@ -1664,19 +1610,8 @@ extern "C" int cvk_grad_norm_plan(cvk_norm_segment* segments, int nsegments, int
                       "+%lld) outside the buffer of %lld elements", r, (long long)e.offset, (long long)e.length, (long long)n);
         total += e.length;
     }
-    const int64_t per = (int64_t)NORM_THREADS * NORM_UNROLL * 4;
-    int64_t budget = (total + per - 1) / per;
-    if (budget > NORM_MAX_BLOCKS) budget = NORM_MAX_BLOCKS;
-    int64_t blocks = 0;
-    for (int r = 0; r < nsegments; ++r) {
-        int64_t nb = (segments[r].length + per - 1) / per;
-        const int64_t share = (int64_t)(((__int128)budget * segments[r].length + total - 1) / total);
-        if (nb > share) nb = share;
-        if (nb < 1) nb = 1;
-        segments[r].block0 = (int32_t)blocks;
-        blocks += nb;
-        CVK_CHECK_ARG(blocks < (1LL << 30), "cvk_grad_norm_plan: too many workgroups");
-    }
+    const int64_t blocks = plan_block0(segments, nsegments, total, (int64_t)NORM_THREADS * NORM_UNROLL * 4, NORM_MAX_BLOCKS);
+    CVK_CHECK_ARG(blocks >= 0, "cvk_grad_norm_plan: too many workgroups");
     return (int)blocks;
 }
 
@@ -1731,57 +1666,6 @@ extern "C" int cvk_grad_accumulate(float* dst, const float* src, int64_t n, cons
     else
         hipLaunchKernelGGL(k_grad_accumulate<2>, grid, block, 0, (hipStream_t)stream, dst, src, n, segments, nsegments, scale);
     CVK_LAUNCH_RETURN("cvk_grad_accumulate");
-}
-
-extern "C" int cvk_adamw_step_ranges_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                          const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                                          const float* record, void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper && record, "cvk_adamw_step_ranges_clip: null pointer");
-    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
-                  "cvk_adamw_step_ranges_clip: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
-    AdamwArgRecords recs = {};
-    for (int i = 0; i < nhyper; ++i) recs.r[i] = hyper[i];
-    hipLaunchKernelGGL(k_adamw_ranges_clip, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, ranges,
-                       nranges, recs, nhyper, record);
-    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_clip");
-}
-
-extern "C" int cvk_adamw_step_ranges_clip_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                              const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper,
-                                              int nhyper, const float* record, void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper && record, "cvk_adamw_step_ranges_clip_dev: null pointer");
-    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_adamw_step_ranges_clip_dev: bad arguments");
-    hipLaunchKernelGGL(k_adamw_ranges_clip_dev, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
-                       ranges, nranges, hyper, nhyper, record);
-    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_clip_dev");
-}
-
-// The EMA forms.  `record` may be null: an unclipped step.
-extern "C" int cvk_adamw_step_ranges_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
-                                         const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                                         const float* record, float alpha, void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ema && ranges && hyper, "cvk_adamw_step_ranges_ema: null pointer");
-    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
-                  "cvk_adamw_step_ranges_ema: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
-    CVK_CHECK_ARG(alpha > 0.f && alpha <= 1.f, "cvk_adamw_step_ranges_ema: alpha %g outside (0, 1]", (double)alpha);
-    AdamwArgRecords recs = {};
-    for (int i = 0; i < nhyper; ++i) recs.r[i] = hyper[i];
-    hipLaunchKernelGGL(k_adamw_ranges_ema, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, ema, n, ranges,
-                       nranges, recs, nhyper, record, alpha);
-    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_ema");
-}
-
-// alpha (DEVICE, one float) is what the kernel reads, rewritten by the host between graph replays; alpha_host is the value the host is
-// about to upload there (at a capture: the first one), checked here because the device value cannot be.
-extern "C" int cvk_adamw_step_ranges_ema_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
-                                             const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper,
-                                             int nhyper, const float* record, const float* alpha, float alpha_host, void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ema && ranges && hyper && alpha, "cvk_adamw_step_ranges_ema_dev: null pointer");
-    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_adamw_step_ranges_ema_dev: bad arguments");
-    CVK_CHECK_ARG(alpha_host > 0.f && alpha_host <= 1.f, "cvk_adamw_step_ranges_ema_dev: alpha %g outside (0, 1]", (double)alpha_host);
-    hipLaunchKernelGGL(k_adamw_ranges_ema_dev, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, ema, n,
-                       ranges, nranges, hyper, nhyper, record, alpha);
-    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_ema_dev");
 }
 
 // ---- library-wide pieces ---------------------------------------------------------------------------------------

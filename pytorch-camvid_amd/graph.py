@@ -26,8 +26,8 @@ group and step count, cvk_adamw_step_ranges_dev; the log row reads param_groups[
 captured optimizer as it drives the eager one.  A FlatAdamW with `max_grad_norm` is captured with its norm reduction and finish between
 backward and the AdamW launch (after the stream's waits for the all-reduces: every rank reduces the same averaged buffer, so no extra
 collective), and the log rows gain the global norm and the clip coefficient; `max_grad_norm` / `norm_type` are baked into the graph.
-A FlatAdamW with `ema_decay` is captured with the EMA form of the step (cvk_adamw_step_ranges_ema_dev): the update's alpha travels with the
-hyper records, one float behind them, so the decay may change between replays and warm-up changes it on every one; whether an EMA exists
+A FlatAdamW with `ema_decay` is captured with its `ema` buffer in the same launch: the update's alpha travels with the hyper records, one
+float behind them, so the decay may change between replays and warm-up changes it on every one; whether an EMA exists
 is baked in.  Under `accumulator=` the average takes one update per window; under data parallel every rank averages the same parameters.
 Frozen parameters (requires_grad False, BatchNorm children in eval mode) are captured as
 they are when the GraphedStep is built; replay() refuses to run after any of that changes:
@@ -199,27 +199,13 @@ class GraphedStep:
             if self._norm_plan is not None:
                 # reduction + finish into the optimizer's {total_norm, clip_coef} record, then the AdamW launch that scales by it
                 self._norm_plan.norm(self._gflat.data_ptr(), self._clip[1], self._clip[0], opt._clip_rec, stream)
+            # alpha is read from the float behind the records; the host value is what the first replay uploads
+            alpha = None
             if self._ema:
-                # the EMA form, clipped or not: alpha is read from the float behind the records; the host value is what the first replay uploads
-                nrec = 1 + len(self._opt_recs)
-                alpha0 = float(_ema_alpha(opt.ema_decay, opt.ema_warmup, opt._ema_updates + 1))
-                check(lib.cvk_adamw_step_ranges_ema_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
-                                                        opt._ema.data_ptr(), opt._flat.numel(), self._table.data_ptr(),
-                                                        len(self._opt_ranges), self._table_blocks, self._hyper.data_ptr() + HYPER_BYTES,
-                                                        len(self._opt_recs),
-                                                        opt._clip_rec.data_ptr() if self._norm_plan is not None else None,
-                                                        self._hyper.data_ptr() + nrec * HYPER_BYTES, alpha0, stream),
-                      "cvk_adamw_step_ranges_ema_dev")
-            elif self._norm_plan is not None:
-                check(lib.cvk_adamw_step_ranges_clip_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
-                                                         opt._flat.numel(), self._table.data_ptr(), len(self._opt_ranges),
-                                                         self._table_blocks, self._hyper.data_ptr() + HYPER_BYTES, len(self._opt_recs),
-                                                         opt._clip_rec.data_ptr(), stream), "cvk_adamw_step_ranges_clip_dev")
-            else:
-                check(lib.cvk_adamw_step_ranges_dev(opt._flat.data_ptr(), self._gflat.data_ptr(), opt._m.data_ptr(), opt._v.data_ptr(),
-                                                    opt._flat.numel(), self._table.data_ptr(), len(self._opt_ranges), self._table_blocks,
-                                                    self._hyper.data_ptr() + HYPER_BYTES, len(self._opt_recs), stream),
-                      "cvk_adamw_step_ranges_dev")
+                alpha = (self._hyper.data_ptr() + (1 + len(self._opt_recs)) * HYPER_BYTES,
+                         _ema_alpha(opt.ema_decay, opt.ema_warmup, opt._ema_updates + 1))
+            opt._launch_ranges(self._gflat, self._table, len(self._opt_ranges), self._table_blocks, self._hyper.data_ptr() + HYPER_BYTES,
+                               len(self._opt_recs), self._norm_plan is not None, alpha, stream)
         if self.log_capacity:
             gw, gb = self._log_w.grad, self._log_b.grad
             if gw is None or gb is None:
@@ -228,13 +214,9 @@ class GraphedStep:
             for g in (gw, gb):
                 if not (g.is_contiguous() or g.is_contiguous(memory_format=torch.channels_last)):
                     raise RuntimeError("GraphedStep: the last layer's gradient is not one dense block")
-            if self._log_cols == _lib.STEP_LOG_NORM_COLUMNS:
-                check(lib.cvk_step_log_norm(self.loss.data_ptr(), self._hyper.data_ptr(), gw.data_ptr(), gw.numel(), gb.data_ptr(),
-                                            gb.numel(), opt._clip_rec.data_ptr(), self._logbuf.data_ptr() + 8, self.log_capacity,
-                                            self._logbuf.data_ptr(), stream), "cvk_step_log_norm")
-            else:
-                check(lib.cvk_step_log(self.loss.data_ptr(), self._hyper.data_ptr(), gw.data_ptr(), gw.numel(), gb.data_ptr(), gb.numel(),
-                                       self._logbuf.data_ptr() + 8, self.log_capacity, self._logbuf.data_ptr(), stream), "cvk_step_log")
+            rec = opt._clip_rec.data_ptr() if self._log_cols == _lib.STEP_LOG_NORM_COLUMNS else None
+            check(lib.cvk_step_log(self.loss.data_ptr(), self._hyper.data_ptr(), gw.data_ptr(), gw.numel(), gb.data_ptr(), gb.numel(), rec,
+                                   self._logbuf.data_ptr() + 8, self.log_capacity, self._logbuf.data_ptr(), stream), "cvk_step_log")
 
     def _upload_hyper(self):
         """Every group as the scheduler left it + the next step counts -> the device records, on the current stream (no host sync: the host

@@ -12,16 +12,17 @@ buffer (cvk_adamw_step_ranges): frozen parameters and their moments are neither 
 
 Gradient clipping: `FlatAdamW(net, max_grad_norm=X, norm_type=2.0)` clips by the global norm inside the step.  A deterministic fp64
 reduction over the exact gradient segments of the parameters that take the step (all groups together, as torch's clip is global) writes a
-device record {total_norm, clip_coef}; the AdamW launch multiplies every gradient element by clip_coef on its way into the update
-(cvk_adamw_step_ranges_clip).  `.grad` is NOT rescaled — the one difference from the two-call idiom `clip_grad_norm_(...); opt.step()`,
+device record {total_norm, clip_coef}; the AdamW launch is handed that record and multiplies every gradient element by clip_coef on its
+way into the update.  `.grad` is NOT rescaled — the one difference from the two-call idiom `clip_grad_norm_(...); opt.step()`,
 which rewrites all gradients in place: after a clipped step `.grad` still holds what backward produced, `opt.grad_norm` its norm and
 `opt.clip_coef` the factor the update applied.  `clip_grad_norm_` below is the stand-alone form with torch's contract (scaled `.grad`s).
 Parameter gradients are fp32 in every mode (fp32, bf16 storage, split operands), so clipping is the same code under all of them.
 
 Weight averaging: `FlatAdamW(net, ema_decay=d, ema_warmup=False)` keeps an exponential moving average of the parameters in one more flat
 buffer, initialised to the weights the optimizer is built on (the convention of torch.optim.swa_utils.AveragedModel and timm).  The thread
-of the AdamW kernel that has just stored an element's new value goes on to `ema += alpha * (p_new - ema)` with it (cvk_adamw_step_ranges_ema:
-two more passes over the buffer instead of the three of a separate lerp, no launch, and inside the captured graph of GraphedStep).
+of the AdamW kernel that has just stored an element's new value goes on to `ema += alpha * (p_new - ema)` with it (the `ema` buffer of
+cvk_adamw_step_ranges: two more passes over the buffer instead of the three of a separate lerp, no launch, and inside the captured graph
+of GraphedStep).
 alpha = 1 - d, with warm-up 1 - min(d, (1 + k) / (10 + k)) at the k-th update (`ema_alpha`).  A parameter a step skips (frozen, no
 gradient) keeps its average: one frozen from the start has an average equal to itself.  `with opt.swap_ema():` exchanges the weights and
 the average for validation and saving (and tells the executor that its derived weights are stale); `opt.ema_state_dict()` is the
@@ -105,17 +106,23 @@ def norm_segments(pairs):
     return out
 
 
+def plan_segments(segments, n):
+    """(host NormSegment array with its workgroups assigned, workgroup count) of `segments` = [(offset, length)] of a buffer of n floats
+    (cvk_grad_norm_plan): the table of a norm, a scale or a fold.  `segments` must not be empty."""
+    arr = (_lib.NormSegment * len(segments))(*[_lib.NormSegment(o, m, 0, 0) for o, m in segments])
+    nb = _lib.load().cvk_grad_norm_plan(ctypes.addressof(arr), len(segments), n)
+    if nb <= 0:
+        check(nb if nb < 0 else -1, "cvk_grad_norm_plan")
+    return arr, nb
+
+
 class _NormPlan:
     """A planned segment table on the device, its workgroup count and the fp64 partials buffer of the reduction."""
 
     def __init__(self, segments, n, device):
-        lib = _lib.load()
         if not segments:
             raise RuntimeError("gradient norm: no parameter has a gradient")
-        arr = (_lib.NormSegment * len(segments))(*[_lib.NormSegment(o, m, 0, 0) for o, m in segments])
-        nb = lib.cvk_grad_norm_plan(ctypes.addressof(arr), len(segments), n)
-        if nb <= 0:
-            check(nb if nb < 0 else -1, "cvk_grad_norm_plan")
+        arr, nb = plan_segments(segments, n)
         self.nseg, self.n, self.blocks = len(segments), n, nb
         self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
         self.partials = torch.empty(nb, device=device, dtype=torch.float64)
@@ -399,6 +406,22 @@ class FlatAdamW(torch.optim.Optimizer):
             ent = self._tables[key] = (dev, nb)
         return ent
 
+    def _launch_ranges(self, grad, table, nranges, nblocks, hyper, nrec, clipped, alpha, stream):
+        """One AdamW launch over a planned range table (device tensor `table`, `nranges` entries, `nblocks` workgroups) with the gradient
+        buffer `grad`.  `hyper`: the `nrec` records, a host AdamwHyper array (eager: cvk_adamw_step_ranges) or the address of device records
+        (captured: cvk_adamw_step_ranges_dev).  `clipped`: the gradient is scaled by the optimizer's {total_norm, clip_coef} record.
+        `alpha`: None without an EMA; else the update's weight, a host float (eager) or (device address, host value) (captured)."""
+        lib = _lib.load()
+        head = (self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                self._ema.data_ptr() if alpha is not None else None, self._flat.numel(), table.data_ptr(), nranges, nblocks)
+        rec = self._clip_rec.data_ptr() if clipped else None
+        if isinstance(hyper, ctypes.Array):
+            check(lib.cvk_adamw_step_ranges(*head, ctypes.addressof(hyper), nrec, rec, 0.0 if alpha is None else float(alpha), stream),
+                  "cvk_adamw_step_ranges")
+        else:
+            adev, ahost = (None, 0.0) if alpha is None else alpha
+            check(lib.cvk_adamw_step_ranges_dev(*head, hyper, nrec, rec, adev, float(ahost), stream), "cvk_adamw_step_ranges_dev")
+
     def _check_homes(self):
         """The module must still read its weights from the flat buffer: net.to()/.cuda()/.float() after construction
         re-homes p.data and step() would then update memory nobody reads."""
@@ -465,10 +488,9 @@ class FlatAdamW(torch.optim.Optimizer):
         for i in idx:
             self._steps[i] += 1
         grad = self._flat_grad(idx)
-        lib = _lib.load()
         stream = torch.cuda.current_stream(self._flat.device).cuda_stream
         recs, ranges = self._ranges(idx)
-        alpha = self._next_ema_alpha() if ema is not None else None
+        alpha = self._next_ema_alpha() if ema is not None else None          # every chunk with the update's one alpha
         if max_norm is not None:      # one norm over everything that takes this step, all groups together: reduction + finish
             self._norm_plan(idx).norm(grad.data_ptr(), norm_type, max_norm, self._clip_rec, stream)
         # the records travel as kernel arguments: one launch per CVK_ADAMW_ARG_RECORDS distinct (group, step count) pairs
@@ -478,20 +500,6 @@ class FlatAdamW(torch.optim.Optimizer):
             hyper = (_lib.AdamwHyper * len(crecs))()
             self._fill(crecs, hyper)
             table, nb = self._table(cranges, len(crecs))
-            if ema is not None:       # the EMA form: the clip record or null, every chunk with the update's one alpha
-                check(lib.cvk_adamw_step_ranges_ema(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                                                    self._ema.data_ptr(), self._flat.numel(), table.data_ptr(), len(cranges), nb,
-                                                    ctypes.addressof(hyper), len(crecs),
-                                                    self._clip_rec.data_ptr() if max_norm is not None else None, float(alpha), stream),
-                      "cvk_adamw_step_ranges_ema")
-                continue
-            if max_norm is not None:
-                check(lib.cvk_adamw_step_ranges_clip(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                                                     self._flat.numel(), table.data_ptr(), len(cranges), nb, ctypes.addressof(hyper),
-                                                     len(crecs), self._clip_rec.data_ptr(), stream), "cvk_adamw_step_ranges_clip")
-                continue
-            check(lib.cvk_adamw_step_ranges(self._flat.data_ptr(), grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr(), self._flat.numel(),
-                                            table.data_ptr(), len(cranges), nb, ctypes.addressof(hyper), len(crecs), stream),
-                  "cvk_adamw_step_ranges")
+            self._launch_ranges(grad, table, len(cranges), nb, hyper, len(crecs), max_norm is not None, alpha, stream)
         engine._bump_epoch()          # the kernel wrote the parameters through raw pointers: derived weight tensors are stale
         return loss

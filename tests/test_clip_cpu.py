@@ -53,14 +53,27 @@ def test_new_entry_points_refuse_bad_arguments_before_any_launch():
     refused(lib.cvk_grad_scale(None, 8, p, 1, 1, p, None), "cvk_grad_scale")
     refused(lib.cvk_grad_scale(p, 8, p, 1, 1, None, None), "cvk_grad_scale")
     refused(lib.cvk_grad_scale(p, 8, p, 0, 0, p, None), "cvk_grad_scale")
-    refused(lib.cvk_adamw_step_ranges_clip(p, p, p, p, 8, p, 1, 1, p, 1, None, None), "cvk_adamw_step_ranges_clip")
-    refused(lib.cvk_adamw_step_ranges_clip(p, p, p, p, 8, p, 0, 0, p, 1, p, None), "cvk_adamw_step_ranges_clip")
-    refused(lib.cvk_adamw_step_ranges_clip(p, p, p, p, 8, p, 1, 1, p, L.ADAMW_ARG_RECORDS + 1, p, None), "cvk_adamw_step_ranges_clip")
-    refused(lib.cvk_adamw_step_ranges_clip_dev(p, p, p, p, 8, p, 1, 1, p, 1, None, None), "cvk_adamw_step_ranges_clip_dev")
-    refused(lib.cvk_adamw_step_ranges_clip_dev(p, None, p, p, 8, p, 1, 1, p, 1, p, None), "cvk_adamw_step_ranges_clip_dev")
-    refused(lib.cvk_adamw_step_ranges_clip_dev(p, p, p, p, 8, p, 0, 0, p, 1, p, None), "cvk_adamw_step_ranges_clip_dev")
-    refused(lib.cvk_step_log_norm(p, p, p, 4, p, 4, None, p, 4, p, None), "cvk_step_log_norm")
-    refused(lib.cvk_step_log_norm(p, p, p, 4, p, 4, p, p, 0, p, None), "cvk_step_log_norm")
+    # the clipped AdamW step and the 7-column log row: the folded entry points with a record.  A null record is no longer an error there
+    # (it means coefficient 1 / 5-column rows); in its place, an average without a usable alpha is refused
+    eager, captured = "cvk_adamw_step_ranges", "cvk_adamw_step_ranges_dev"
+    refused(lib.cvk_adamw_step_ranges(p, p, p, p, p, 8, p, 1, 1, p, 1, p, 1.5, None), eager)                 # ema with alpha outside (0, 1]
+    assert "alpha" in lib.cvk_last_error_string().decode()
+    refused(lib.cvk_adamw_step_ranges(p, p, p, p, None, 8, p, 0, 0, p, 1, p, 0.0, None), eager)
+    refused(lib.cvk_adamw_step_ranges(p, p, p, p, None, 8, p, 1, 1, p, L.ADAMW_ARG_RECORDS + 1, p, 0.0, None), eager)
+    refused(lib.cvk_adamw_step_ranges_dev(p, p, p, p, p, 8, p, 1, 1, p, 1, p, None, 0.5, None), captured)    # ema with a null device alpha
+    assert "null" in lib.cvk_last_error_string().decode()
+    refused(lib.cvk_adamw_step_ranges_dev(p, None, p, p, None, 8, p, 1, 1, p, 1, p, None, 0.0, None), captured)
+    refused(lib.cvk_adamw_step_ranges_dev(p, p, p, p, None, 8, p, 0, 0, p, 1, p, None, 0.0, None), captured)
+    # without an average alpha is ignored, not checked: the alpha test comes before the table test in both entry points, and an
+    # out-of-range alpha with an empty table is refused for the table
+    refused(lib.cvk_adamw_step_ranges(p, p, p, p, None, 8, p, 0, 0, p, 1, p, 1.5, None), eager)
+    assert "bad arguments" in lib.cvk_last_error_string().decode() and "alpha" not in lib.cvk_last_error_string().decode()
+    refused(lib.cvk_adamw_step_ranges_dev(p, p, p, p, None, 8, p, 0, 0, p, 1, p, None, float("nan"), None), captured)
+    assert "bad arguments" in lib.cvk_last_error_string().decode() and "alpha" not in lib.cvk_last_error_string().decode()
+    refused(lib.cvk_adamw_step_ranges(p, p, p, p, p, 8, p, 0, 0, p, 1, p, 1.5, None), eager)               # ... and with one, for alpha
+    assert "alpha" in lib.cvk_last_error_string().decode()
+    refused(lib.cvk_step_log(p, p, p, 4, p, 4, p, p, 0, p, None), "cvk_step_log")
+    refused(lib.cvk_step_log(p, p, p, 4, p, 4, p, None, 4, p, None), "cvk_step_log")
     # the planner: null, empty, segments outside [0, n)
     refused(lib.cvk_grad_norm_plan(None, 1, 8), "cvk_grad_norm_plan")
     one = (L.NormSegment * 1)(L.NormSegment(0, 8, 0, 0))

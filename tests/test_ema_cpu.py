@@ -1,5 +1,5 @@
 """The weight EMA of FlatAdamW, the parts that need no GPU: the per-update weight `ema_alpha`, the option check of the constructor and the
-argument checks of the two EMA entry points (refused on the host, before any launch)."""
+argument checks of the two range-step entry points with an EMA buffer (refused on the host, before any launch)."""
 import numpy as np
 import pytest
 
@@ -51,19 +51,20 @@ def test_ema_entry_points_refuse_bad_arguments_before_any_launch():
     from pytorch_camvid_amd import _lib as L
     lib = L.load()
     p = 4096                                                  # never dereferenced: every call is refused on the host
-    eager, captured = "cvk_adamw_step_ranges_ema", "cvk_adamw_step_ranges_ema_dev"
-    # a null ema buffer (and, like the neighbours, any other null pointer except the clip record)
-    _refused(lib, lib.cvk_adamw_step_ranges_ema(p, p, p, p, None, 8, p, 1, 1, p, 1, None, 0.1, None), eager, "null")
-    _refused(lib, lib.cvk_adamw_step_ranges_ema(p, None, p, p, p, 8, p, 1, 1, p, 1, p, 0.1, None), eager, "null")
-    _refused(lib, lib.cvk_adamw_step_ranges_ema_dev(p, p, p, p, None, 8, p, 1, 1, p, 1, None, p, 0.1, None), captured, "null")
-    _refused(lib, lib.cvk_adamw_step_ranges_ema_dev(p, p, p, p, p, 8, p, 1, 1, p, 1, p, None, 0.1, None), captured, "null")
+    eager, captured = "cvk_adamw_step_ranges", "cvk_adamw_step_ranges_dev"
+    # null pointers.  A null ema buffer itself is the step without an average (as a null clip record is the unclipped step), so it is not
+    # refused; every other buffer still is, with and without an average, and so is an average whose device alpha is null
+    _refused(lib, lib.cvk_adamw_step_ranges(p, p, p, None, None, 8, p, 1, 1, p, 1, None, 0.1, None), eager, "null")
+    _refused(lib, lib.cvk_adamw_step_ranges(p, None, p, p, p, 8, p, 1, 1, p, 1, p, 0.1, None), eager, "null")
+    _refused(lib, lib.cvk_adamw_step_ranges_dev(p, p, p, None, None, 8, p, 1, 1, p, 1, None, p, 0.1, None), captured, "null")
+    _refused(lib, lib.cvk_adamw_step_ranges_dev(p, p, p, p, p, 8, p, 1, 1, p, 1, p, None, 0.1, None), captured, "null")
     # alpha outside (0, 1], with and without a clip record
     for alpha in (0.0, 1.5, -0.25, float("nan")):
         for rec in (None, p):
-            _refused(lib, lib.cvk_adamw_step_ranges_ema(p, p, p, p, p, 8, p, 1, 1, p, 1, rec, alpha, None), eager, "alpha")
-            _refused(lib, lib.cvk_adamw_step_ranges_ema_dev(p, p, p, p, p, 8, p, 1, 1, p, 1, rec, p, alpha, None), captured, "alpha")
+            _refused(lib, lib.cvk_adamw_step_ranges(p, p, p, p, p, 8, p, 1, 1, p, 1, rec, alpha, None), eager, "alpha")
+            _refused(lib, lib.cvk_adamw_step_ranges_dev(p, p, p, p, p, 8, p, 1, 1, p, 1, rec, p, alpha, None), captured, "alpha")
     # the record limit of the kernel-argument form; an empty table in both
-    _refused(lib, lib.cvk_adamw_step_ranges_ema(p, p, p, p, p, 8, p, 1, 1, p, L.ADAMW_ARG_RECORDS + 1, None, 0.1, None), eager, "records")
+    _refused(lib, lib.cvk_adamw_step_ranges(p, p, p, p, p, 8, p, 1, 1, p, L.ADAMW_ARG_RECORDS + 1, None, 0.1, None), eager, "records")
     assert L.ADAMW_ARG_RECORDS + 1 == 17
-    _refused(lib, lib.cvk_adamw_step_ranges_ema(p, p, p, p, p, 8, p, 0, 0, p, 1, None, 0.1, None), eager, "bad arguments")
-    _refused(lib, lib.cvk_adamw_step_ranges_ema_dev(p, p, p, p, p, 8, p, 0, 0, p, 1, None, p, 0.1, None), captured, "bad arguments")
+    _refused(lib, lib.cvk_adamw_step_ranges(p, p, p, p, p, 8, p, 0, 0, p, 1, None, 0.1, None), eager, "bad arguments")
+    _refused(lib, lib.cvk_adamw_step_ranges_dev(p, p, p, p, p, 8, p, 0, 0, p, 1, None, p, 0.1, None), captured, "bad arguments")

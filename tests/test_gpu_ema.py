@@ -248,7 +248,7 @@ def _make(A, iters):
 
 
 def test_captured_iteration_with_ema_is_bitwise_the_eager_loop():
-    """The eager loop writes its own log rows with the kernel the graph ends in (cvk_step_log_norm on the record of the step it has just
+    """The eager loop writes its own log rows with the kernel the graph ends in (cvk_step_log with the record of the step it has just
     taken), so the rows compare bit for bit, all seven columns."""
     import pytorch_camvid_amd as A
     from pytorch_camvid_amd import _lib
@@ -281,9 +281,9 @@ def test_captured_iteration_with_ema_is_bitwise_the_eager_loop():
         _lib.check(lib.cvk_adamw_hyper_fill(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                                             float(g["weight_decay"]), opt_r._step, ctypes.addressof(rec)), "cvk_adamw_hyper_fill")
         hyper.copy_(torch.tensor(list(np.frombuffer(bytes(rec), np.float32)), dtype=torch.float32))
-        _lib.check(lib.cvk_step_log_norm(lb.data_ptr(), hyper.data_ptr(), rw.grad.data_ptr(), rw.grad.numel(), rb.grad.data_ptr(),
-                                         rb.grad.numel(), opt_r._clip_rec.data_ptr(), ring.data_ptr() + 8, iters, ring.data_ptr(), stream),
-                   "cvk_step_log_norm")
+        _lib.check(lib.cvk_step_log(lb.data_ptr(), hyper.data_ptr(), rw.grad.data_ptr(), rw.grad.numel(), rb.grad.data_ptr(),
+                                    rb.grad.numel(), opt_r._clip_rec.data_ptr(), ring.data_ptr() + 8, iters, ring.data_ptr(), stream),
+                   "cvk_step_log")
         sched_r.step()
         assert torch.equal(la, lb), (it, la.item(), lb.item())
         assert torch.equal(opt._flat, opt_r._flat) and torch.equal(opt._m, opt_r._m) and torch.equal(opt._v, opt_r._v), it

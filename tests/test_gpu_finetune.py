@@ -218,9 +218,9 @@ def test_range_launch_is_bitwise_cvk_adamw_step():
         tdev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev())
         ptrs = [t.data_ptr() for t in b]
         if dev_form:
-            rc = lib.cvk_adamw_step_ranges_dev(*ptrs, n, tdev.data_ptr(), len(ranges), nb, hdev.data_ptr(), 1, s)
+            rc = lib.cvk_adamw_step_ranges_dev(*ptrs, None, n, tdev.data_ptr(), len(ranges), nb, hdev.data_ptr(), 1, None, None, 0.0, s)
         else:
-            rc = lib.cvk_adamw_step_ranges(*ptrs, n, tdev.data_ptr(), len(ranges), nb, ctypes.addressof(hyper), 1, s)
+            rc = lib.cvk_adamw_step_ranges(*ptrs, None, n, tdev.data_ptr(), len(ranges), nb, ctypes.addressof(hyper), 1, None, 0.0, s)
         assert rc == 0
         torch.cuda.synchronize()
         return b
@@ -251,6 +251,108 @@ def test_range_launch_is_bitwise_cvk_adamw_step():
     assert lib.cvk_adamw_step(flat0.data_ptr(), gl.data_ptr(), m.data_ptr(), v.data_ptr(), flat0.numel(), 1e-3, 0.9, 0.999, 1e-8, 1e-2, 1, s) == 0
     torch.cuda.synchronize()
     assert torch.equal(flat0, opt._flat) and torch.equal(m, opt._m) and torch.equal(v, opt._v)
+
+
+# ---- the folded range step: records as arguments / on the device x clip record or none x average or none ----------------------------------
+MATRIX_N = 3072
+MATRIX_RANGES = [(0, 260, 0), (512, 1028, 1), (3068, 4, 0)]      # longer than a workgroup with a tail; several workgroups; 4 floats up to the end
+MATRIX_HYPER = [(3e-3, 0.9, 0.999, 1e-8, 1e-2, 7), (1e-3, 0.85, 0.99, 1e-8, 5e-2, 3)]
+MATRIX_CLIP = (3.0, 0.37)                                        # {total_norm, clip_coef}
+MATRIX_ALPHA = 0.1
+_MATRIX = {}                                                     # the inputs and, per coefficient, the reference and the first case's result
+
+
+def _matrix_inputs():
+    """param, grad, exp_avg, exp_avg_sq, ema of MATRIX_N floats (never written: every case works on clones)."""
+    if "bufs" not in _MATRIX:
+        g = torch.Generator(device=dev()).manual_seed(23)
+        bufs = [torch.randn(MATRIX_N, generator=g, device=dev()) for _ in range(2)]
+        bufs += [torch.rand(MATRIX_N, generator=g, device=dev()) * 1e-3 for _ in range(2)]
+        bufs[3] = bufs[3] * bufs[3]
+        bufs.append(torch.randn(MATRIX_N, generator=g, device=dev()))
+        _MATRIX["bufs"] = bufs
+    return _MATRIX["bufs"]
+
+
+def _matrix_reference(lib, coef):
+    """Per range (param, exp_avg, exp_avg_sq) of cvk_adamw_step (k_adamw, whole buffer, scalars as arguments) on clones of the range's slices,
+    with the range's record and the gradient multiplied by `coef` in torch fp32 (None: not multiplied)."""
+    key = ("ref", coef)
+    if key not in _MATRIX:
+        p, g, m, v, _ = _matrix_inputs()
+        s = torch.cuda.current_stream().cuda_stream
+        out = []
+        for o, n, r in MATRIX_RANGES:
+            sl = [t[o:o + n].clone() for t in (p, g, m, v)]
+            if coef is not None:
+                sl[1] = sl[1] * torch.tensor(coef, dtype=torch.float32, device=dev())
+            assert lib.cvk_adamw_step(*[t.data_ptr() for t in sl], n, *MATRIX_HYPER[r], s) == 0
+            out.append((sl[0], sl[2], sl[3]))
+        torch.cuda.synchronize()
+        _MATRIX[key] = out
+    return _MATRIX[key]
+
+
+@pytest.mark.parametrize("with_ema", [False, True], ids=["noema", "ema"])
+@pytest.mark.parametrize("with_record", [False, True], ids=["norec", "rec"])
+@pytest.mark.parametrize("dev_form", [False, True], ids=["host", "device"])
+def test_folded_range_step_matrix(dev_form, with_record, with_ema):
+    """cvk_adamw_step_ranges / cvk_adamw_step_ranges_dev with every combination of their two nullable pointers.  Inside the ranges param and
+    the moments are bitwise cvk_adamw_step on the slice; outside nothing changes, in any buffer; the average follows
+    e + alpha * (p_new - e) within the bound of test_gpu_ema.py (one update: 2^-21 times the largest magnitude among p and e, which is what
+    its derivation takes max|p| for); cases with the same coefficient agree bitwise."""
+    from pytorch_camvid_amd import _lib
+    lib = _lib.load()
+    s = torch.cuda.current_stream().cuda_stream
+    orig = _matrix_inputs()
+    b = [t.clone() for t in orig[:4]]
+    ema = orig[4].clone() if with_ema else None                     # without an average there is no buffer at all
+    coef = MATRIX_CLIP[1] if with_record else None
+    ref = _matrix_reference(lib, coef)
+
+    hyper = (_lib.AdamwHyper * len(MATRIX_HYPER))()
+    for r, args in enumerate(MATRIX_HYPER):
+        assert lib.cvk_adamw_hyper_fill(*args, ctypes.addressof(hyper) + r * ctypes.sizeof(_lib.AdamwHyper)) == 0
+    tab = (_lib.AdamwRange * len(MATRIX_RANGES))(*[_lib.AdamwRange(o, n, r, 0) for o, n, r in MATRIX_RANGES])
+    nb = lib.cvk_adamw_plan_ranges(ctypes.addressof(tab), len(MATRIX_RANGES), MATRIX_N, len(MATRIX_HYPER))
+    assert nb == 2 + 5 + 1 and [e.block0 for e in tab] == [0, 2, 7]
+    tdev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev())
+    rec = torch.tensor(MATRIX_CLIP, dtype=torch.float32, device=dev()) if with_record else None
+    alpha = torch.tensor([MATRIX_ALPHA], dtype=torch.float32, device=dev())
+    head = [t.data_ptr() for t in b] + [ema.data_ptr() if with_ema else None, MATRIX_N, tdev.data_ptr(), len(MATRIX_RANGES), nb]
+    recp = rec.data_ptr() if with_record else None
+    if dev_form:
+        hdev = torch.frombuffer(bytearray(bytes(hyper)), dtype=torch.uint8).to(dev())
+        rc = lib.cvk_adamw_step_ranges_dev(*head, hdev.data_ptr(), len(MATRIX_HYPER), recp, alpha.data_ptr() if with_ema else None,
+                                           MATRIX_ALPHA if with_ema else 0.0, s)
+    else:
+        rc = lib.cvk_adamw_step_ranges(*head, ctypes.addressof(hyper), len(MATRIX_HYPER), recp, MATRIX_ALPHA if with_ema else 0.0, s)
+    assert rc == 0, lib.cvk_last_error_string()
+    torch.cuda.synchronize()
+
+    inside = torch.zeros(MATRIX_N, dtype=torch.bool, device=dev())
+    for (o, n, _), (rp, rm, rv) in zip(MATRIX_RANGES, ref):
+        inside[o:o + n] = True
+        assert torch.equal(b[0][o:o + n], rp) and torch.equal(b[2][o:o + n], rm) and torch.equal(b[3][o:o + n], rv), (o, n)
+        assert not torch.equal(b[0][o:o + n], orig[0][o:o + n])
+    assert int(inside.sum()) == sum(n for _, n, _ in MATRIX_RANGES) < MATRIX_N
+    for got, was in zip(b, orig):                                    # outside the ranges: the original bits; the gradient: everywhere
+        assert torch.equal(got[~inside], was[~inside])
+    assert torch.equal(b[1], orig[1])
+    if with_ema:
+        assert torch.equal(ema[~inside], orig[4][~inside])
+        a32 = float(alpha.item())
+        e0, pn = orig[4].double(), b[0].double()
+        want = e0 + a32 * (pn - e0)
+        pmax = float(torch.stack([orig[0].abs().max(), b[0].abs().max(), orig[4].abs().max()]).max())
+        worst, bound = float((ema.double() - want).abs()[inside].max()), 2.0 ** -21 * pmax
+        print(f"folded step matrix: max |ema - fp64| = {worst:.3e}, bound {bound:.3e} (largest magnitude {pmax:.4f})")
+        assert worst <= bound
+        assert not torch.equal(ema[inside], orig[4][inside])
+    first = _MATRIX.setdefault(("seen", coef), (b[0], b[2], b[3]))    # the cases with this coefficient that ran before: the same bits
+    assert all(torch.equal(x, y) for x, y in zip(first, (b[0], b[2], b[3])))
+    if ("seen", None) in _MATRIX and ("seen", MATRIX_CLIP[1]) in _MATRIX:
+        assert not torch.equal(_MATRIX[("seen", None)][0], _MATRIX[("seen", MATRIX_CLIP[1])][0])     # the record really scaled the gradient
 
 
 def _ft_make(A, iters, seed=0):

@@ -54,25 +54,29 @@ def test_new_entry_points_validate_arguments_without_gpu():
     assert lib.cvk_adamw_hyper_fill(1e-3, 0.9, 0.999, 1e-8, 0.0, 0, ctypes.addressof(h)) == -1        # step < 1
     assert lib.cvk_adamw_hyper_fill(1e-3, 0.9, 0.999, 1e-8, 0.0, -5, ctypes.addressof(h)) == -1
 
-    step = lib.cvk_adamw_step_dev
-    #           param grad m  v   n     hyper stream
-    for args in ((None, P, P, P, 100, P), (P, None, P, P, 100, P), (P, P, None, P, 100, P), (P, P, P, None, 100, P),
-                 (P, P, P, P, 100, None)):
-        assert step(*args, None) == -1
+    step = lib.cvk_adamw_step_ranges_dev
+    #           param grad m  v  ema   n    ranges nr nb hyper nh rec  alpha a_host stream
+    good = [P, P, P, P, None, 100, P, 1, 1, P, 1, None, None, 0.0, None]
+    for i in (0, 1, 2, 3, 6, 9):                                                                       # every pointer that may not be null
+        args = list(good)
+        args[i] = None
+        assert step(*args) == -1
         assert b"null" in _err()
-    assert step(P, P, P, P, 0, P, None) == -1                                                          # n <= 0
-    assert b"bad arguments" in _err()
-    assert step(P, P, P, P, -7, P, None) == -1
+    for n in (0, -7):                                                                                  # n <= 0
+        args = list(good)
+        args[5] = n
+        assert step(*args) == -1
+        assert b"bad arguments" in _err()
 
     log = lib.cvk_step_log
-    #      loss hyper gw nw gb nb  ring cap counter stream
-    good = [P, P, P, 12, P, 12, P, 8, P, None]
-    for i in (0, 1, 2, 4, 6, 8):                                                                       # every pointer
+    #      loss hyper gw nw gb nb  rec   ring cap counter stream
+    good = [P, P, P, 12, P, 12, None, P, 8, P, None]
+    for i in (0, 1, 2, 4, 7, 9):                                                                       # every pointer but the clip record
         args = list(good)
         args[i] = None
         assert log(*args) == -1
         assert b"null" in _err()
-    for i, bad in ((7, 0), (7, -1), (3, 0), (3, -4), (5, 0), (5, -4)):                                # capacity, nw, nb
+    for i, bad in ((8, 0), (8, -1), (3, 0), (3, -4), (5, 0), (5, -4)):                                # capacity, nw, nb
         args = list(good)
         args[i] = bad
         assert log(*args) == -1
