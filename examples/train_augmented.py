@@ -59,7 +59,16 @@ def main():
                     help="keep an exponential moving average of the weights inside the fused step (FlatAdamW(ema_decay=X); needs --graphed); "
                     "every epoch validates the live and, inside opt.swap_ema(), the averaged weights")
     ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: decay min(X, (1 + k) / (10 + k)) at the k-th update")
+    ap.add_argument("--tta-scales", default=None, metavar="S,S,...",
+                    help="validate with multi-scale test-time augmentation at these scales, e.g. 0.75,1.0,1.25 (cvk.TestTimeAugmentation)")
+    ap.add_argument("--tta-flip", action="store_true", help="also validate on the mirrored views (alone: scale 1.0 and its mirror image)")
     a = ap.parse_args()
+    tta = None
+    if a.tta_scales or a.tta_flip:
+        try:
+            tta = cvk.TestTimeAugmentation(scales=[float(v) for v in (a.tta_scales or "1.0").split(",")], flip=a.tta_flip)
+        except ValueError as e:
+            ap.error(f"--tta-scales: {e}")
     if (a.ema_decay is not None or a.ema_warmup) and not a.graphed:
         ap.error("--ema-decay / --ema-warmup need --graphed (the average lives in FlatAdamW's flat buffers)")
     if a.ema_warmup and a.ema_decay is None:
@@ -126,12 +135,12 @@ def main():
             print(f"  grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of {n.numel()} steps "
                   f"(max_norm {a.clip_grad_norm:g})")
         val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
-        acc, iou, miou = cvk.evaluate(net, val, num_classes=12, ignore_index=11)
+        acc, iou, miou = cvk.evaluate(net, val, num_classes=12, ignore_index=11, tta=tta)
         print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
                 val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)    # the same frames again
-                acc_e, _, miou_e = cvk.evaluate(net, val, num_classes=12, ignore_index=11)
+                acc_e, _, miou_e = cvk.evaluate(net, val, num_classes=12, ignore_index=11, tta=tta)
             print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
 
 

@@ -52,7 +52,16 @@ def main():
                     help="keep an exponential moving average of the weights inside the fused step (FlatAdamW(ema_decay=X); needs --flat-adamw or "
                     "--graphed); every epoch validates the live and, inside opt.swap_ema(), the averaged weights")
     ap.add_argument("--ema-warmup", action="store_true", help="with --ema-decay: decay min(X, (1 + k) / (10 + k)) at the k-th update")
+    ap.add_argument("--tta-scales", default=None, metavar="S,S,...",
+                    help="validate with multi-scale test-time augmentation at these scales, e.g. 0.75,1.0,1.25 (cvk.TestTimeAugmentation)")
+    ap.add_argument("--tta-flip", action="store_true", help="also validate on the mirrored views (alone: scale 1.0 and its mirror image)")
     a = ap.parse_args()
+    tta = None
+    if a.tta_scales or a.tta_flip:
+        try:
+            tta = cvk.TestTimeAugmentation(scales=[float(v) for v in (a.tta_scales or "1.0").split(",")], flip=a.tta_flip)
+        except ValueError as e:
+            ap.error(f"--tta-scales: {e}")
     a.flat_adamw = a.flat_adamw or a.graphed
     if (a.ema_decay is not None or a.ema_warmup) and not a.flat_adamw:
         ap.error("--ema-decay / --ema-warmup need --flat-adamw or --graphed (the average lives in FlatAdamW's flat buffers)")
@@ -153,12 +162,12 @@ def main():
             m = masks[it].to(dev)
             frames = ((m.unsqueeze(-1) * torch.tensor([20, 15, 10], device=dev)) % 256).clamp(0, 255).to(torch.uint8)
             batches.append((cvk.preprocess_uint8(frames), m))
-        acc, iou, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11)
+        acc, iou, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta)
         if rank == 0:
             print(f"          val acc {acc:.4f}  mIoU(11 classes) {miou:.4f}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
-                acc_e, _, miou_e = cvk.evaluate(net, batches, num_classes=12, ignore_index=11)
+                acc_e, _, miou_e = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta)
             if rank == 0:
                 print(f"          EMA acc {acc_e:.4f}  mIoU(11 classes) {miou_e:.4f}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
     if rank == 0:

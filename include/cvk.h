@@ -507,6 +507,30 @@ int cvk_argmax_channels(const float* logits, int ld, int64_t* out, int M, int C,
 int cvk_confusion_accumulate(const int64_t* pred, const int64_t* label, int64_t* hist, int M, int num_classes,
                              int ignore_index, void* stream);
 
+/* ---- multi-scale / flip test-time augmentation: the merge of the views' logits (not in the reference) ------------------
+ * Bilinear resampling here is torch's F.interpolate(mode="bilinear", align_corners=False) with the sample position taken from
+ * integers: for destination index d of `out` samples over `in` source samples, num = max((2 d + 1) in - out, 0), lower source
+ * index i0 = num / (2 out), upper i1 = min(i0 + 1, in - 1), fraction f = float(num % (2 out)) / float(2 out) (rounded once),
+ * weights (1 - f, f); the value is wy0 (wx0 a + wx1 b) + wy1 (wx0 c + wx1 d).  At in == out the weights are exactly (1, 0).
+ *
+ * cvk_tta_accumulate, one call per view, in view order: logits are the view's dense NHWC rows [N][h][w][ld] (ld >= C), acc is
+ * dense float [N][H][W][C].  Per pixel (n, y, x): v = the logits resampled to H x W at (y, x) — at (y, W - 1 - x) when flip != 0,
+ * the mirrored view turned back —, p = softmax(v) (max-subtracted) and
+ *   first != 0: acc = p (acc is not read, the caller need not clear it), else acc += p;
+ *   last  != 0: acc = (that sum) * inv_k, and pred (int64 [N][H][W], required) = the first-maximum channel of exactly the values
+ *               stored (a NaN wins, as in cvk_argmax_channels).  first and last together: a softmax + arg-max pass.
+ * Every sum runs in the order of the calls, no atomics: the result is bitwise reproducible.  1 <= C <= 32 (a pixel's classes are
+ * held in registers), sizes up to 16384 per side, N * H * W * C < 2^31.  C % 4 == 0 with ld % 4 == 0 and 16-byte aligned pointers
+ * moves rows as 16-byte vectors; anything else takes scalar paths.  One launch, no allocation, no host sync.
+ *
+ * cvk_tta_resize_input: a view's network input.  src: logical [N][3][H][W] float of any strides (in floats, as cvk_import_nchw)
+ * -> dst dense NHWC [N][h][w][4] (cvk_preprocess_u8's layout, pad channel 0, 16-byte aligned), resampled as above; flip != 0
+ * mirrors the result left-right (dst column x = resampled column w - 1 - x).  One launch. */
+int cvk_tta_accumulate(const float* logits, int ld, int h, int w, float* acc, int64_t* pred, int N, int H, int W, int C, int flip,
+                       int first, int last, float inv_k, void* stream);
+int cvk_tta_resize_input(const float* src, int64_t sN, int64_t sC, int64_t sH, int64_t sW, float* dst, int N, int H, int W, int h, int w,
+                         int flip, void* stream);
+
 /* ---- input pipeline on device (transforms.ToTensor + Normalize: transforms.py:485-538, MEAN/STD conf/settings.py:8-9) ----
  * src uint8 [N,H,W,3] (channel order as decoded, i.e. cv2 BGR) -> dst float32 NHWC with ld = 4 (pad channel 0):
  * dst[c] = (src[c]/255 - mean3[c]) / std3[c].  mean3 / std3 are HOST pointers to 3 floats. */

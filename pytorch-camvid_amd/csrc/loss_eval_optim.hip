@@ -788,6 +788,146 @@ __global__ void k_argmax(const float* __restrict__ logits, int ld, int64_t* __re
     }
 }
 
+// ---- multi-scale / flip test-time augmentation (cvk_tta_accumulate, cvk_tta_resize_input) ---------------------------------------
+// One launch per view folds that view's logits into the [M][C] probability accumulator: a workgroup owns CE_CHUNK consecutive
+// accumulator rows (a contiguous span of 256 C floats), one thread per pixel.  The accumulator side is staged through LDS exactly
+// as k_ce_fwd stages its logits (a thread's own row is C floats apart from its neighbour's: read and written directly, a wave
+// would touch 64 lines for 64 * 4 useful bytes per instruction), with pitch C + 1 so the row walk is conflict free.  The gather
+// side is not staged: a pixel reads the two or four source rows around its sample position straight from global memory, as
+// 16-byte vectors where the layout allows; neighbouring pixels share source rows, and a view's logits are at most a few tens of
+// MB that the pass walks in order, so these reads are L2 hits after the first touch.  The resampled logits, their softmax and the
+// arg-max stay in registers (CP = C rounded up to a multiple of 4 is the compile-time register count).
+// Sample positions come from integers (include/cvk.h); the divisions are per row and per column, never per channel: the rows a
+// workgroup covers are tabulated in LDS by its first threads, a thread computes its own column once.
+constexpr int TTA_MAX_C = 32;            // classes held in registers per pixel
+constexpr int TTA_MAX_DIM = 16384;       // (2 d + 1) in - out stays inside int32
+
+struct TtaTap {
+    int i0, i1;                          // lower / upper source index (upper clamped to the last one)
+    float w0, w1;                        // their weights (1 - f, f)
+};
+
+__device__ __forceinline__ TtaTap tta_tap(int dst, int in, int out) {
+    const int den = 2 * out;
+    int num = (2 * dst + 1) * in - out;
+    num = num < 0 ? 0 : num;
+    const int i0 = num / den, rem = num - i0 * den;
+    TtaTap t;
+    t.i0 = i0;
+    t.i1 = i0 + 1 < in ? i0 + 1 : in - 1;
+    t.w1 = (float)rem / (float)den;      // both exact in fp32 (< 2^24): one rounding
+    t.w0 = 1.f - t.w1;
+    return t;
+}
+
+template <int CP, bool IDENT>
+__global__ __launch_bounds__(CE_CHUNK) void k_tta_accumulate(const float* __restrict__ logits, int ld, int h, int w,
+                                                            float* __restrict__ acc, int64_t* __restrict__ pred, int H, int W, int M,
+                                                            int C, int flip, int first, int last, float inv_k) {
+    extern __shared__ float lds[];       // CE_CHUNK accumulator rows, pitch C + 1
+    __shared__ TtaTap s_row[CE_CHUNK];   // the output rows this workgroup's pixels lie in (at most CE_CHUNK of them, at W = 1)
+    __shared__ int s_img[CE_CHUNK];
+    const int pitch = C + 1;
+    const int m0 = blockIdx.x * CE_CHUNK;
+    const int rows = min(CE_CHUNK, M - m0);
+    const int gy0 = m0 / W;                                   // uniform: first row of the [N * H] rows this workgroup touches
+    const int nrows = (m0 + rows - 1) / W - gy0 + 1;
+    for (int r = threadIdx.x; r < nrows; r += CE_CHUNK) {
+        const int gy = gy0 + r, n = gy / H;
+        s_row[r] = tta_tap(gy - n * H, h, H);
+        s_img[r] = n;
+    }
+    if (!first) ce_chunk_load(acc + (size_t)m0 * C, lds, rows * C, C);
+    __syncthreads();
+    int bi = 0;
+    if ((int)threadIdx.x < rows) {
+        // (row, column) of pixel m0 + threadIdx.x relative to row gy0: off < W + CE_CHUNK < 2^24, so the fp32 quotient is off by one at most
+        const int off = m0 - gy0 * W + (int)threadIdx.x;
+        int q = (int)((float)off * (1.f / (float)W));
+        int x = off - q * W;
+        if (x < 0) { x += W; --q; } else if (x >= W) { x -= W; ++q; }
+        const TtaTap ty = s_row[q];
+        const TtaTap tx = tta_tap(flip ? W - 1 - x : x, w, W);
+        const float* img = logits + (size_t)s_img[q] * h * w * ld;
+        const float* r00 = img + ((size_t)ty.i0 * w + tx.i0) * ld;
+        float v[CP];
+        const bool vec = (C & 3) == 0 && (ld & 3) == 0 && ((uintptr_t)logits & 15u) == 0;        // uniform
+        if (IDENT) {                                          // view at the output size: weights (1, 0) both ways, one source row
+            if (vec) {
+#pragma unroll
+                for (int j = 0; j < CP / 4; ++j) {
+                    const f32x4 a = reinterpret_cast<const f32x4*>(r00)[j];
+                    v[4 * j] = a[0]; v[4 * j + 1] = a[1]; v[4 * j + 2] = a[2]; v[4 * j + 3] = a[3];
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < CP; ++c) v[c] = c < C ? r00[c] : 0.f;
+            }
+        } else {
+            const float* r01 = img + ((size_t)ty.i0 * w + tx.i1) * ld;
+            const float* r10 = img + ((size_t)ty.i1 * w + tx.i0) * ld;
+            const float* r11 = img + ((size_t)ty.i1 * w + tx.i1) * ld;
+            if (vec) {
+#pragma unroll
+                for (int j = 0; j < CP / 4; ++j) {
+                    const f32x4 a = reinterpret_cast<const f32x4*>(r00)[j], b = reinterpret_cast<const f32x4*>(r01)[j];
+                    const f32x4 c = reinterpret_cast<const f32x4*>(r10)[j], d = reinterpret_cast<const f32x4*>(r11)[j];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[4 * j + k] = ty.w0 * (tx.w0 * a[k] + tx.w1 * b[k]) + ty.w1 * (tx.w0 * c[k] + tx.w1 * d[k]);
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < CP; ++c)
+                    v[c] = c < C ? ty.w0 * (tx.w0 * r00[c] + tx.w1 * r01[c]) + ty.w1 * (tx.w0 * r10[c] + tx.w1 * r11[c]) : 0.f;
+            }
+        }
+        float mx = v[0];
+#pragma unroll
+        for (int c = 1; c < CP; ++c)
+            if (c < C) mx = fmaxf(mx, v[c]);
+        float se = 0.f;
+#pragma unroll
+        for (int c = 0; c < CP; ++c)
+            if (c < C) { v[c] = expf(v[c] - mx); se += v[c]; }
+        const float inv = 1.f / se;
+        float* p = lds + threadIdx.x * pitch;
+        float best = 0.f;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) {
+            if (c < C) {
+                float s = v[c] * inv;
+                if (!first) s = p[c] + s;
+                if (last) s *= inv_k;
+                p[c] = s;
+                if (c == 0 || s > best || (s != s && best == best)) { best = s; bi = c; }   // k_argmax's rule on the stored values
+            }
+        }
+    }
+    __syncthreads();
+    ce_chunk_store(acc + (size_t)m0 * C, lds, rows * C, C);
+    if (last && (int)threadIdx.x < rows) pred[m0 + threadIdx.x] = bi;
+}
+
+// A view's network input: [N][3][H][W] of any strides -> NHWC-4 [N][h][w][4]; grid (ceil(w / 256), h, N), so the row tap is uniform
+// per workgroup and a thread divides once, for its column.
+__global__ __launch_bounds__(256) void k_tta_resize_input(const float* __restrict__ src, int64_t sN, int64_t sC, int64_t sH, int64_t sW,
+                                                         float* __restrict__ dst, int H, int W, int h, int w, int flip) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, n = blockIdx.z;
+    if (x >= w) return;
+    const TtaTap ty = tta_tap(y, H, h);
+    const TtaTap tx = tta_tap(flip ? w - 1 - x : x, W, w);
+    const float* b = src + n * sN;
+    const int64_t o00 = ty.i0 * sH + tx.i0 * sW, o01 = ty.i0 * sH + tx.i1 * sW, o10 = ty.i1 * sH + tx.i0 * sW, o11 = ty.i1 * sH + tx.i1 * sW;
+    f32x4 o;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float* p = b + c * sC;
+        o[c] = ty.w0 * (tx.w0 * p[o00] + tx.w1 * p[o01]) + ty.w1 * (tx.w0 * p[o10] + tx.w1 * p[o11]);
+    }
+    o[3] = 0.f;
+    *reinterpret_cast<f32x4*>(dst + (((size_t)n * h + y) * w + x) * 4) = o;
+}
+
 __global__ __launch_bounds__(256) void k_confusion(const int64_t* __restrict__ pred, const int64_t* __restrict__ label,
                                                   unsigned long long* __restrict__ hist, int M, int K, int ignore) {
     extern __shared__ unsigned int h[];  // [3][K]
@@ -1467,6 +1607,51 @@ extern "C" int cvk_argmax_channels(const float* logits, int ld, int64_t* out, in
     const int blocks = cvk_cdiv(M, 256) < 8192 ? cvk_cdiv(M, 256) : 8192;
     hipLaunchKernelGGL(k_argmax, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, ld, out, M, C);
     CVK_LAUNCH_RETURN("cvk_argmax_channels");
+}
+
+template <bool IDENT>
+static bool tta_launch(int CP, int nb, size_t lds_bytes, hipStream_t s, const float* logits, int ld, int h, int w, float* acc, int64_t* pred,
+                       int H, int W, int M, int C, int flip, int first, int last, float inv_k) {
+#define TTA_CASE(cp)                                                                                                              \
+    case cp:                                                                                                                      \
+        hipLaunchKernelGGL((k_tta_accumulate<cp, IDENT>), dim3(nb), dim3(CE_CHUNK), lds_bytes, s, logits, ld, h, w, acc, pred, H, W, M, C, \
+                           flip, first, last, inv_k);                                                                             \
+        return true;
+    switch (CP) {
+        TTA_CASE(4) TTA_CASE(8) TTA_CASE(12) TTA_CASE(16) TTA_CASE(20) TTA_CASE(24) TTA_CASE(28) TTA_CASE(32)
+    }
+#undef TTA_CASE
+    return false;
+}
+
+extern "C" int cvk_tta_accumulate(const float* logits, int ld, int h, int w, float* acc, int64_t* pred, int N, int H, int W, int C,
+                                  int flip, int first, int last, float inv_k, void* stream) {
+    CVK_CHECK_ARG(logits && acc && (pred || !last), "cvk_tta_accumulate: null pointer");
+    CVK_CHECK_ARG(C <= TTA_MAX_C, "cvk_tta_accumulate: %d classes, the kernel holds at most %d per pixel in registers", C, TTA_MAX_C);
+    CVK_CHECK_ARG(N > 0 && H > 0 && W > 0 && h > 0 && w > 0 && C > 0 && ld >= C && H <= TTA_MAX_DIM && W <= TTA_MAX_DIM &&
+                      h <= TTA_MAX_DIM && w <= TTA_MAX_DIM && inv_k > 0.f && inv_k <= 3.0e38f,
+                  "cvk_tta_accumulate: bad arguments");
+    CVK_CHECK_ARG((int64_t)N * H * W * C < 2147483647LL - CE_CHUNK * TTA_MAX_C, "cvk_tta_accumulate: accumulator of 2^31 values or more");
+    const int M = N * H * W, nb = cvk_cdiv(M, CE_CHUNK), CP = (C + 3) / 4 * 4;
+    const size_t lds_bytes = (size_t)CE_CHUNK * (C + 1) * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    const bool ok = h == H && w == W
+                        ? tta_launch<true>(CP, nb, lds_bytes, s, logits, ld, h, w, acc, pred, H, W, M, C, flip, first, last, inv_k)
+                        : tta_launch<false>(CP, nb, lds_bytes, s, logits, ld, h, w, acc, pred, H, W, M, C, flip, first, last, inv_k);
+    CVK_CHECK_ARG(ok, "cvk_tta_accumulate: no kernel for %d classes", C);
+    CVK_LAUNCH_RETURN("cvk_tta_accumulate");
+}
+
+extern "C" int cvk_tta_resize_input(const float* src, int64_t sN, int64_t sC, int64_t sH, int64_t sW, float* dst, int N, int H, int W,
+                                    int h, int w, int flip, void* stream) {
+    CVK_CHECK_ARG(src && dst, "cvk_tta_resize_input: null pointer");
+    CVK_CHECK_ARG(N > 0 && H > 0 && W > 0 && h > 0 && w > 0 && H <= TTA_MAX_DIM && W <= TTA_MAX_DIM && h <= TTA_MAX_DIM && w <= TTA_MAX_DIM &&
+                      cvk_aligned16(dst),
+                  "cvk_tta_resize_input: bad arguments");
+    CVK_CHECK_ARG(N <= 65535, "cvk_tta_resize_input: grid too large");
+    hipLaunchKernelGGL(k_tta_resize_input, dim3(cvk_cdiv(w, 256), h, N), dim3(256), 0, (hipStream_t)stream, src, sN, sC, sH, sW, dst, H, W,
+                       h, w, flip);
+    CVK_LAUNCH_RETURN("cvk_tta_resize_input");
 }
 
 extern "C" int cvk_confusion_accumulate(const int64_t* pred, const int64_t* label, int64_t* hist, int M, int num_classes,

@@ -503,11 +503,168 @@ def preprocess_uint8(images_u8, mean=CAMVID_MEAN, std=CAMVID_STD):
     return dst[..., :3].permute(0, 3, 1, 2)
 
 
+class TestTimeAugmentation:
+    """Multi-scale and horizontal-flip test-time inference, merged on the device (cvk_tta_accumulate, cvk_tta_resize_input).
+
+      tta = TestTimeAugmentation(scales=(0.75, 1.0, 1.25), flip=True, size_divisor=1)
+      probs, pred = tta(net, images)
+
+    For images [N,3,H,W] the views are, in this order, `for s in scales: unflipped, then mirrored (if flip)`, each at
+    h = size_divisor * ceil(floor(H * s + 0.5) / size_divisor) (w likewise), resampled bilinearly (align_corners=False).  Every
+    view's logits, of whatever spatial size the network returns, are resampled to H x W, soft-maxed, mirrored back where the view
+    was mirrored, and averaged: probs = ((p_1 + p_2) + ... + p_K) * float32(1 / K) in view order, pred = its first-maximum arg-max
+    (`torch.equal(pred, argmax_channels(probs))`).  One launch per view does all of that; no resized, soft-maxed or flipped tensor
+    is written, nothing synchronises with the host and no atomics are used, so two runs agree bitwise.  Bilinear weights come from
+    integer arithmetic (include/cvk.h), so they are correctly rounded at any size.
+
+    `probs` is float32 [N,C,H,W], a channels_last view of the accumulator this object keeps per output shape: the next call with
+    that shape overwrites it (clone it to keep it).  `pred` is a fresh int64 [N,H,W].  The network runs in eval mode under no_grad
+    and gets its `training` flag back.  Networks in bf16 mode or with split operands work unchanged (their logits are float32 at
+    the module boundary), and so does a call inside `opt.swap_ema()`.  At most 32 classes.  Every distinct view size is one more
+    cached plan of the network (DESIGN.md states the memory).  A size the network cannot run raises whatever the network raises."""
+
+    __test__ = False                    # the name starts with "Test": not a pytest class
+
+    def __init__(self, scales=(0.75, 1.0, 1.25), flip=True, size_divisor=1):
+        import math
+        try:
+            scales = tuple(float(s) for s in scales)
+        except (TypeError, ValueError):
+            raise ValueError(f"scales must be a non-empty sequence of positive finite numbers. Got: {scales!r}") from None
+        if not scales or not all(math.isfinite(s) and s > 0.0 for s in scales):
+            raise ValueError(f"scales must be a non-empty sequence of positive finite numbers. Got: {scales!r}")
+        if isinstance(size_divisor, bool) or not isinstance(size_divisor, int) or size_divisor < 1:
+            raise ValueError(f"size_divisor must be an integer >= 1. Got: {size_divisor!r}")
+        self.scales, self.flip, self.size_divisor = scales, bool(flip), size_divisor
+        self._acc = {}
+
+    def _plan(self, H, W):
+        """[(scale, h, w, flipped)] in view order."""
+        import math
+        d = self.size_divisor
+        out = []
+        for s in self.scales:
+            h = d * math.ceil(math.floor(H * s + 0.5) / d)
+            w = d * math.ceil(math.floor(W * s + 0.5) / d)
+            if h < 1 or w < 1:
+                raise ValueError(f"scale {s} of a {H} x {W} image leaves no pixel")
+            out.append((s, h, w, False))
+            if self.flip:
+                out.append((s, h, w, True))
+        return out
+
+    def view_sizes(self, H, W):
+        """[(h, w, flipped), ...] in view order for a label size (H, W).  Host arithmetic only."""
+        return [(h, w, f) for _, h, w, f in self._plan(int(H), int(W))]
+
+    def loss_view(self, H, W):
+        """Index of the view evaluate_report takes its loss from: scale 1.0, not mirrored, at the label size; None when there is none."""
+        for i, (s, h, w, f) in enumerate(self._plan(int(H), int(W))):
+            if s == 1.0 and not f and (h, w) == (H, W):
+                return i
+        return None
+
+    @staticmethod
+    def _check_images(images):
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+            raise ValueError("expected float32 images of shape [N, 3, H, W]")
+        if not images.is_cuda:
+            raise RuntimeError("pytorch_camvid_amd.TestTimeAugmentation needs HIP tensors (no CPU fallback)")
+
+    def views(self, images):
+        """The network inputs, in view order (what `tta(net, images)` feeds the network): the scale-1.0 unmirrored view at the image
+        size is `images` itself, every other one a fresh float32 [N,3,h,w] view of an NHWC-4 buffer (as `preprocess_uint8` returns),
+        written by one launch."""
+        self._check_images(images)
+        lib = _lib.load()
+        N, _, H, W = images.shape
+        src = images.detach()
+        for s, h, w, flipped in self._plan(H, W):
+            if s == 1.0 and not flipped and (h, w) == (H, W):
+                yield images
+                continue
+            dst = torch.empty((N, h, w, 4), device=images.device, dtype=torch.float32)
+            check(lib.cvk_tta_resize_input(src.data_ptr(), *src.stride(), dst.data_ptr(), N, H, W, h, w, int(flipped), _stream(images)),
+                  "cvk_tta_resize_input")
+            yield dst[..., :3].permute(0, 3, 1, 2)
+
+    def _merge(self, net, images, on_logits=None):
+        lib = _lib.load()
+        self._check_images(images)
+        N, _, H, W = images.shape
+        plan = self._plan(H, W)
+        K = len(plan)
+        import numpy as np
+        inv_k = float(np.float32(1.0) / np.float32(K))
+        acc = pred = None
+        C = None
+        was_training = net.training
+        net.eval()
+        try:
+            with torch.no_grad():
+                for i, ((s, h, w, flipped), x) in enumerate(zip(plan, self.views(images))):
+                    logits = net(x)
+                    if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
+                        raise ValueError("the network must return logits of shape [N, C, h, w]")
+                    if logits.dtype != torch.float32 or not logits.is_cuda:
+                        raise RuntimeError(f"expected float32 logits on a HIP device, got {logits.dtype} on {logits.device}")
+                    if acc is None:
+                        C = logits.shape[1]
+                        if not 1 <= C <= 32:
+                            raise ValueError(f"pytorch_camvid_amd.TestTimeAugmentation serves 1 to 32 classes, got C = {C}")
+                        key = (N, C, H, W, logits.device)
+                        acc = self._acc.get(key)
+                        if acc is None:
+                            acc = self._acc[key] = torch.empty((N, H, W, C), device=logits.device, dtype=torch.float32)
+                        pred = torch.empty((N, H, W), device=logits.device, dtype=torch.int64)
+                    if logits.shape[0] != N or logits.shape[1] != C or logits.device != acc.device:
+                        raise ValueError(f"view {i} ({h} x {w}{', mirrored' if flipped else ''}): the network returned logits "
+                                         f"{list(logits.shape)} on {logits.device}, the accumulator is {[N, C, H, W]} on {acc.device}")
+                    if on_logits is not None:
+                        on_logits(i, logits)
+                    lg, ld = _as_nhwc(logits.detach())
+                    lh, lw = lg.shape[1], lg.shape[2]
+                    check(lib.cvk_tta_accumulate(lg.data_ptr(), ld, lh, lw, acc.data_ptr(), pred.data_ptr(), N, H, W, C, int(flipped),
+                                                 int(i == 0), int(i == K - 1), inv_k, _stream(logits)), "cvk_tta_accumulate")
+        finally:
+            net.train(was_training)
+        return acc.permute(0, 3, 1, 2), pred
+
+    def __call__(self, net, images):
+        """(probs float32 [N,C,H,W], pred int64 [N,H,W]) of one batch; see the class."""
+        return self._merge(net, images)
+
+
+def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None):
+    """evaluate / evaluate_report with test-time augmentation: (meter, the per-batch losses of the loss view: empty without one)."""
+    meter, losses = None, []
+
+    def keep_loss(masks, want):
+        def on_logits(i, logits):
+            if i == want:
+                losses.append(loss_fn(logits, masks).detach())
+        return on_logits
+
+    for images, masks in batches:
+        want = tta.loss_view(images.shape[2], images.shape[3]) if loss_fn is not None else None
+        _, pred = tta._merge(net, images, keep_loss(masks, want) if want is not None else None)
+        if meter is None:
+            meter = ConfusionMeter(num_classes, ignore_index, pred.device)
+        meter.update(pred, masks)
+    return meter, losses
+
+
 @torch.no_grad()
-def evaluate(net, batches, num_classes=12, ignore_index=11):
+def evaluate(net, batches, num_classes=12, ignore_index=11, tta=None):
     """Validation pass of reference train.py:169-206 / eval.py:44-80 without their bugs: eval-mode forward, device-side
     argmax and histogram accumulation over the WHOLE set, one host copy at the end.
-    `batches` yields (images [N,3,H,W] float32, masks [N,H,W] int64) on the GPU.  Returns (accuracy, per-class IoU, mIoU)."""
+    `batches` yields (images [N,3,H,W] float32, masks [N,H,W] int64) on the GPU.  Returns (accuracy, per-class IoU, mIoU).
+    With `tta` (a TestTimeAugmentation) the prediction of a batch is the arg-max of the views' mean probabilities."""
+    if tta is not None:
+        meter, _ = _evaluate_tta(net, batches, num_classes, ignore_index, tta)
+        if meter is None:
+            raise ValueError("evaluate(): no batches")
+        return meter.compute()
     was_training = net.training
     net.eval()
     meter = None
@@ -522,11 +679,26 @@ def evaluate(net, batches, num_classes=12, ignore_index=11):
     return meter.compute()
 
 
-def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None):
+def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None, tta=None):
     """The report of reference eval.py:44-80: {"miou", "precision", "recall", "loss" (mean over batches), "accuracy",
     "iou" (per class)} for a set of (images, masks) batches on the GPU; eval-mode forward under no_grad, argmax and
-    histograms on the device, one host copy at the end (the reference copies N*H*W int64 per batch, eval.py:60-62)."""
+    histograms on the device, one host copy at the end (the reference copies N*H*W int64 per batch, eval.py:60-62).
+    With `tta` (a TestTimeAugmentation) the predictions are the merged ones and "loss" is `loss_fn` of the logits of the
+    scale-1.0 unmirrored view at the label size: None when that view is not among the views."""
     loss_fn = loss_fn or CrossEntropyLoss()
+    if tta is not None:
+        meter, losses = _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn)
+        if meter is None:
+            raise ValueError("evaluate_report(): no batches")
+        acc, iou, miou = meter.compute()
+        prec, rec = meter.precision_recall()
+        loss = None
+        if losses:
+            loss_sum = losses[0]
+            for l in losses[1:]:
+                loss_sum = loss_sum + l
+            loss = float(loss_sum) / len(losses)
+        return {"miou": miou, "precision": prec, "recall": rec, "loss": loss, "accuracy": acc, "iou": iou}
     was_training = net.training
     net.eval()
     meter, loss_sum, n = None, None, 0
@@ -547,22 +719,26 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None)
     return {"miou": miou, "precision": prec, "recall": rec, "loss": float(loss_sum) / n, "accuracy": acc, "iou": iou}
 
 
-def predict(net, image_u8, out_size=None, mean=CAMVID_MEAN, std=CAMVID_STD):
+def predict(net, image_u8, out_size=None, mean=CAMVID_MEAN, std=CAMVID_STD, tta=None):
     """reference predict.py:35-57 from the decoded image onward: `image_u8` is one uint8 [H, W, 3] frame (BGR, as cv2
     decodes; a CPU or GPU tensor or a numpy array) already at the network's input size; normalisation, eval-mode forward
     and channel argmax run on the device.  Returns the int64 class map [H, W]; with out_size=(h, w) it is resized by
     nearest neighbour the way `cv2.resize(..., INTER_NEAREST)` does (predict.py:55; source index floor(dst * in / out)).
-    Image decoding / PIL resizing to IMAGE_SIZE stay on the host side (cv2 / PIL are not part of this package)."""
+    Image decoding / PIL resizing to IMAGE_SIZE stay on the host side (cv2 / PIL are not part of this package).
+    With `tta` (a TestTimeAugmentation) the class map is the arg-max of the views' mean probabilities."""
     dev = next(net.parameters()).device
     img = torch.as_tensor(image_u8)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[-1] != 3:
         raise ValueError("expected one uint8 image of shape [H, W, 3]")
     x = preprocess_uint8(img.to(dev).unsqueeze(0), mean, std)
-    was_training = net.training
-    net.eval()
-    with torch.no_grad():
-        cls = argmax_channels(net(x))[0]
-    net.train(was_training)
+    if tta is not None:
+        cls = tta(net, x)[1][0]
+    else:
+        was_training = net.training
+        net.eval()
+        with torch.no_grad():
+            cls = argmax_channels(net(x))[0]
+        net.train(was_training)
     if out_size is not None:
         h, w = out_size
         H, W = cls.shape
