@@ -44,10 +44,13 @@ def main():
     ap.add_argument("--class-weights", default="none", choices=["none", "median_frequency", "enet"],
                     help="class-weighted loss, weights from one pass over the training masks (cvk.class_weights)")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
-    ap.add_argument("--loss", default="ce", choices=["ce", "focal", "dice", "ce+dice"],
-                    help="ce: cvk.CrossEntropyLoss (the reference's loss); the others: cvk.SegmentationLoss, one fused pass")
+    ap.add_argument("--loss", default="ce", choices=["ce", "focal", "dice", "ce+dice", "ohem"],
+                    help="ce: cvk.CrossEntropyLoss (the reference's loss); focal, dice, ce+dice: cvk.SegmentationLoss, one fused pass; "
+                         "ohem: cvk.OhemCrossEntropyLoss, online hard example mining")
     ap.add_argument("--focal-gamma", type=float, default=2.0, help="--loss focal: the focusing exponent")
     ap.add_argument("--dice-weight", type=float, default=0.5, help="--loss ce+dice: the Dice term's coefficient")
+    ap.add_argument("--ohem-thresh", type=float, default=0.7, help="--loss ohem: keep the pixels whose target probability is below this")
+    ap.add_argument("--ohem-min-kept", type=int, default=100000, help="--loss ohem: never keep fewer than this many of the hardest pixels")
     ap.add_argument("--graphed", action="store_true", help="cvk.FlatAdamW and the whole iteration as one captured graph (cvk.GraphedStep)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                     help="clip the global gradient 2-norm to X (cvk.clip_grad_norm_; with --graphed: FlatAdamW(max_grad_norm=X), inside the "
@@ -93,8 +96,11 @@ def main():
     else:
         if a.label_smoothing:
             raise SystemExit("--label-smoothing belongs to --loss ce")
-        ce, dice = {"focal": (1.0, 0.0), "dice": (0.0, 1.0), "ce+dice": (1.0, a.dice_weight)}[a.loss]
-        loss_fn = cvk.SegmentationLoss(ce, dice, focal_gamma=a.focal_gamma if a.loss == "focal" else 0.0, weight=weight)
+        if a.loss == "ohem":
+            loss_fn = cvk.OhemCrossEntropyLoss(a.ohem_thresh, a.ohem_min_kept, weight=weight)
+        else:
+            ce, dice = {"focal": (1.0, 0.0), "dice": (0.0, 1.0), "ce+dice": (1.0, a.dice_weight)}[a.loss]
+            loss_fn = cvk.SegmentationLoss(ce, dice, focal_gamma=a.focal_gamma if a.loss == "focal" else 0.0, weight=weight)
     train_tf, valid_tf = transforms.train_transforms(), transforms.valid_transforms()
     step = None
     for epoch in range(1, a.epochs + 1):

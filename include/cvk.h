@@ -492,6 +492,32 @@ int cvk_seg_loss_bwd(const float* logits, int ld, const int64_t* target, const f
                      const float* record, const float* grad_out, float scale, float* dlogits, int ld_d, int M, int C, int ignore_index,
                      void* stream);
 
+/* ---- OHEM cross-entropy: online hard example mining with an on-device k-th-largest select ---------------------------------------
+ * logits: dense NHWC rows [M][ld] (ld >= C, 0 < C <= 128), target int64 [M], weight float [C] nullable (all ones): all DEVICE.
+ * A pixel's loss l = lse - x[t] is the unweighted fp32 cross-entropy (>= 0).  V = the valid pixels (t != ignore_index),
+ * k = min(min_kept, V), L = the k-th largest l over the valid pixels.  A valid pixel is kept iff l > loss_thresh or l >= L (fp32
+ * comparisons): every pixel harder than the threshold, never fewer than the min_kept hardest, ties at the boundary all kept.
+ *   loss = sum_kept w[t] l / sum_kept w[t]                       (V = 0: 0/0 = NaN)
+ * loss_thresh = -log(probability threshold) >= 0 and finite; min_kept >= 1.  Any target outside [0, C) other than ignore_index
+ * makes the loss NaN and is counted, as in cvk_softmax_ce_fwd.
+ * fwd: `scratch` is DEVICE memory of cvk_ohem_scratch_bytes(M) bytes (cleared by the call itself, on the stream); `record` is DEVICE
+ * float[cvk_ohem_record_floats()] = float[8]: [0] = loss, [1] = V, [2] = out-of-range targets, [3] = sum_kept w[t], [4] = kept
+ * pixels, [5] = L, [6] = loss_thresh, [7] = k (counts stored as floats are exact up to 2^24 pixels); loss_px: DEVICE float [M],
+ * required: l per pixel, -1 where ignored, NaN where the target is out of range.  L is exact: a three-level radix select (11 + 10 +
+ * 10 bits) over the bit patterns of l with integer histogram atomics; no float atomics, every float sum in one fixed order (bitwise
+ * reproducible), no allocation, no host sync.  Ranks and counts are 32-bit.
+ * bwd: record and loss_px are fwd's; dlogits [M][ld_d] = g w[t] / record[3] (softmax(x) - onehot(t)) on the kept rows,
+ * g = grad_out * scale; grad_out: one DEVICE float, nullable (1).  The kept predicate is re-evaluated from loss_px, record[5] and
+ * record[6], so it cannot differ from the forward's.  Rows that are not kept, ignored or out of range and columns [C, ld_d) are
+ * written as zeros. */
+int cvk_ohem_scratch_bytes(int M);
+int cvk_ohem_record_floats(void);
+int cvk_ohem_ce_fwd(const float* logits, int ld, const int64_t* target, const float* weight, float loss_thresh, int min_kept,
+                    void* scratch, float* record, float* loss_px, int M, int C, int ignore_index, void* stream);
+int cvk_ohem_ce_bwd(const float* logits, int ld, const int64_t* target, const float* weight, const float* record,
+                    const float* loss_px, const float* grad_out, float scale, float* dlogits, int ld_d, int M, int C, int ignore_index,
+                    void* stream);
+
 /* ---- class statistics of label masks (class weights for the loss above; SegNet's median-frequency balancing) ----------
  * masks: DEVICE [N][HW] of mask_bytes = 1 (uint8) or 8 (int64) per label (cvk_augment_u8's convention); 0 < num_classes <= 256.
  * Accumulates into DEVICE int64 hist[2 * num_classes + 1] (the caller zeroes it once): hist[c] += pixels of class c,

@@ -186,6 +186,10 @@ SIGNATURES = {
     "cvk_seg_loss_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_float, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "cvk_seg_loss_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_vp, c_vp, c_float, c_vp, c_int, c_int, c_int, c_int,
                                  c_vp]),
+    "cvk_ohem_scratch_bytes": (c_int, [c_int]),
+    "cvk_ohem_record_floats": (c_int, []),
+    "cvk_ohem_ce_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "cvk_ohem_ce_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_float, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "cvk_class_histogram": (c_int, [c_vp, c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp]),
     "cvk_argmax_channels": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp]),
     "cvk_confusion_accumulate": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

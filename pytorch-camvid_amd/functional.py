@@ -336,6 +336,157 @@ def segmentation_loss(logits, target, ce=1.0, dice=0.0, *, focal_gamma=0.0, weig
     return _SegLoss.apply(logits, target, weight, (opts[0], opts[1], opts[2], opts[3], dice_average, ignore_index, 1.0))
 
 
+OHEM_RECORD = 8                                    # loss | V | out of range | sum_kept w[t] | kept | L | lambda | k
+
+
+def ohem_loss_threshold(thresh):
+    """The loss boundary of a probability threshold: float32(-log(thresh)), the logarithm taken in double and rounded once.  A pixel
+    whose target probability is below `thresh` has a loss above it."""
+    import math
+    import numpy as np
+    thresh = float(thresh)
+    if not 0.0 < thresh <= 1.0:
+        raise ValueError(f"thresh must be a probability in (0, 1]. Got: {thresh}")
+    return float(np.float32(-math.log(thresh)))
+
+
+def _check_ohem_options(thresh, min_kept, weight):
+    lam = ohem_loss_threshold(thresh)
+    if isinstance(min_kept, bool) or not isinstance(min_kept, int) or min_kept < 1:
+        raise ValueError(f"min_kept must be an integer >= 1. Got: {min_kept!r}")
+    if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dim() != 1):
+        raise ValueError("weight must be a 1-D tensor of one value per class")
+    return lam, min(min_kept, 2 ** 31 - 1)
+
+
+class _OhemCrossEntropy(torch.autograd.Function):
+    """Online hard example mining over the per-pixel cross-entropy (cvk_ohem_ce_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, opts):
+        lam, min_kept, ignore_index, grad_scale = opts
+        lib = _lib.load()
+        if not logits.is_cuda:
+            raise RuntimeError("pytorch_camvid_amd.OhemCrossEntropyLoss needs HIP tensors (no CPU fallback)")
+        if logits.dtype != torch.float32 or target.dtype != torch.int64:
+            raise RuntimeError(f"expected float32 logits and int64 target, got {logits.dtype} / {target.dtype}")
+        N, C, H, W = logits.shape
+        if tuple(target.shape) != (N, H, W):
+            raise ValueError(f"Expected target size {[N, H, W]}, got {list(target.shape)}")
+        if weight is not None:
+            if weight.dim() != 1 or weight.numel() != C:
+                raise RuntimeError(f"weight tensor should be defined either for all {C} classes or no classes but got weight tensor "
+                                   f"of shape: {list(weight.shape)}")
+            if weight.device != logits.device:
+                raise RuntimeError(f"weight is on {weight.device} but the logits are on {logits.device} (no implicit copy: the loss "
+                                   "stays capturable); move the loss module with .to(device)")
+            if weight.dtype != torch.float32:
+                raise RuntimeError(f"expected a float32 weight, got {weight.dtype}")
+            weight = weight.detach().contiguous()
+        lg, ld = _as_nhwc(logits)
+        tg = target.contiguous()
+        M = N * H * W
+        nbytes = lib.cvk_ohem_scratch_bytes(M)
+        if nbytes <= 0 or not 1 <= C <= 128:
+            raise RuntimeError(f"pytorch_camvid_amd.OhemCrossEntropyLoss serves 1 to 128 classes and a non-empty batch, got C = {C}, M = {M}")
+        scratch = torch.empty(nbytes, device=logits.device, dtype=torch.uint8)
+        rec = torch.empty(lib.cvk_ohem_record_floats(), device=logits.device, dtype=torch.float32)
+        px = torch.empty((N, H, W), device=logits.device, dtype=torch.float32)
+        wp = weight.data_ptr() if weight is not None else None
+        from . import engine
+        engine._timed(None, "k_ohem_fwd", 4.0 * M * ld + 8.0 * M + 16.0 * M, lambda: check(
+            lib.cvk_ohem_ce_fwd(lg.data_ptr(), ld, tg.data_ptr(), wp, lam, min_kept, scratch.data_ptr(), rec.data_ptr(), px.data_ptr(),
+                                M, C, int(ignore_index), _stream(logits)), "cvk_ohem_ce_fwd"), "byte")
+        ctx.save_for_backward(lg, tg, rec, px, weight)
+        ctx.meta = (N, C, H, W, ld, float(grad_scale), int(ignore_index))
+        _CrossEntropy.last_status = rec
+        _OhemCrossEntropy.last_pixel_loss = px
+        return rec[0].clone()           # not a view: rec is saved for backward (divisor, L, lambda) and published as the status
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        lg, tg, rec, px, weight = ctx.saved_tensors
+        N, C, H, W, ld, grad_scale, ignore_index = ctx.meta
+        M = N * H * W
+        d = torch.empty((N, H, W, C), device=lg.device, dtype=torch.float32)
+        g = gout.contiguous()
+        wp = weight.data_ptr() if weight is not None else None
+        from . import engine
+        engine._timed(None, "k_ohem_bwd", 4.0 * M * ld + 12.0 * M + 4.0 * M * C, lambda: check(
+            lib.cvk_ohem_ce_bwd(lg.data_ptr(), ld, tg.data_ptr(), wp, rec.data_ptr(), px.data_ptr(), g.data_ptr(), grad_scale,
+                                d.data_ptr(), C, M, C, ignore_index, _stream(lg)), "cvk_ohem_ce_bwd"), "byte")
+        return d.permute(0, 3, 1, 2), None, None, None
+
+
+class OhemCrossEntropyLoss(nn.Module):
+    """Cross-entropy with online hard example mining as one autograd node (the rule of HRNet/OCR's OhemCrossEntropy and mmseg's
+    OHEMPixelSampler): train on the pixels whose target probability is below `thresh`, and never on fewer than the `min_kept` hardest.
+    With l = lse(x) - x[t] the unweighted fp32 loss of a valid pixel (t != `ignore_index`), V the number of valid pixels,
+    lambda = `ohem_loss_threshold(thresh)` and L the min(min_kept, V)-th largest l, a valid pixel is kept iff l > lambda or l >= L:
+      loss = sum_kept w[t] l / sum_kept w[t]
+    Ties at the boundary are all kept, so at least min(min_kept, V) pixels always are.  (HRNet and mmseg take element `min_kept` of the
+    ascending sort and compare strictly: a batch whose losses are all equal keeps nothing there and gives NaN; the two rules differ by
+    at most the ties at the boundary.)  L is found on the device by an exact three-level radix select over the bit patterns of the
+    losses: no sort, no compaction, no host sync, so the loss can be captured by `GraphedStep`; every float sum has one fixed order, so
+    the loss and its gradient are bitwise reproducible.  The backward re-evaluates the predicate from the forward's saved loss map.
+    Conventions of CrossEntropyLoss hold: float32 logits [N, C, H, W] (C <= 128), int64 targets [N, H, W], a 0-dim loss, `weight`
+    (float32 [C], a registered buffer) weighs the kept pixels' mean, an out-of-range target makes the loss NaN and `last_ce_status()`
+    reports it, no valid pixel gives 0/0 = NaN with a zero gradient, `grad_scale` multiplies the backward only.
+    After a forward, device views for logging without a sync: `last_record` ([loss, V, out of range, sum_kept w[t], kept, L, lambda,
+    k]), `last_kept`, `last_threshold` (min(lambda, L): a valid pixel is kept iff its loss reaches it, up to the strictness at lambda) and
+    `last_pixel_loss` ([N, H, W], -1 where ignored).  Under `ddp.DataParallel` every rank selects over its own part of the batch, as
+    the Dice sums of SegmentationLoss are per rank."""
+
+    def __init__(self, thresh=0.7, min_kept=100000, *, weight=None, ignore_index=-100, grad_scale=1.0):
+        super().__init__()
+        self.loss_threshold, self.min_kept = _check_ohem_options(thresh, min_kept, weight)
+        self.thresh = float(thresh)
+        self.ignore_index = ignore_index
+        self.grad_scale = grad_scale
+        self.register_buffer("weight", weight)
+        self._record = self._px = None
+
+    def forward(self, logits, target):
+        loss = _OhemCrossEntropy.apply(logits, target, self.weight, (self.loss_threshold, self.min_kept, self.ignore_index,
+                                                                     self.grad_scale))
+        self._record, self._px = _CrossEntropy.last_status, _OhemCrossEntropy.last_pixel_loss
+        return loss
+
+    def _rec(self):
+        if self._record is None:
+            raise RuntimeError("no forward has run yet")
+        return self._record
+
+    @property
+    def last_record(self):
+        """The device record of the most recent forward (float32 [8], no sync)."""
+        return self._rec()
+
+    @property
+    def last_kept(self):
+        """Number of kept pixels of the most recent forward (0-dim device view, no sync)."""
+        return self._rec()[4]
+
+    @property
+    def last_threshold(self):
+        """The effective loss boundary min(lambda, L) of the most recent forward (0-dim device tensor, no sync)."""
+        r = self._rec()
+        return torch.minimum(r[5], r[6])
+
+    @property
+    def last_pixel_loss(self):
+        """The unweighted per-pixel losses of the most recent forward: [N, H, W], -1 where ignored, NaN where out of range."""
+        self._rec()
+        return self._px
+
+
+def ohem_cross_entropy(logits, target, thresh, min_kept, weight=None, ignore_index=-100):
+    """Functional form of OhemCrossEntropyLoss (same kernels)."""
+    lam, min_kept = _check_ohem_options(thresh, min_kept, weight)
+    return _OhemCrossEntropy.apply(logits, target, weight, (lam, min_kept, ignore_index, 1.0))
+
+
 def last_ce_status():
     """(valid pixels, out-of-range targets) of the most recent cross-entropy forward — one device->host copy; raises
     IndexError like torch's `Target out of bounds` when the second number is not zero."""
