@@ -1208,8 +1208,8 @@ __global__ __launch_bounds__(256) void k_confusion(const int64_t* __restrict__ p
     for (int i = threadIdx.x; i < 3 * K; i += blockDim.x) h[i] = 0;
     __syncthreads();
     for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
-        const int l = (int)label[m], p = (int)pred[m];
-        if (l == ignore) continue;
+        const int64_t l = label[m], p = pred[m];  // compared as 64-bit values: 2^32 + c is no class and 2^32 + ignore not the ignore index
+        if (l == (int64_t)ignore) continue;
         if (p >= 0 && p < K) {
             atomicAdd(&h[K + p], 1u);
             if (p == l) atomicAdd(&h[p], 1u);
