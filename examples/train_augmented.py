@@ -65,13 +65,27 @@ def main():
     ap.add_argument("--tta-scales", default=None, metavar="S,S,...",
                     help="validate with multi-scale test-time augmentation at these scales, e.g. 0.75,1.0,1.25 (cvk.TestTimeAugmentation)")
     ap.add_argument("--tta-flip", action="store_true", help="also validate on the mirrored views (alone: scale 1.0 and its mirror image)")
+    ap.add_argument("--window-crop", default=None, metavar="H,W",
+                    help="validate by sliding-window inference with crops of this size, e.g. 360,480 (cvk.SlidingWindow); with --tta-scales / "
+                    "--tta-flip every view is evaluated in windows")
+    ap.add_argument("--window-stride", default=None, metavar="H,W", help="with --window-crop: the step between windows (default: two thirds of the crop)")
     a = ap.parse_args()
-    tta = None
+    tta = window = None
+    if a.window_stride and not a.window_crop:
+        ap.error("--window-stride needs --window-crop")
+    if a.window_crop:
+        try:
+            crop = tuple(int(v) for v in a.window_crop.split(","))
+            stride = tuple(int(v) for v in a.window_stride.split(",")) if a.window_stride else tuple(max(1, 2 * c // 3) for c in crop)
+            window = cvk.SlidingWindow(crop=crop, stride=stride)
+        except ValueError as e:
+            ap.error(f"--window-crop / --window-stride: {e}")
     if a.tta_scales or a.tta_flip:
         try:
-            tta = cvk.TestTimeAugmentation(scales=[float(v) for v in (a.tta_scales or "1.0").split(",")], flip=a.tta_flip)
+            tta = cvk.TestTimeAugmentation(scales=[float(v) for v in (a.tta_scales or "1.0").split(",")], flip=a.tta_flip, window=window)
         except ValueError as e:
             ap.error(f"--tta-scales: {e}")
+        window = None                   # the views are evaluated in windows: evaluate() takes tta= or window=, not both
     if (a.ema_decay is not None or a.ema_warmup) and not a.graphed:
         ap.error("--ema-decay / --ema-warmup need --graphed (the average lives in FlatAdamW's flat buffers)")
     if a.ema_warmup and a.ema_decay is None:
@@ -141,12 +155,12 @@ def main():
             print(f"  grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of {n.numel()} steps "
                   f"(max_norm {a.clip_grad_norm:g})")
         val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
-        acc, iou, miou = cvk.evaluate(net, val, num_classes=12, ignore_index=11, tta=tta)
+        acc, iou, miou = cvk.evaluate(net, val, num_classes=12, ignore_index=11, tta=tta, window=window)
         print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
                 val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)    # the same frames again
-                acc_e, _, miou_e = cvk.evaluate(net, val, num_classes=12, ignore_index=11, tta=tta)
+                acc_e, _, miou_e = cvk.evaluate(net, val, num_classes=12, ignore_index=11, tta=tta, window=window)
             print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
 
 

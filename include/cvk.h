@@ -557,6 +557,28 @@ int cvk_tta_accumulate(const float* logits, int ld, int h, int w, float* acc, in
 int cvk_tta_resize_input(const float* src, int64_t sN, int64_t sC, int64_t sH, int64_t sW, float* dst, int N, int H, int W, int h, int w,
                          int flip, void* stream);
 
+/* ---- sliding-window inference: the merge of overlapping windows' logits (not in the reference) --------------------------
+ * The grid of an H x W image for a crop (hc, wc) and a stride (sy, sx), 1 <= sy <= hc, 1 <= sx <= wc (the rule of mmseg's
+ * mode='slide'): window height hw = min(hc, H), gy = (max(H - hc, 0) + sy - 1) / sy + 1 window rows, row i starts at
+ * y1(i) = min(i * sy, H - hw); columns likewise (ww, gx, x1).  All windows are hw x ww, the last row / column is pulled back inside
+ * the image, no two windows coincide and every pixel is covered.  The windows that hold pixel (y, x) are grid rows lo_y..hi_y times
+ * grid columns lo_x..hi_x with lo_y = y < hw ? 0 : min((y - hw) / sy + 1, gy - 1), hi_y = y >= H - hw ? gy - 1 : y / sy (x likewise),
+ * cnt = (hi_y - lo_y + 1) * (hi_x - lo_x + 1) of them.
+ *
+ * cvk_window_merge, one call per window in row-major order of (iy, ix) on one stream: logits are window (iy, ix)'s dense NHWC rows
+ * [N][hw][ww][ld] (ld >= C; the padding is never read into a result), out is dense float [N][H][W][C], pred int64 [N][H][W] or NULL.
+ * Per pixel of the window, at image position (y, x) = (y1(iy) + wy, x1(ix) + wx), with l its logits:
+ *   (iy, ix) == (lo_y, lo_x): out = l (out is not read: the caller never clears it), else out += l;
+ *   (iy, ix) == (hi_y, hi_x): the pixel is finished: out = (that sum) / float(cnt), one correctly rounded fp32 division, and with
+ *                             pred non-NULL pred = the first-maximum channel of exactly the values stored (a NaN wins, as in
+ *                             cvk_argmax_channels).
+ * Pixels outside the window are untouched.  Every sum runs in window order, no atomics, no memset: the result is bitwise
+ * reproducible, and where cnt == 1 it is bitwise the window's logits.  1 <= C <= 32, sizes up to 16384 per side,
+ * N * H * W * C < 2^31; a stride outside 1..crop or (iy, ix) outside the grid is CVK_EINVAL.  C % 4 == 0 with ld % 4 == 0 and
+ * 16-byte aligned pointers moves 16-byte vectors; anything else takes scalar paths.  One launch, no allocation, no host sync. */
+int cvk_window_merge(const float* logits, int ld, float* out, int64_t* pred, int N, int H, int W, int C, int hc, int wc, int sy, int sx,
+                     int iy, int ix, void* stream);
+
 /* ---- input pipeline on device (transforms.ToTensor + Normalize: transforms.py:485-538, MEAN/STD conf/settings.py:8-9) ----
  * src uint8 [N,H,W,3] (channel order as decoded, i.e. cv2 BGR) -> dst float32 NHWC with ld = 4 (pad channel 0):
  * dst[c] = (src[c]/255 - mean3[c]) / std3[c].  mean3 / std3 are HOST pointers to 3 floats. */

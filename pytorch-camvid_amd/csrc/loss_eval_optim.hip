@@ -1202,6 +1202,111 @@ __global__ __launch_bounds__(256) void k_tta_resize_input(const float* __restric
     *reinterpret_cast<f32x4*>(dst + (((size_t)n * h + y) * w + x) * 4) = o;
 }
 
+// ---- sliding-window inference: the merge of overlapping windows' logits (cvk_window_merge) ---------------------------------------
+// One launch per window folds that window's logits into the full-size map: a workgroup owns CE_CHUNK consecutive pixels of the window
+// (a contiguous span of 256 ld floats of the logits; in `out` one contiguous span of C floats per window row it touches).  The pass is
+// element-wise, so it runs in the order of the floats, not one pixel per thread: consecutive lanes move consecutive 16-byte vectors of
+// both sides (full lines, as ce_chunk_load / ce_chunk_store move theirs), and a pixel's terms — where it lies in `out`, how many windows
+// cover it, whether this window is the first or the last of them — come from a table in LDS that the pixel's thread fills once.  Those
+// terms are integer closed forms of the grid (include/cvk.h), divided out per window row (tabulated by the workgroup's first threads, as
+// k_tta_accumulate tabulates its row taps) and per column, never per channel.  Only the values of the pixels this window finishes go
+// through LDS (pitch C + 1), for the arg-max: one thread per finished pixel walks its row with a scalar running best.
+struct WinGrid {
+    int H, W, hw, ww, sy, sx, gy, gx, iy, ix, y1, x1;
+};
+
+struct WinCover {
+    int lo, hi;                          // first / last grid index whose window holds the position
+};
+
+// windows of `win` positions at min(i * stride, size - win), i < g, stride <= win: the i whose window holds position p
+__device__ __forceinline__ WinCover win_cover(int p, int size, int win, int stride, int g) {
+    WinCover c;
+    c.lo = p < win ? 0 : min((p - win) / stride + 1, g - 1);
+    c.hi = p >= size - win ? g - 1 : p / stride;
+    return c;
+}
+
+constexpr int WIN_FIRST = 1, WIN_LAST = 2;
+
+__global__ __launch_bounds__(CE_CHUNK) void k_window_merge(const float* __restrict__ logits, int ld, float* __restrict__ out,
+                                                          int64_t* __restrict__ pred, int M, int C, WinGrid g) {
+    extern __shared__ float lds[];       // the finished pixels' values, pitch C + 1 (no bytes when pred is null)
+    __shared__ int s_row_pix[CE_CHUNK], s_row_cnt[CE_CHUNK], s_row_fl[CE_CHUNK];   // the window rows this workgroup touches (at most CE_CHUNK, at ww = 1)
+    __shared__ int s_pix[CE_CHUNK], s_cnt[CE_CHUNK], s_fl[CE_CHUNK];               // its pixels: index in out / pred, count, WIN_FIRST | WIN_LAST
+    const int pitch = C + 1;
+    const int m0 = blockIdx.x * CE_CHUNK;
+    const int rows = min(CE_CHUNK, M - m0);
+    const int r0 = m0 / g.ww;                                 // uniform: first of the [N * hw] window rows this workgroup touches
+    const int nrows = (m0 + rows - 1) / g.ww - r0 + 1;
+    for (int r = threadIdx.x; r < nrows; r += CE_CHUNK) {
+        const int wr = r0 + r, n = wr / g.hw, y = g.y1 + (wr - n * g.hw);
+        const WinCover cy = win_cover(y, g.H, g.hw, g.sy, g.gy);
+        s_row_pix[r] = (n * g.H + y) * g.W + g.x1;
+        s_row_cnt[r] = cy.hi - cy.lo + 1;
+        s_row_fl[r] = (g.iy == cy.lo ? WIN_FIRST : 0) | (g.iy == cy.hi ? WIN_LAST : 0);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < rows) {
+        // (row, column) of pixel m0 + threadIdx.x relative to row r0: off < ww + CE_CHUNK < 2^24, so the fp32 quotient is off by one at most
+        const int off = m0 - r0 * g.ww + (int)threadIdx.x;
+        int q = (int)((float)off * (1.f / (float)g.ww));
+        int x = off - q * g.ww;
+        if (x < 0) { x += g.ww; --q; } else if (x >= g.ww) { x -= g.ww; ++q; }
+        const WinCover cx = win_cover(g.x1 + x, g.W, g.ww, g.sx, g.gx);
+        s_pix[threadIdx.x] = s_row_pix[q] + x;
+        s_cnt[threadIdx.x] = s_row_cnt[q] * (cx.hi - cx.lo + 1);
+        s_fl[threadIdx.x] = s_row_fl[q] & ((g.ix == cx.lo ? WIN_FIRST : 0) | (g.ix == cx.hi ? WIN_LAST : 0));
+    }
+    __syncthreads();
+    const float* lg = logits + (size_t)m0 * ld;
+    if ((C & 3) == 0 && (ld & 3) == 0 && (((uintptr_t)logits | (uintptr_t)out) & 15u) == 0) {       // uniform
+        const int nv = C >> 2;
+        for (int v = threadIdx.x; v < rows * nv; v += CE_CHUNK) {
+            const int p = v / nv, c = (v - p * nv) * 4;
+            const int fl = s_fl[p];
+            f32x4 s = *reinterpret_cast<const f32x4*>(lg + (size_t)p * ld + c);
+            float* o = out + (size_t)s_pix[p] * C + c;
+            if (!(fl & WIN_FIRST)) s = *reinterpret_cast<const f32x4*>(o) + s;
+            if (fl & WIN_LAST) {
+                const float d = (float)s_cnt[p];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s[k] = __fdiv_rn(s[k], d);
+                if (pred) {
+                    float* q = lds + p * pitch + c;
+                    q[0] = s[0]; q[1] = s[1]; q[2] = s[2]; q[3] = s[3];
+                }
+            }
+            *reinterpret_cast<f32x4*>(o) = s;
+        }
+    } else {
+        for (int f = threadIdx.x; f < rows * C; f += CE_CHUNK) {
+            const int p = f / C, c = f - p * C;
+            const int fl = s_fl[p];
+            float s = lg[(size_t)p * ld + c];
+            float* o = out + (size_t)s_pix[p] * C + c;
+            if (!(fl & WIN_FIRST)) s = *o + s;
+            if (fl & WIN_LAST) {
+                s = __fdiv_rn(s, (float)s_cnt[p]);
+                if (pred) lds[p * pitch + c] = s;
+            }
+            *o = s;
+        }
+    }
+    if (!pred) return;                                        // uniform
+    __syncthreads();
+    if ((int)threadIdx.x < rows && (s_fl[threadIdx.x] & WIN_LAST)) {
+        const float* p = lds + threadIdx.x * pitch;
+        float best = p[0];
+        int bi = 0;
+        for (int c = 1; c < C; ++c) {
+            const float v = p[c];
+            if (v > best || (v != v && best == best)) { best = v; bi = c; }       // k_argmax's rule on the stored values
+        }
+        pred[s_pix[threadIdx.x]] = bi;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_confusion(const int64_t* __restrict__ pred, const int64_t* __restrict__ label,
                                                   unsigned long long* __restrict__ hist, int M, int K, int ignore) {
     extern __shared__ unsigned int h[];  // [3][K]
@@ -1968,6 +2073,32 @@ extern "C" int cvk_tta_resize_input(const float* src, int64_t sN, int64_t sC, in
     hipLaunchKernelGGL(k_tta_resize_input, dim3(cvk_cdiv(w, 256), h, N), dim3(256), 0, (hipStream_t)stream, src, sN, sC, sH, sW, dst, H, W,
                        h, w, flip);
     CVK_LAUNCH_RETURN("cvk_tta_resize_input");
+}
+
+extern "C" int cvk_window_merge(const float* logits, int ld, float* out, int64_t* pred, int N, int H, int W, int C, int hc, int wc,
+                                int sy, int sx, int iy, int ix, void* stream) {
+    CVK_CHECK_ARG(logits && out, "cvk_window_merge: null pointer");
+    CVK_CHECK_ARG(C <= TTA_MAX_C, "cvk_window_merge: %d classes, the kernel serves at most %d", C, TTA_MAX_C);
+    CVK_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && ld >= C && hc > 0 && wc > 0 && H <= TTA_MAX_DIM && W <= TTA_MAX_DIM &&
+                      hc <= TTA_MAX_DIM && wc <= TTA_MAX_DIM,
+                  "cvk_window_merge: bad arguments");
+    CVK_CHECK_ARG(sy >= 1 && sy <= hc && sx >= 1 && sx <= wc, "cvk_window_merge: stride (%d, %d) outside 1..crop (%d, %d)", sy, sx, hc, wc);
+    CVK_CHECK_ARG((int64_t)N * H * W * C < 2147483647LL, "cvk_window_merge: output of 2^31 values or more");
+    WinGrid g;
+    g.H = H; g.W = W; g.sy = sy; g.sx = sx; g.iy = iy; g.ix = ix;
+    g.hw = hc < H ? hc : H;
+    g.ww = wc < W ? wc : W;
+    g.gy = (H - g.hw + sy - 1) / sy + 1;
+    g.gx = (W - g.ww + sx - 1) / sx + 1;
+    CVK_CHECK_ARG(iy >= 0 && iy < g.gy && ix >= 0 && ix < g.gx, "cvk_window_merge: window (%d, %d) outside the %d x %d grid", iy, ix, g.gy,
+                  g.gx);
+    g.y1 = iy * sy < H - g.hw ? iy * sy : H - g.hw;
+    g.x1 = ix * sx < W - g.ww ? ix * sx : W - g.ww;
+    const int M = N * g.hw * g.ww;
+    const size_t lds_bytes = pred ? (size_t)CE_CHUNK * (C + 1) * sizeof(float) : 0;
+    hipLaunchKernelGGL(k_window_merge, dim3(cvk_cdiv(M, CE_CHUNK)), dim3(CE_CHUNK), lds_bytes, (hipStream_t)stream, logits, ld, out, pred, M, C,
+                       g);
+    CVK_LAUNCH_RETURN("cvk_window_merge");
 }
 
 extern "C" int cvk_confusion_accumulate(const int64_t* pred, const int64_t* label, int64_t* hist, int M, int num_classes,

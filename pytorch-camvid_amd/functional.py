@@ -654,6 +654,127 @@ def preprocess_uint8(images_u8, mean=CAMVID_MEAN, std=CAMVID_STD):
     return dst[..., :3].permute(0, 3, 1, 2)
 
 
+def _check_images(who, images):
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError("expected float32 images of shape [N, 3, H, W]")
+    if not images.is_cuda:
+        raise RuntimeError(f"pytorch_camvid_amd.{who} needs HIP tensors (no CPU fallback)")
+
+
+def _int_pair(name, v):
+    ok = isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, int) and not isinstance(e, bool) and e >= 1 for e in v)
+    if not ok:
+        raise ValueError(f"{name} must be a pair of positive integers (height, width). Got: {v!r}")
+    return int(v[0]), int(v[1])
+
+
+class SlidingWindow:
+    """Sliding-window inference: the network runs on overlapping crops of an image of any size and the windows' logits are averaged
+    where they overlap, merged on the device (cvk_window_merge).
+
+      sw = SlidingWindow(crop=(360, 480), stride=(240, 320))
+      logits, pred = sw(net, images)
+
+    The grid is the one of mmseg's mode='slide' (include/cvk.h): for images [N,3,H,W] the windows are hw x ww = min(crop, image) per
+    side, (max(H - hc, 0) + sy - 1) // sy + 1 rows of them starting at min(i * sy, H - hw) (columns likewise), visited in row-major
+    order; the last row and column are pulled back inside the image, never padded.  A window's network input is the view
+    images[:, :, y1:y1+hw, x1:x1+ww] (no copy: the network's import reads any strides).  One launch per window adds its logits into
+    the full-size map; the launch of the last window that covers a pixel divides by the pixel's window count and takes the arg-max:
+    logits = ((l_1 + l_2) + ...) / float32(count) in visiting order, pred = its first-maximum arg-max
+    (`torch.equal(pred, argmax_channels(logits))`).  No count matrix, cleared buffer, atomics or host synchronisation, so two runs
+    agree bitwise, and where one window covers a pixel the value is that window's logit bit for bit.
+
+    `logits` is float32 [N,C,H,W], a channels_last view of the buffer this object keeps per (N, C, H, W, device): the next call with
+    that shape overwrites it (clone it to keep it).  `pred` is a fresh int64 [N,H,W].  The network runs in eval mode under no_grad and
+    gets its `training` flag back.  Networks in bf16 mode or with split operands work unchanged (their logits are float32 at the module
+    boundary), and so does a call inside `opt.swap_ema()`.  At most 32 classes.  One cached plan of the network, at the window size,
+    serves every image size.  A size the network cannot run raises whatever the network raises."""
+
+    def __init__(self, crop=(360, 480), stride=(240, 320)):
+        self.crop, self.stride = _int_pair("crop", crop), _int_pair("stride", stride)
+        if self.stride[0] > self.crop[0] or self.stride[1] > self.crop[1]:
+            raise ValueError(f"stride must not exceed crop (pixels between two windows would be skipped). Got: stride {self.stride}, "
+                             f"crop {self.crop}")
+        self._out = {}
+
+    def _grid(self, H, W):
+        """(hw, ww, [y1 per grid row], [x1 per grid column])."""
+        H, W = int(H), int(W)
+        if H < 1 or W < 1:
+            raise ValueError(f"an image of {H} x {W} has no pixel")
+        (hc, wc), (sy, sx) = self.crop, self.stride
+        hw, ww = min(hc, H), min(wc, W)
+        gy, gx = (H - hw + sy - 1) // sy + 1, (W - ww + sx - 1) // sx + 1
+        return hw, ww, [min(i * sy, H - hw) for i in range(gy)], [min(j * sx, W - ww) for j in range(gx)]
+
+    def windows(self, H, W):
+        """[(y1, x1, hw, ww), ...] in visiting order (row-major) for an image size (H, W).  Host arithmetic only."""
+        hw, ww, ys, xs = self._grid(H, W)
+        return [(y1, x1, hw, ww) for y1 in ys for x1 in xs]
+
+    def counts(self, H, W):
+        """int64 [H, W]: how many windows cover each pixel.  Host arithmetic only."""
+        hw, ww, ys, xs = self._grid(H, W)
+        cy, cx = torch.zeros(int(H), dtype=torch.int64), torch.zeros(int(W), dtype=torch.int64)
+        for y1 in ys:
+            cy[y1:y1 + hw] += 1
+        for x1 in xs:
+            cx[x1:x1 + ww] += 1
+        return cy[:, None] * cx[None, :]
+
+    def _merge(self, net, images, want_pred):
+        lib = _lib.load()
+        _check_images("SlidingWindow", images)
+        N, _, H, W = images.shape
+        hw, ww, ys, xs = self._grid(H, W)
+        (hc, wc), (sy, sx) = self.crop, self.stride
+        out = pred = None
+        C = None
+        was_training = net.training
+        net.eval()
+        try:
+            with torch.no_grad():
+                for iy, y1 in enumerate(ys):
+                    for ix, x1 in enumerate(xs):
+                        logits = net(images[:, :, y1:y1 + hw, x1:x1 + ww])
+                        if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
+                            raise ValueError("the network must return logits of shape [N, C, h, w]")
+                        if logits.dtype != torch.float32 or not logits.is_cuda:
+                            raise RuntimeError(f"expected float32 logits on a HIP device, got {logits.dtype} on {logits.device}")
+                        if out is None:
+                            C = logits.shape[1]
+                            if not 1 <= C <= 32:
+                                raise ValueError(f"pytorch_camvid_amd.SlidingWindow serves 1 to 32 classes, got C = {C}")
+                            key = (N, C, H, W, logits.device)
+                            out = self._out.get(key)
+                            if out is None:
+                                out = self._out[key] = torch.empty((N, H, W, C), device=logits.device, dtype=torch.float32)
+                            if want_pred:
+                                pred = torch.empty((N, H, W), device=logits.device, dtype=torch.int64)
+                        if tuple(logits.shape) != (N, C, hw, ww) or logits.device != out.device:
+                            raise ValueError(f"window ({iy}, {ix}) at ({y1}, {x1}): the network returned logits {list(logits.shape)} on "
+                                             f"{logits.device}, the merge expects {[N, C, hw, ww]} on {out.device}")
+                        lg, ld = _as_nhwc(logits.detach())
+                        check(lib.cvk_window_merge(lg.data_ptr(), ld, out.data_ptr(), pred.data_ptr() if want_pred else None, N, H, W, C,
+                                                   hc, wc, sy, sx, iy, ix, _stream(logits)), "cvk_window_merge")
+        finally:
+            net.train(was_training)
+        return out.permute(0, 3, 1, 2), pred
+
+    def __call__(self, net, images):
+        """(logits float32 [N,C,H,W], pred int64 [N,H,W]) of one batch; see the class."""
+        return self._merge(net, images, True)
+
+    def logits(self, net, images):
+        """The merged logits alone (float32 [N,C,H,W], the same buffer `sw(net, images)` returns): no arg-max is taken."""
+        return self._merge(net, images, False)[0]
+
+
+def _check_window(window):
+    if window is not None and not isinstance(window, SlidingWindow):
+        raise ValueError(f"window must be a pytorch_camvid_amd.SlidingWindow or None. Got: {window!r}")
+
+
 class TestTimeAugmentation:
     """Multi-scale and horizontal-flip test-time inference, merged on the device (cvk_tta_accumulate, cvk_tta_resize_input).
 
@@ -672,11 +793,15 @@ class TestTimeAugmentation:
     that shape overwrites it (clone it to keep it).  `pred` is a fresh int64 [N,H,W].  The network runs in eval mode under no_grad
     and gets its `training` flag back.  Networks in bf16 mode or with split operands work unchanged (their logits are float32 at
     the module boundary), and so does a call inside `opt.swap_ema()`.  At most 32 classes.  Every distinct view size is one more
-    cached plan of the network (DESIGN.md states the memory).  A size the network cannot run raises whatever the network raises."""
+    cached plan of the network (DESIGN.md states the memory).  A size the network cannot run raises whatever the network raises.
+
+    With `window` (a SlidingWindow) every view's logits are `window.logits(net, view)` instead of `net(view)`: the network runs on
+    crops of the view and the merged map, dense logits at the view's size, goes through everything above unchanged (evaluate_report's
+    loss view sees the merged logits).  One plan at the crop size then serves every scale."""
 
     __test__ = False                    # the name starts with "Test": not a pytest class
 
-    def __init__(self, scales=(0.75, 1.0, 1.25), flip=True, size_divisor=1):
+    def __init__(self, scales=(0.75, 1.0, 1.25), flip=True, size_divisor=1, window=None):
         import math
         try:
             scales = tuple(float(s) for s in scales)
@@ -686,7 +811,8 @@ class TestTimeAugmentation:
             raise ValueError(f"scales must be a non-empty sequence of positive finite numbers. Got: {scales!r}")
         if isinstance(size_divisor, bool) or not isinstance(size_divisor, int) or size_divisor < 1:
             raise ValueError(f"size_divisor must be an integer >= 1. Got: {size_divisor!r}")
-        self.scales, self.flip, self.size_divisor = scales, bool(flip), size_divisor
+        _check_window(window)
+        self.scales, self.flip, self.size_divisor, self.window = scales, bool(flip), size_divisor, window
         self._acc = {}
 
     def _plan(self, H, W):
@@ -717,10 +843,7 @@ class TestTimeAugmentation:
 
     @staticmethod
     def _check_images(images):
-        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
-            raise ValueError("expected float32 images of shape [N, 3, H, W]")
-        if not images.is_cuda:
-            raise RuntimeError("pytorch_camvid_amd.TestTimeAugmentation needs HIP tensors (no CPU fallback)")
+        _check_images("TestTimeAugmentation", images)
 
     def views(self, images):
         """The network inputs, in view order (what `tta(net, images)` feeds the network): the scale-1.0 unmirrored view at the image
@@ -754,7 +877,7 @@ class TestTimeAugmentation:
         try:
             with torch.no_grad():
                 for i, ((s, h, w, flipped), x) in enumerate(zip(plan, self.views(images))):
-                    logits = net(x)
+                    logits = net(x) if self.window is None else self.window.logits(net, x)
                     if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
                         raise ValueError("the network must return logits of shape [N, C, h, w]")
                     if logits.dtype != torch.float32 or not logits.is_cuda:
@@ -805,12 +928,21 @@ def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None):
     return meter, losses
 
 
+def _check_tta_window(who, tta, window):
+    _check_window(window)
+    if tta is not None and window is not None:
+        raise ValueError(f"{who}(): pass tta= or window=, not both; for sliding windows under test-time augmentation pass "
+                         "tta=TestTimeAugmentation(..., window=window)")
+
+
 @torch.no_grad()
-def evaluate(net, batches, num_classes=12, ignore_index=11, tta=None):
+def evaluate(net, batches, num_classes=12, ignore_index=11, window=None, tta=None):
     """Validation pass of reference train.py:169-206 / eval.py:44-80 without their bugs: eval-mode forward, device-side
     argmax and histogram accumulation over the WHOLE set, one host copy at the end.
     `batches` yields (images [N,3,H,W] float32, masks [N,H,W] int64) on the GPU.  Returns (accuracy, per-class IoU, mIoU).
-    With `tta` (a TestTimeAugmentation) the prediction of a batch is the arg-max of the views' mean probabilities."""
+    With `tta` (a TestTimeAugmentation) the prediction of a batch is the arg-max of the views' mean probabilities; with `window` (a
+    SlidingWindow) it is the arg-max of the windows' merged logits.  One of the two: TestTimeAugmentation(..., window=) combines them."""
+    _check_tta_window("evaluate", tta, window)
     if tta is not None:
         meter, _ = _evaluate_tta(net, batches, num_classes, ignore_index, tta)
         if meter is None:
@@ -820,22 +952,29 @@ def evaluate(net, batches, num_classes=12, ignore_index=11, tta=None):
     net.eval()
     meter = None
     for images, masks in batches:
-        logits = net(images)
+        if window is None:
+            logits = net(images)
+            pred = argmax_channels(logits)
+        else:
+            logits, pred = window(net, images)
         if meter is None:
             meter = ConfusionMeter(num_classes, ignore_index, logits.device)
-        meter.update(argmax_channels(logits), masks)
+        meter.update(pred, masks)
     net.train(was_training)
     if meter is None:
         raise ValueError("evaluate(): no batches")
     return meter.compute()
 
 
-def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None, tta=None):
+def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None, window=None, tta=None):
     """The report of reference eval.py:44-80: {"miou", "precision", "recall", "loss" (mean over batches), "accuracy",
     "iou" (per class)} for a set of (images, masks) batches on the GPU; eval-mode forward under no_grad, argmax and
     histograms on the device, one host copy at the end (the reference copies N*H*W int64 per batch, eval.py:60-62).
     With `tta` (a TestTimeAugmentation) the predictions are the merged ones and "loss" is `loss_fn` of the logits of the
-    scale-1.0 unmirrored view at the label size: None when that view is not among the views."""
+    scale-1.0 unmirrored view at the label size: None when that view is not among the views.  With `window` (a SlidingWindow) the
+    predictions and the logits `loss_fn` sees are the windows' merged ones.  One of the two: TestTimeAugmentation(..., window=) combines
+    them."""
+    _check_tta_window("evaluate_report", tta, window)
     loss_fn = loss_fn or CrossEntropyLoss()
     if tta is not None:
         meter, losses = _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn)
@@ -855,13 +994,17 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
     meter, loss_sum, n = None, None, 0
     with torch.no_grad():
         for images, masks in batches:
-            logits = net(images)
+            if window is None:
+                logits = net(images)
+                pred = argmax_channels(logits)
+            else:
+                logits, pred = window(net, images)
             if meter is None:
                 meter = ConfusionMeter(num_classes, ignore_index, logits.device)
             l = loss_fn(logits, masks).detach()
             loss_sum = l if loss_sum is None else loss_sum + l
             n += 1
-            meter.update(argmax_channels(logits), masks)
+            meter.update(pred, masks)
     net.train(was_training)
     if meter is None:
         raise ValueError("evaluate_report(): no batches")
@@ -870,13 +1013,15 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
     return {"miou": miou, "precision": prec, "recall": rec, "loss": float(loss_sum) / n, "accuracy": acc, "iou": iou}
 
 
-def predict(net, image_u8, out_size=None, mean=CAMVID_MEAN, std=CAMVID_STD, tta=None):
+def predict(net, image_u8, out_size=None, mean=CAMVID_MEAN, std=CAMVID_STD, window=None, tta=None):
     """reference predict.py:35-57 from the decoded image onward: `image_u8` is one uint8 [H, W, 3] frame (BGR, as cv2
     decodes; a CPU or GPU tensor or a numpy array) already at the network's input size; normalisation, eval-mode forward
     and channel argmax run on the device.  Returns the int64 class map [H, W]; with out_size=(h, w) it is resized by
     nearest neighbour the way `cv2.resize(..., INTER_NEAREST)` does (predict.py:55; source index floor(dst * in / out)).
     Image decoding / PIL resizing to IMAGE_SIZE stay on the host side (cv2 / PIL are not part of this package).
-    With `tta` (a TestTimeAugmentation) the class map is the arg-max of the views' mean probabilities."""
+    With `tta` (a TestTimeAugmentation) the class map is the arg-max of the views' mean probabilities; with `window` (a SlidingWindow)
+    the frame may have any size and the class map is the arg-max of the windows' merged logits.  One of the two."""
+    _check_tta_window("predict", tta, window)
     dev = next(net.parameters()).device
     img = torch.as_tensor(image_u8)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[-1] != 3:
@@ -884,6 +1029,8 @@ def predict(net, image_u8, out_size=None, mean=CAMVID_MEAN, std=CAMVID_STD, tta=
     x = preprocess_uint8(img.to(dev).unsqueeze(0), mean, std)
     if tta is not None:
         cls = tta(net, x)[1][0]
+    elif window is not None:
+        cls = window(net, x)[1][0]
     else:
         was_training = net.training
         net.eval()
