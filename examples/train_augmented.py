@@ -7,6 +7,7 @@ package); random.seed makes the augmentation decisions of the reference's Compos
 
   python examples/train_augmented.py --epochs 2 --iters 20 -b 8
   python examples/train_augmented.py --graphed --clip-grad-norm 1.0    # FlatAdamW with global-norm clipping, one graph replay per iteration
+  python examples/train_augmented.py --graphed --optimizer sgd -lr 0.05 --clip-grad-norm 1.0    # the same with momentum SGD (cvk.FlatSGD)
   python examples/train_augmented.py --graphed --ema-decay 0.999 --ema-warmup   # weight EMA inside the captured step, validated too
 """
 import argparse
@@ -51,7 +52,12 @@ def main():
     ap.add_argument("--dice-weight", type=float, default=0.5, help="--loss ce+dice: the Dice term's coefficient")
     ap.add_argument("--ohem-thresh", type=float, default=0.7, help="--loss ohem: keep the pixels whose target probability is below this")
     ap.add_argument("--ohem-min-kept", type=int, default=100000, help="--loss ohem: never keep fewer than this many of the hardest pixels")
-    ap.add_argument("--graphed", action="store_true", help="cvk.FlatAdamW and the whole iteration as one captured graph (cvk.GraphedStep)")
+    ap.add_argument("--graphed", action="store_true", help="cvk.FlatAdamW (with --optimizer sgd: cvk.FlatSGD) and the whole iteration as one "
+                    "captured graph (cvk.GraphedStep)")
+    ap.add_argument("--optimizer", default="adamw", choices=["adamw", "sgd"],
+                    help="sgd: momentum SGD as the U-Net and SegNet papers trained (cvk.FlatSGD with --graphed, torch.optim.SGD otherwise)")
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd: the momentum (OneCycleLR cycles it between 0.85 and this)")
+    ap.add_argument("--nesterov", action="store_true", help="--optimizer sgd: Nesterov momentum")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                     help="clip the global gradient 2-norm to X (cvk.clip_grad_norm_; with --graphed: FlatAdamW(max_grad_norm=X), inside the "
                     "captured step); prints the epoch's largest norm and the share of clipped steps")
@@ -98,9 +104,15 @@ def main():
     torch.manual_seed(0)
     random.seed(a.seed)
     net = cvk.get_model(a.net, 3, 12).to(dev)
-    opt = cvk.FlatAdamW(net, lr=a.lr, max_grad_norm=a.clip_grad_norm, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup) if a.graphed else \
-        torch.optim.AdamW(net.parameters(), lr=a.lr)
-    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=updates, epochs=a.epochs)
+    fused = dict(max_grad_norm=a.clip_grad_norm, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup)
+    if a.optimizer == "sgd":
+        sgd = dict(lr=a.lr, momentum=a.momentum, nesterov=a.nesterov)
+        opt = cvk.FlatSGD(net, **sgd, **fused) if a.graphed else torch.optim.SGD(net.parameters(), **sgd)
+    else:
+        opt = cvk.FlatAdamW(net, lr=a.lr, **fused) if a.graphed else torch.optim.AdamW(net.parameters(), lr=a.lr)
+    cycle = dict(max_momentum=a.momentum, base_momentum=min(0.85, a.momentum)) if a.optimizer == "sgd" and a.momentum > 0 else \
+        dict(cycle_momentum=a.optimizer != "sgd")
+    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=updates, epochs=a.epochs, **cycle)
     accum = cvk.GradAccumulator(net, steps=K) if K > 1 else None
     weight = None
     if a.class_weights != "none":

@@ -7,6 +7,7 @@ augmentation of 960x720 frames on the device see examples/train_augmented.py.  E
   python examples/train_synthetic.py --graphed      # each iteration (step, AdamW, log line) as ONE graph replay
   python examples/train_synthetic.py --graphed --clip-grad-norm 1.0     # global-norm clipping inside the captured AdamW step
   python examples/train_synthetic.py --graphed --ema-decay 0.999 --ema-warmup   # weight EMA inside the captured AdamW step, validated too
+  python examples/train_synthetic.py --graphed --optimizer sgd -lr 0.05 -wd 1e-4 --clip-grad-norm 1.0   # momentum SGD (cvk.FlatSGD), captured
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_synthetic.py   # data parallel
 """
 import argparse
@@ -29,7 +30,12 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)           # reference 120 (train.py:24)
     ap.add_argument("--iters", type=int, default=20, help="synthetic batches per epoch")
     ap.add_argument("-wd", type=float, default=0.0)            # train.py:25
-    ap.add_argument("--flat-adamw", action="store_true", help="one fused optimizer kernel (cvk.FlatAdamW)")
+    ap.add_argument("--flat-adamw", action="store_true", help="one fused optimizer kernel (cvk.FlatAdamW; with --optimizer sgd: cvk.FlatSGD)")
+    ap.add_argument("--optimizer", default="adamw", choices=["adamw", "sgd"],
+                    help="adamw: the reference's optimizer; sgd: momentum SGD as the U-Net and SegNet papers trained (cvk.FlatSGD with "
+                    "--flat-adamw / --graphed, torch.optim.SGD otherwise); -lr is the schedule's peak, -wd the coupled L2 weight decay")
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd: the momentum (OneCycleLR cycles it between 0.85 and this)")
+    ap.add_argument("--nesterov", action="store_true", help="--optimizer sgd: Nesterov momentum")
     ap.add_argument("--graphed", action="store_true", help="the whole iteration (forward, loss, backward, FlatAdamW, the log line) as one "
                     "captured graph (cvk.GraphedStep); the log is read once per epoch.  Implies --flat-adamw")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
@@ -101,10 +107,16 @@ def main():
     cvk.set_conv_precision(net, a.precision)
     cvk.set_split_operands(net, a.split_operands)
     model = cvk.ddp.DataParallel(net) if world > 1 else net
-    opt = cvk.FlatAdamW(net, lr=a.lr, weight_decay=a.wd, max_grad_norm=a.clip_grad_norm, ema_decay=a.ema_decay,
-                        ema_warmup=a.ema_warmup) if a.flat_adamw else \
-        torch.optim.AdamW(net.parameters(), lr=a.lr, weight_decay=a.wd)     # train.py:100
-    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=updates, epochs=a.epochs)  # :103-104
+    fused = dict(max_grad_norm=a.clip_grad_norm, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup)
+    if a.optimizer == "sgd":
+        sgd = dict(lr=a.lr, momentum=a.momentum, weight_decay=a.wd, nesterov=a.nesterov)
+        opt = cvk.FlatSGD(net, **sgd, **fused) if a.flat_adamw else torch.optim.SGD(net.parameters(), **sgd)
+    else:
+        opt = cvk.FlatAdamW(net, lr=a.lr, weight_decay=a.wd, **fused) if a.flat_adamw else \
+            torch.optim.AdamW(net.parameters(), lr=a.lr, weight_decay=a.wd)     # train.py:100
+    cycle = dict(max_momentum=a.momentum, base_momentum=min(0.85, a.momentum)) if a.optimizer == "sgd" and a.momentum > 0 else \
+        dict(cycle_momentum=a.optimizer != "sgd")
+    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=a.lr, steps_per_epoch=updates, epochs=a.epochs, **cycle)  # :103-104
     if K > 1 and a.graphed and world > 1:
         ap.error("--accumulate with --graphed runs on one GPU (a window with captured collectives is not supported)")
     accum = cvk.GradAccumulator(model, steps=K) if K > 1 else None           # folds the flat gradient buffers of K backward passes
@@ -164,8 +176,9 @@ def main():
             rows, dropped = step.log()                                      # the epoch's per-iteration lines: one D2H copy
             if a.clip_grad_norm is not None:                                # 7 columns: ..., global norm, clip coefficient
                 norms = list(torch.from_numpy(rows[:, 5].copy()))
+            col2 = "Momentum" if a.optimizer == "sgd" else "Beta1"          # column 2 of the log: what the scheduler cycles
             for i, (l, lr, beta, gw, gb) in enumerate(rows[:, :5]):         # train.py:135-143 + utils.visulaize_lastlayer
-                print(("Training Epoch:{epoch} [{trained_samples}/{total_samples}] Lr:{lr:0.6f} Loss:{loss:0.4f} Beta1:{beta:0.4f} "
+                print(("Training Epoch:{epoch} [{trained_samples}/{total_samples}] Lr:{lr:0.6f} Loss:{loss:0.4f} " + col2 + ":{beta:0.4f} "
                        "grad_norm2_weights:{gw:0.4e} grad_norm2_bias:{gb:0.4e}").format(
                     epoch=epoch, trained_samples=(dropped + i + 1) * a.b * K, total_samples=a.iters * a.b, lr=lr, loss=l, beta=beta,
                     gw=gw, gb=gb))

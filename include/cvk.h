@@ -656,6 +656,44 @@ int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, f
                               const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
                               const float* record, const float* alpha, float alpha_host, void* stream);
 
+/* ---- fused momentum SGD over the same range table (torch.optim.SGD) -------------------------------------------------------------
+ * The second update rule of the flat optimizer.  Everything around the element update is cvk_adamw_step_ranges': the DEVICE range table
+ * planned by cvk_adamw_plan_ranges (cvk_adamw_range; `hyper` indexes the cvk_sgd_hyper records here), the workgroup-to-range search,
+ * the {total_norm, clip_coef} record (null: coefficient 1.0f), the ema buffer with ema[i] += alpha * (p_new - ema[i]) from the register,
+ * the two record sources.  Elements outside every range are never touched, in any buffer.  The update, in fp32, one expression list for
+ * both entry points (they cannot round differently):
+ *     d = grad[i] * clip_coef;  d = d + weight_decay * param[i]                      (coupled L2, as torch; not decoupled)
+ *     if momentum != 0:  b = first ? d : momentum * buf[i] + (1 - dampening) * d;  buf[i] = b;  d = nesterov ? d + momentum * b : b
+ *     param[i] = param[i] - lr * d
+ * `first` is torch's `momentum_buffer is None`: on a parameter's first step with a non-zero momentum the buffer becomes d itself.
+ *
+ * cvk_sgd_hyper: 7 floats, the size of cvk_adamw_hyper, so the records travel in the same slots (kernel arguments or the device ring of
+ *   GraphedStep) and cvk_step_log, which reads floats 0 and 1 of its record, works unchanged: lr is float 0 and momentum float 1 (log
+ *   column 2 carries the momentum where it carries beta1 for AdamW).  nesterov and first are 0.0f or 1.0f; reserved is 0.
+ * cvk_sgd_hyper_fill (host function, no launch) fills one.  Refused: a negative or NaN lr, momentum or weight_decay; nesterov with
+ *   momentum <= 0 or dampening != 0.
+ * cvk_sgd_step_ranges (eager): hyper is a HOST array of nhyper <= CVK_ADAMW_ARG_RECORDS records; they and alpha travel as kernel
+ *   arguments.  momentum_buf (DEVICE, laid out like param) may be null only if every record's momentum is 0 (checked on the host); with
+ *   a null buffer the kernel neither reads nor writes one: 3 passes over the ranges instead of 5.  With a buffer, the ranges of a record
+ *   whose momentum is 0 are still left alone in it.
+ * cvk_sgd_step_ranges_dev (captured graphs): hyper and alpha in DEVICE memory, alpha_host only checked, as for
+ *   cvk_adamw_step_ranges_dev.  The device records cannot be checked: a null momentum_buf runs the buffer-free kernel whatever they carry.
+ * Both check their arguments like cvk_adamw_step_ranges[_dev] (null pointers, alpha outside (0, 1] with an ema, the record limit of the
+ * argument form, an empty table) before any launch. */
+typedef struct cvk_sgd_hyper {
+    float lr, momentum, dampening, weight_decay;
+    float nesterov;              /* 0 or 1 */
+    float first;                 /* 0 or 1: the ranges of this record have no momentum buffer yet */
+    float reserved;              /* 0 */
+} cvk_sgd_hyper;
+int cvk_sgd_hyper_fill(float lr, float momentum, float dampening, float weight_decay, int nesterov, int first, cvk_sgd_hyper* out);
+int cvk_sgd_step_ranges(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n,
+                        const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_sgd_hyper* hyper, int nhyper,
+                        const float* record, float alpha, void* stream);
+int cvk_sgd_step_ranges_dev(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n,
+                            const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_sgd_hyper* hyper, int nhyper,
+                            const float* record, const float* alpha, float alpha_host, void* stream);
+
 /* ---- the per-iteration training log (train.py:133-143 print of loss / lr / Beta1; utils.visulaize_lastlayer utils.py:33-36) -------
  * One single-workgroup launch appends the row [loss, lr, beta1, ||gw||_2, ||gb||_2] (fp32) to a DEVICE ring of `capacity` rows at row
  * counter % capacity, then increments *counter (DEVICE int64).  loss: DEVICE scalar; hyper: DEVICE record (lr and beta1 of the step);

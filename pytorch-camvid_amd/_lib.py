@@ -239,6 +239,9 @@ SIGNATURES = {
     "cvk_adamw_plan_ranges": (c_int, [c_vp, c_int, c_i64, c_int]),                                   # HOST table (AdamwRange)
     "cvk_adamw_step_ranges": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_float, c_vp]),   # HOST AdamwHyper array
     "cvk_adamw_step_ranges_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_float, c_vp]),
+    "cvk_sgd_hyper_fill": (c_int, [c_float, c_float, c_float, c_float, c_int, c_int, c_vp]),       # out: HOST SgdHyper
+    "cvk_sgd_step_ranges": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_float, c_vp]),     # HOST SgdHyper array
+    "cvk_sgd_step_ranges_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_float, c_vp]),
     "cvk_step_log": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "cvk_clip_coef": (c_float, [c_float, c_float]),                                                  # host function
     "cvk_grad_norm_plan": (c_int, [c_vp, c_int, c_i64]),                                             # HOST table (NormSegment)
@@ -259,6 +262,11 @@ class AugmentRecord(ctypes.Structure):  # include/cvk.h cvk_augment_record (its 
 class AdamwHyper(ctypes.Structure):     # include/cvk.h cvk_adamw_hyper
     _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("weight_decay", ctypes.c_float), ("bc1", ctypes.c_float), ("bc2_sqrt", ctypes.c_float)]
+
+
+class SgdHyper(ctypes.Structure):       # include/cvk.h cvk_sgd_hyper: the size of AdamwHyper, lr and momentum where lr and beta1 are
+    _fields_ = [("lr", ctypes.c_float), ("momentum", ctypes.c_float), ("dampening", ctypes.c_float), ("weight_decay", ctypes.c_float),
+                ("nesterov", ctypes.c_float), ("first", ctypes.c_float), ("reserved", ctypes.c_float)]
 
 
 class AdamwRange(ctypes.Structure):     # include/cvk.h cvk_adamw_range

@@ -1409,6 +1409,64 @@ __global__ void k_adamw_ranges(float* __restrict__ p, const float* __restrict__ 
     }
 }
 
+// One momentum-SGD element update (torch.optim.SGD: coupled L2 weight decay, dampening, Nesterov), in fp32.  Shared by the eager and the
+// captured instantiation of k_sgd_ranges: one expression list, so they cannot round differently (the convention of adamw_update).
+// coef scales the gradient on its way in, as in adamw_update.  `mom` (momentum != 0 under MOM): the buffer is in use; `first` is torch's
+// `momentum_buffer is None`: the buffer becomes the (decayed) gradient itself, not (1 - dampening) * d.  Without `mom`, buf is neither
+// read nor written.  Returns the parameter value it stored, for the EMA that goes on with it in the register.
+__device__ __forceinline__ float sgd_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t i,
+                                            float lr, float momentum, float dampening, float wd, bool nesterov, bool first, bool mom,
+                                            float coef) {
+    const float pi = p[i];
+    float d = g[i] * coef;
+    d = d + wd * pi;
+    if (mom) {
+        const float b = first ? d : momentum * buf[i] + (1.f - dampening) * d;
+        buf[i] = b;
+        d = nesterov ? d + momentum * b : b;
+    }
+    const float pn = pi - lr * d;
+    p[i] = pn;
+    return pn;
+}
+
+// Momentum SGD over a range table (cvk_sgd_step_ranges, cvk_sgd_step_ranges_dev): the table, the workgroup-to-range search, the record
+// sources (a cvk_sgd_hyper has the size of a cvk_adamw_hyper and travels in the same slots), the clip record and the EMA tail are those of
+// k_adamw_ranges.  MOM false: no record uses a momentum buffer; `buf` is never read or written (3 passes over the range instead of 5).
+// Under MOM a record whose momentum is 0 still leaves its ranges of `buf` alone, as torch keeps no buffer for such a group.
+static_assert(sizeof(cvk_sgd_hyper) == sizeof(cvk_adamw_hyper), "cvk_sgd_hyper travels in the record slots of cvk_adamw_hyper");
+
+template <class SRC, bool EMA, bool MOM>
+__global__ void k_sgd_ranges(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, float* __restrict__ ema,
+                             int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, const SRC src, int nhyper,
+                             const float* __restrict__ clip) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = nr - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rt[mid].block0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const int64_t off = rt[lo].offset, len = rt[lo].length;
+    const int hx = rt[lo].hyper, b0 = rt[lo].block0;
+    const int nb = (lo + 1 < nr ? rt[lo + 1].block0 : (int)gridDim.x) - b0;
+    if (off < 0 || len <= 0 || off + len > n || hx < 0 || hx >= nhyper || nb <= 0 || b < b0) return;
+    const cvk_sgd_hyper* __restrict__ hyper = reinterpret_cast<const cvk_sgd_hyper*>(src.records());
+    const float lr = hyper[hx].lr, momentum = hyper[hx].momentum, dampening = hyper[hx].dampening, wd = hyper[hx].weight_decay;
+    const bool nesterov = hyper[hx].nesterov != 0.f, first = hyper[hx].first != 0.f;
+    const bool mom = MOM && momentum != 0.f;
+    const float coef = clip != nullptr ? clip[1] : 1.f;
+    float alpha = 0.f;
+    if constexpr (EMA) alpha = src.alpha();
+    for (int64_t i = off + (int64_t)(b - b0) * blockDim.x + threadIdx.x; i < off + len; i += (int64_t)nb * blockDim.x) {
+        const float pi = sgd_update(p, g, buf, i, lr, momentum, dampening, wd, nesterov, first, mom, coef);
+        if constexpr (EMA) {
+            const float e = ema[i];
+            ema[i] = e + alpha * (pi - e);
+        }
+    }
+}
+
 // One row [loss, lr, beta1, ||gw||_2, ||gb||_2] of the per-iteration log, with `rec` (the {total_norm, clip_coef} record of cvk_grad_norm)
 // followed by its two floats, into ring[(*counter % capacity) * cols ..] (cols = 5 or 7), then ++*counter.
 // One workgroup of 256 threads: thread t sums the squares of elements t, t + 256, ... in fp64, then a fixed tree over LDS.
@@ -2217,6 +2275,76 @@ extern "C" int cvk_adamw_step_ranges_dev(float* param, const float* grad, float*
     const AdamwDevSource src = {hyper, alpha};
     adamw_ranges_launch(param, grad, exp_avg, exp_avg_sq, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
     CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_dev");
+}
+
+// ---- momentum SGD over the same range table (torch.optim.SGD) ----------------------------------------------------------------------
+extern "C" int cvk_sgd_hyper_fill(float lr, float momentum, float dampening, float weight_decay, int nesterov, int first,
+                                  cvk_sgd_hyper* out) {
+    CVK_CHECK_ARG(out, "cvk_sgd_hyper_fill: null pointer");
+    CVK_CHECK_ARG(lr >= 0.f, "cvk_sgd_hyper_fill: lr %g must be >= 0", (double)lr);
+    CVK_CHECK_ARG(momentum >= 0.f, "cvk_sgd_hyper_fill: momentum %g must be >= 0", (double)momentum);
+    CVK_CHECK_ARG(weight_decay >= 0.f, "cvk_sgd_hyper_fill: weight_decay %g must be >= 0", (double)weight_decay);
+    CVK_CHECK_ARG(!nesterov || (momentum > 0.f && dampening == 0.f), "cvk_sgd_hyper_fill: nesterov needs a momentum > 0 and zero dampening "
+                  "(momentum %g, dampening %g)", (double)momentum, (double)dampening);
+    out->lr = lr;
+    out->momentum = momentum;
+    out->dampening = dampening;
+    out->weight_decay = weight_decay;
+    out->nesterov = nesterov ? 1.f : 0.f;
+    out->first = first ? 1.f : 0.f;
+    out->reserved = 0.f;
+    return CVK_OK;
+}
+
+// One launch of the SGD range kernel: SRC, EMA and MOM pick the instantiation, the argument list is the same for all eight.
+template <class SRC, bool MOM>
+static void sgd_ranges_launch(float* param, const float* grad, float* buf, float* ema, int64_t n, const cvk_adamw_range* ranges, int nranges,
+                              int nblocks, const SRC& src, int nhyper, const float* record, void* stream) {
+    if (ema != nullptr)
+        hipLaunchKernelGGL((k_sgd_ranges<SRC, true, MOM>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, buf, ema, n, ranges,
+                           nranges, src, nhyper, record);
+    else
+        hipLaunchKernelGGL((k_sgd_ranges<SRC, false, MOM>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, buf, ema, n, ranges,
+                           nranges, src, nhyper, record);
+}
+
+extern "C" int cvk_sgd_step_ranges(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n,
+                                   const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_sgd_hyper* hyper, int nhyper,
+                                   const float* record, float alpha, void* stream) {
+    CVK_CHECK_ARG(param && grad && ranges && hyper, "cvk_sgd_step_ranges: null pointer");
+    CVK_CHECK_ARG(!ema || (alpha > 0.f && alpha <= 1.f), "cvk_sgd_step_ranges: alpha %g outside (0, 1]", (double)alpha);
+    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
+                  "cvk_sgd_step_ranges: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
+    AdamwArgSource src = {};
+    for (int i = 0; i < nhyper; ++i) {
+        CVK_CHECK_ARG(momentum_buf || hyper[i].momentum == 0.f, "cvk_sgd_step_ranges: null momentum buffer, but record %d has momentum %g", i,
+                      (double)hyper[i].momentum);
+        src.recs.r[i] = {hyper[i].lr, hyper[i].momentum, hyper[i].dampening, hyper[i].weight_decay, hyper[i].nesterov, hyper[i].first,
+                         hyper[i].reserved};                          // the 7 floats in their slots (static_assert above the kernel)
+    }
+    src.a = alpha;
+    if (momentum_buf != nullptr)
+        sgd_ranges_launch<AdamwArgSource, true>(param, grad, momentum_buf, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
+    else
+        sgd_ranges_launch<AdamwArgSource, false>(param, grad, momentum_buf, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
+    CVK_LAUNCH_RETURN("cvk_sgd_step_ranges");
+}
+
+// hyper and alpha as in cvk_adamw_step_ranges_dev.  The device records cannot be checked here: a null momentum_buf selects the kernel that
+// never touches a buffer, whatever momentum they carry (FlatSGD captures it only while every group's momentum is 0 and GraphedStep
+// refuses to replay after that changes).
+extern "C" int cvk_sgd_step_ranges_dev(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n,
+                                       const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_sgd_hyper* hyper, int nhyper,
+                                       const float* record, const float* alpha, float alpha_host, void* stream) {
+    CVK_CHECK_ARG(param && grad && ranges && hyper && (!ema || alpha), "cvk_sgd_step_ranges_dev: null pointer");
+    CVK_CHECK_ARG(!ema || (alpha_host > 0.f && alpha_host <= 1.f), "cvk_sgd_step_ranges_dev: alpha %g outside (0, 1]", (double)alpha_host);
+    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_sgd_step_ranges_dev: bad arguments");
+    const AdamwDevSource src = {reinterpret_cast<const cvk_adamw_hyper*>(hyper), alpha};
+    if (momentum_buf != nullptr)
+        sgd_ranges_launch<AdamwDevSource, true>(param, grad, momentum_buf, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
+    else
+        sgd_ranges_launch<AdamwDevSource, false>(param, grad, momentum_buf, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
+    CVK_LAUNCH_RETURN("cvk_sgd_step_ranges_dev");
 }
 
 // record (the {total_norm, clip_coef} record of cvk_grad_norm) may be null: rows of 5 floats; with it, rows of 7.

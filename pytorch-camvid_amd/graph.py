@@ -18,7 +18,9 @@ bucketed all-reduces (`GraphedStep(dp_net.module, ..., allow_grad_sync=True)`): 
 collectives run on RCCL's stream inside it, and 8 single-threaded ranks no longer sit on 11-15 ms of Python enqueue per step.
 gloo groups (CPU rehearsals) cannot be captured.
 
-The whole iteration (train.py:124-150): with `optimizer=` (a FlatAdamW) the graph also runs the AdamW step after backward (after
+The whole iteration (train.py:124-150): with `optimizer=` (a FlatAdamW or a FlatSGD; what follows says AdamW and holds for both, with the
+SGD records carrying lr / momentum / dampening / weight decay / nesterov and a "first step" flag per record where AdamW's carry the bias
+corrections, and log column 2 the momentum instead of beta1) the graph also runs the optimizer step after backward (after
 the captured all-reduces under data parallel), and with `log_capacity=` it ends in one launch that appends the reference's log
 line [loss, lr, beta1, ||last weight grad||, ||last bias grad||] to a device ring.  lr, betas, eps and weight decay of every parameter
 group are read at every replay, the bias corrections computed on the host and uploaded into device records the graph reads (one per
@@ -51,7 +53,8 @@ from . import _lib, engine
 from ._lib import check
 from .optim import ema_alpha as _ema_alpha
 
-HYPER_FLOATS = 7                         # include/cvk.h cvk_adamw_hyper: lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt
+HYPER_FLOATS = 7                         # include/cvk.h cvk_adamw_hyper: lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt; cvk_sgd_hyper has
+                                         # the same size with lr and momentum in floats 0 and 1
 HYPER_BYTES = 4 * HYPER_FLOATS
 HYPER_SLOTS = 32                         # pinned staging records: the host may run this many replays ahead of the GPU before it waits
 
@@ -71,10 +74,10 @@ def last_layer_params(net):
 class GraphedStep:
     def __init__(self, net, lossf, x, t, warmup=2, allow_grad_sync=False, *, optimizer=None, scheduler=None, log_capacity=0, accumulator=None):
         from .modules import runner_of
-        from .optim import FlatAdamW
-        if optimizer is not None and not isinstance(optimizer, FlatAdamW):
-            raise TypeError(f"GraphedStep: only FlatAdamW can be captured with the step, not {type(optimizer).__name__}; step other "
-                            "optimizers after replay()")
+        from .optim import _FlatOptimizer
+        if optimizer is not None and not isinstance(optimizer, _FlatOptimizer):
+            raise TypeError(f"GraphedStep: only FlatAdamW and FlatSGD can be captured with the step, not {type(optimizer).__name__}; step "
+                            "other optimizers after replay()")
         if scheduler is not None and optimizer is None:
             raise ValueError("GraphedStep: a scheduler needs the captured optimizer it drives (optimizer=)")
         if scheduler is not None and getattr(scheduler, "optimizer", optimizer) is not optimizer:
@@ -121,7 +124,7 @@ class GraphedStep:
         self.params = [p for p in net.parameters() if p.requires_grad]
         if optimizer is not None:
             # the parameters the captured step updates (those that receive a gradient) and its records: record 0 = param_groups[0] for the log,
-            # then one per (group, step count) of the range table (FlatAdamW._ranges); rewritten before every replay from a ring of pinned slots
+            # then one per (group, record key) of the range table (_FlatOptimizer._ranges); rewritten before every replay from a ring of pinned slots
             self._opt_idx = [i for i, p in enumerate(optimizer._plist) if p.requires_grad]
             if not self._opt_idx:
                 raise ValueError("GraphedStep: the optimizer has no trainable parameter to step")
@@ -224,17 +227,14 @@ class GraphedStep:
         opt = self.optimizer
         if self._ema:
             opt._ema_options()              # a decay outside [0, 1) is refused before anything is counted
-        g = opt.param_groups[0]
         opt._step += 1
-        for i in self._opt_idx:
-            opt._steps[i] += 1
+        opt._count(self._opt_idx)
         slot = self._hyper_slot
         self._hyper_slot = (slot + 1) % HYPER_SLOTS
         if self._hyper_busy[slot] is not None:
             self._hyper_busy[slot].synchronize()
         pin = self._hyper_pin[slot]
-        check(_lib.load().cvk_adamw_hyper_fill(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                               float(g["weight_decay"]), opt._step, pin.data_ptr()), "cvk_adamw_hyper_fill")
+        opt._fill_record(0, None, pin.data_ptr())       # record 0: param_groups[0] as it is now, for the log row
         opt._fill(self._opt_recs, pin[HYPER_FLOATS:])
         if self._ema:
             pin[-1] = float(opt._next_ema_alpha())
@@ -245,7 +245,7 @@ class GraphedStep:
 
     def log(self):
         """The log rows the replays wrote since the previous call, oldest first: (rows [k, 5] float32 numpy array of
-        [loss, lr, beta1, ||grad of the last weight||_2, ||grad of the last bias||_2], dropped).  With a clipping optimizer
+        [loss, lr, beta1 (FlatAdamW) / momentum (FlatSGD), ||grad of the last weight||_2, ||grad of the last bias||_2], dropped).  With a clipping optimizer
         (FlatAdamW(max_grad_norm=...)) the rows have 7 columns: the five, then the step's global gradient norm and its clip coefficient.
         When more than log_capacity rows were
         written since the last call, the oldest were overwritten on the device: rows holds the newest log_capacity of them and
@@ -277,13 +277,14 @@ class GraphedStep:
             + (plan_key_blocks(self.net),) + ((id(acc), acc.steps, acc.mean) if acc is not None else (None, 1, True))
 
     def _optimizer_signature(self):
-        """The captured AdamW step writes the optimizer's flat buffers through raw pointers: the same optimizer, one parameter group, the
-        same flat buffer, and every parameter still a view of it at its capture-time address (a rebuilt FlatAdamW re-homes them)."""
+        """The captured optimizer step writes the optimizer's flat buffers through raw pointers: the same optimizer, one parameter group, the
+        same flat buffer, and every parameter still a view of it at its capture-time address (a rebuilt FlatAdamW re-homes them); the kernel
+        variant is fixed too: clip or not, EMA or not, and what the rule adds (FlatSGD: whether a momentum buffer is in use)."""
         opt = getattr(self, "optimizer", None)
         if opt is None:
             return ()
         return (id(opt), len(opt.param_groups), tuple(opt._group_of()), opt._flat.data_ptr(), tuple(p.data_ptr() for p in opt._plist),
-                opt.max_grad_norm, opt.norm_type, opt.ema_decay is not None)
+                opt.max_grad_norm, opt.norm_type, opt.ema_decay is not None) + opt._variant()
 
     def replay(self, x=None, t=None):
         """Copy a new batch into the static input buffers (optional) and replay the step.  Returns the (static) loss tensor.
@@ -294,7 +295,8 @@ class GraphedStep:
                                "block's BatchNorm, a parameter's requires_grad, a swapped block, conv precision, a kernel "
                                "knob, it was wrapped in / unwrapped from ddp.DataParallel, a GradAccumulator was attached, detached or given other "
                                "steps / mean, or the captured FlatAdamW was rebuilt, re-homed, "
-                               "regrouped, given another max_grad_norm / norm_type or its EMA switched on or off): the "
+                               "regrouped, given another max_grad_norm / norm_type, its EMA switched on or off or a FlatSGD's momentum switched between zero and "
+                               "non-zero): the "
                                "captured graph would silently run the "
                                "old configuration — build a new GraphedStep")
         if self.accumulator is not None and self.accumulator.micro_step:
