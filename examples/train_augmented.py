@@ -9,6 +9,7 @@ package); random.seed makes the augmentation decisions of the reference's Compos
   python examples/train_augmented.py --graphed --clip-grad-norm 1.0    # FlatAdamW with global-norm clipping, one graph replay per iteration
   python examples/train_augmented.py --graphed --optimizer sgd -lr 0.05 --clip-grad-norm 1.0    # the same with momentum SGD (cvk.FlatSGD)
   python examples/train_augmented.py --graphed --ema-decay 0.999 --ema-warmup   # weight EMA inside the captured step, validated too
+  python examples/train_augmented.py --net segnet --teacher unet --teacher-weights unet.pth --graphed   # distil the UNet into SegNet
 """
 import argparse
 import os
@@ -52,6 +53,14 @@ def main():
     ap.add_argument("--dice-weight", type=float, default=0.5, help="--loss ce+dice: the Dice term's coefficient")
     ap.add_argument("--ohem-thresh", type=float, default=0.7, help="--loss ohem: keep the pixels whose target probability is below this")
     ap.add_argument("--ohem-min-kept", type=int, default=100000, help="--loss ohem: never keep fewer than this many of the hardest pixels")
+    ap.add_argument("--teacher", default=None, choices=["unet", "segnet"],
+                    help="knowledge distillation: train --net under this network's logits with cvk.DistillationLoss (cross-entropy on the "
+                         "labels + --kd-weight * temperature-softened KL towards the teacher); the teacher runs in eval mode under no_grad")
+    ap.add_argument("--teacher-weights", default=None, metavar="FILE",
+                    help="with --teacher: its state_dict; without it the teacher is freshly initialised, good for a smoke run only")
+    ap.add_argument("--kd-weight", type=float, default=1.0, help="with --teacher: the KL term's coefficient")
+    ap.add_argument("--kd-temperature", type=float, default=4.0, help="with --teacher: the temperature T (the KL term carries T^2)")
+    ap.add_argument("--kd-ignored", action="store_true", help="with --teacher: distil on the pixels the labels ignore too")
     ap.add_argument("--graphed", action="store_true", help="cvk.FlatAdamW (with --optimizer sgd: cvk.FlatSGD) and the whole iteration as one "
                     "captured graph (cvk.GraphedStep)")
     ap.add_argument("--optimizer", default="adamw", choices=["adamw", "sgd"],
@@ -100,6 +109,13 @@ def main():
     if K < 1 or a.iters % K:
         ap.error("--accumulate K needs K >= 1 and --iters a multiple of K")
     updates = a.iters // K
+    if a.teacher is None and (a.teacher_weights or a.kd_ignored):
+        ap.error("--teacher-weights / --kd-ignored need --teacher")
+    if a.teacher is not None and (a.loss != "ce" or a.label_smoothing):
+        ap.error("--teacher distils next to the plain cross-entropy: --loss ce without --label-smoothing")
+    if a.teacher is not None and a.graphed and K > 1:
+        ap.error("--teacher with --graphed and --accumulate is not provided: the bound teacher-logits buffer holds one batch, not a window; "
+                 "drop --graphed (the eager accumulation loop passes each micro-batch's teacher logits)")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     random.seed(a.seed)
@@ -127,29 +143,47 @@ def main():
         else:
             ce, dice = {"focal": (1.0, 0.0), "dice": (0.0, 1.0), "ce+dice": (1.0, a.dice_weight)}[a.loss]
             loss_fn = cvk.SegmentationLoss(ce, dice, focal_gamma=a.focal_gamma if a.loss == "focal" else 0.0, weight=weight)
+    teacher = kd = kd_buf = None
+    if a.teacher is not None:
+        teacher = cvk.get_model(a.teacher, 3, 12).to(dev)
+        if a.teacher_weights:
+            teacher.load_state_dict(torch.load(a.teacher_weights, map_location=dev))
+        else:
+            print("--teacher without --teacher-weights: the teacher is freshly initialised; that is good for a smoke run only")
+        teacher.eval().requires_grad_(False)
+        kd = cvk.DistillationLoss(1.0, a.kd_weight, a.kd_temperature, weight=weight, distill_ignored=a.kd_ignored)
     train_tf, valid_tf = transforms.train_transforms(), transforms.valid_transforms()
     step = None
     for epoch in range(1, a.epochs + 1):
         net.train()
         t0 = time.time()
         norms = []                                                          # device scalars: read once per epoch
-        window = []
+        pending = []                                                        # --graphed --accumulate: the open window's batches
         for images, masks in cvk.DevicePrefetcher(synthetic_camvid(a.iters, a.b, epoch), transforms=train_tf):
+            z = None
+            if teacher is not None:
+                with torch.no_grad():
+                    z = teacher(images)                                     # the teacher's logits: a constant of this step
             if a.graphed:
                 if accum is not None:                                       # a window of K batches: [K, N, 3, H, W], [K, N, H, W]
-                    window.append((images, masks))
-                    if len(window) < K:
+                    pending.append((images, masks))
+                    if len(pending) < K:
                         continue
-                    images, masks = torch.stack([w[0] for w in window]), torch.stack([w[1] for w in window])
-                    window = []
+                    images, masks = torch.stack([w[0] for w in pending]), torch.stack([w[1] for w in pending])
+                    pending = []
                 if step is None:
+                    if kd is not None:                                      # the captured kernels read the teacher's logits from kd_buf
+                        kd_buf = z.clone()
+                        loss_fn = kd.bind(kd_buf)
                     step = cvk.GraphedStep(net, loss_fn, images, masks, optimizer=opt, scheduler=sched, log_capacity=updates,
                                            accumulator=accum)
+                if kd is not None:
+                    kd_buf.copy_(z)
                 loss = step.replay(images, masks)
                 continue
             if accum is None or accum.micro_step == 0:
                 opt.zero_grad()
-            loss = loss_fn(net(images), masks)
+            loss = loss_fn(net(images), masks) if kd is None else kd(net(images), masks, z)
             loss.backward()
             if accum is not None and not accum.ready:                       # the window is still open: .grad is None, nothing to step
                 continue
@@ -159,6 +193,10 @@ def main():
         torch.cuda.synchronize()
         dt = time.time() - t0
         print(f"epoch {epoch}: loss {loss.item():.4f}  {a.b * a.iters / dt:.1f} img/s (incl. host data synthesis)")
+        if kd is not None:                                          # device views of the last step's record
+            kd_h, kd_k = kd.last_terms.tolist()
+            print(f"  distillation: H {kd_h:.4f}  K {kd_k:.4f}  arg-max agreement with the teacher {kd.last_agreement.item():.4f}  "
+                  f"(T {a.kd_temperature:g}, kd weight {a.kd_weight:g})")
         if step is not None:
             rows, _ = step.log()                                            # with clipping: 7 columns, the norm is column 5
             norms = list(torch.from_numpy(rows[:, 5].copy())) if a.clip_grad_norm is not None else []

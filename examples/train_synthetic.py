@@ -8,6 +8,7 @@ augmentation of 960x720 frames on the device see examples/train_augmented.py.  E
   python examples/train_synthetic.py --graphed --clip-grad-norm 1.0     # global-norm clipping inside the captured AdamW step
   python examples/train_synthetic.py --graphed --ema-decay 0.999 --ema-warmup   # weight EMA inside the captured AdamW step, validated too
   python examples/train_synthetic.py --graphed --optimizer sgd -lr 0.05 -wd 1e-4 --clip-grad-norm 1.0   # momentum SGD (cvk.FlatSGD), captured
+  python examples/train_synthetic.py --net segnet --teacher unet --teacher-weights unet.pth --kd-temperature 4   # distil the UNet into SegNet
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_synthetic.py   # data parallel
 """
 import argparse
@@ -49,6 +50,14 @@ def main():
     ap.add_argument("--dice-weight", type=float, default=0.5, help="--loss ce+dice: the Dice term's coefficient")
     ap.add_argument("--ohem-thresh", type=float, default=0.7, help="--loss ohem: keep the pixels whose target probability is below this")
     ap.add_argument("--ohem-min-kept", type=int, default=100000, help="--loss ohem: never keep fewer than this many of the hardest pixels")
+    ap.add_argument("--teacher", default=None, choices=["unet", "segnet"],
+                    help="knowledge distillation: train --net under this network's logits with cvk.DistillationLoss (cross-entropy on the "
+                         "labels + --kd-weight * temperature-softened KL towards the teacher); the teacher runs in eval mode under no_grad")
+    ap.add_argument("--teacher-weights", default=None, metavar="FILE",
+                    help="with --teacher: its state_dict; without it the teacher is freshly initialised, good for a smoke run only")
+    ap.add_argument("--kd-weight", type=float, default=1.0, help="with --teacher: the KL term's coefficient")
+    ap.add_argument("--kd-temperature", type=float, default=4.0, help="with --teacher: the temperature T (the KL term carries T^2)")
+    ap.add_argument("--kd-ignored", action="store_true", help="with --teacher: distil on the pixels the labels ignore too")
     ap.add_argument("--split-operands", type=int, default=0, choices=[0, 2, 3],
                     help="opt-in for fp32: matrix products on the 16-bit matrix pipe with split fp32 operands (cvk.set_split_operands; 2 = fp16 x 2)")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
@@ -94,6 +103,13 @@ def main():
     if K < 1 or a.iters % K:
         ap.error("--accumulate K needs K >= 1 and --iters a multiple of K")
     updates = a.iters // K
+    if a.teacher is None and (a.teacher_weights or a.kd_ignored):
+        ap.error("--teacher-weights / --kd-ignored need --teacher")
+    if a.teacher is not None and (a.loss != "ce" or a.label_smoothing):
+        ap.error("--teacher distils next to the plain cross-entropy: --loss ce without --label-smoothing")
+    if a.teacher is not None and a.graphed and K > 1:
+        ap.error("--teacher with --graphed and --accumulate is not provided: the bound teacher-logits buffer holds one batch, not a window; "
+                 "drop --graphed (the eager accumulation loop passes each micro-batch's teacher logits)")
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -135,33 +151,51 @@ def main():
         else:
             ce, dice = {"focal": (1.0, 0.0), "dice": (0.0, 1.0), "ce+dice": (1.0, a.dice_weight)}[a.loss]
             loss_fn = cvk.SegmentationLoss(ce, dice, focal_gamma=a.focal_gamma if a.loss == "focal" else 0.0, weight=weight)
+    teacher = kd = kd_buf = None
+    if a.teacher is not None:
+        teacher = cvk.get_model(a.teacher, 3, 12).to(dev)
+        if a.teacher_weights:
+            teacher.load_state_dict(torch.load(a.teacher_weights, map_location=dev))
+        elif rank == 0:
+            print("--teacher without --teacher-weights: the teacher is freshly initialised; that is good for a smoke run only")
+        teacher.eval().requires_grad_(False)
+        kd = cvk.DistillationLoss(1.0, a.kd_weight, a.kd_temperature, weight=weight, distill_ignored=a.kd_ignored)
     step = None
     for epoch in range(1, a.epochs + 1):
         net.train()
         t0 = time.time()
         norms = []                                                          # device scalars: read once per epoch
-        window = []
+        pending = []                                                        # --graphed --accumulate: the open window's batches
         for it in range(a.iters):
             m = masks[it].to(dev)
             frames = ((m.unsqueeze(-1) * torch.tensor([20, 15, 10], device=dev)) % 256 +
                       torch.randint(0, 30, (a.b, 360, 480, 3), device=dev)).clamp(0, 255).to(torch.uint8)
             images = cvk.preprocess_uint8(frames)                           # transforms.ToTensor + Normalize on device
+            z = None
+            if teacher is not None:
+                with torch.no_grad():
+                    z = teacher(images)                                     # the teacher's logits: a constant of this step
             if a.graphed:
                 if accum is not None:                                       # a window of K batches: [K, N, 3, H, W], [K, N, H, W]
-                    window.append((images, m))
-                    if len(window) < K:
+                    pending.append((images, m))
+                    if len(pending) < K:
                         continue
-                    images, m = torch.stack([w[0] for w in window]), torch.stack([w[1] for w in window])
-                    window = []
+                    images, m = torch.stack([w[0] for w in pending]), torch.stack([w[1] for w in pending])
+                    pending = []
                 if step is None:                                            # capture once, on the first batch of the geometry
+                    if kd is not None:                                      # the captured kernels read the teacher's logits from kd_buf
+                        kd_buf = z.clone()
+                        loss_fn = kd.bind(kd_buf)
                     step = cvk.GraphedStep(net, loss_fn, images, m, allow_grad_sync=world > 1, optimizer=opt, scheduler=sched,
                                            log_capacity=updates, accumulator=accum)
+                if kd is not None:
+                    kd_buf.copy_(z)
                 loss = step.replay(images, m)                               # train.py:124-134 + the log line, one launch
                 continue
             if accum is None or accum.micro_step == 0:
                 opt.zero_grad()                                             # train.py:124
             preds = model(images)                                           # :128
-            loss = loss_fn(preds, m)                                        # :130
+            loss = loss_fn(preds, m) if kd is None else kd(preds, m, z)     # :130
             loss.backward()                                                 # :131
             if accum is not None and not accum.ready:                       # the window is still open: .grad is None, nothing to step
                 continue
@@ -185,6 +219,10 @@ def main():
         if rank == 0:
             print(f"epoch {epoch}: loss {loss.item():.4f}  lr {sched.get_last_lr()[0]:.6f}  "
                   f"{world * a.b * a.iters / dt:.1f} img/s (incl. data synthesis + optimizer)")
+            if kd is not None:                                          # device views of the last step's record
+                kd_h, kd_k = kd.last_terms.tolist()
+                print(f"          distillation: H {kd_h:.4f}  K {kd_k:.4f}  arg-max agreement with the teacher {kd.last_agreement.item():.4f}  "
+                      f"(T {a.kd_temperature:g}, kd weight {a.kd_weight:g})")
             if norms:
                 n = torch.stack([v.detach().float().cpu() for v in norms])
                 print(f"          grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of "

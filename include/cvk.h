@@ -492,6 +492,39 @@ int cvk_seg_loss_bwd(const float* logits, int ld, const int64_t* target, const f
                      const float* record, const float* grad_out, float scale, float* dlogits, int ld_d, int M, int C, int ignore_index,
                      void* stream);
 
+/* ---- knowledge-distillation loss, L = ce H + kd K (cross-entropy on the labels + temperature-softened KL towards a teacher) -------
+ * student: dense NHWC rows [M][ld_s], teacher: [M][ld_t] (each ld >= C, 0 < C <= 128; the two strides are independent), target int64
+ * [M], weight float [C] nullable (all ones): all DEVICE.  ce, kd >= 0, finite and not both 0.  tau = float(1 / T) and t2 = float(T T)
+ * for a temperature T > 0, each evaluated in double by the caller and rounded once; both positive and finite.  For a pixel with
+ * student row x, teacher row z and target t:
+ *   p = softmax(x), ps = softmax(tau x), qs = softmax(tau z),
+ *   kl = sum_c qs_c (log qs_c - log ps_c), taken from the two log-sum-exps (no log of a softmax value; 0 when z holds x's numbers)
+ *   H = sum_{valid} w[t] (lse(x) - x[t]) / sum_{valid} w[t]        (valid: t != ignore_index; the weighted mean of
+ *                                                                   cvk_softmax_ce_fwd_ex; 0/0 = NaN)
+ *   K = t2 sum_{m in D} kl_m / |D|                                 (0/0 = NaN)
+ * D = the valid pixels, or every pixel when distill_ignored != 0 (an ignored pixel has no label but the teacher has an opinion).
+ * Class weights enter H only.  A term whose coefficient is 0 is not computed and cannot make L NaN.  Any target outside [0, C) other
+ * than ignore_index makes L NaN and is counted, as in cvk_softmax_ce_fwd; such a pixel is in neither set.  target may be null when
+ * ce = 0: no pixel has a label, every pixel is in D and counts as valid.  teacher may be null when kd = 0: L = H.
+ * fwd: `part` is DEVICE scratch of cvk_kd_loss_part_floats(M) floats; `record` is DEVICE float[cvk_kd_loss_record_floats()] = float[9]:
+ * [0] = L, [1] = valid pixels, [2] = out-of-range targets, [3] = sum w[t], [4] = H (0 when ce = 0), [5] = K (0 when kd = 0), [6] = |D|,
+ * [7] = pixels of D where student and teacher agree on the arg-max (first index of the maximum, as cvk_argmax_channels; 0 when
+ * kd = 0), [8] = [7] / [6] (0 when kd = 0).  Counts stored as floats are exact up to 2^24 pixels.  Two launches (one pass over both
+ * logit tensors, a one-workgroup fp64 finish); no allocation, no float atomics (every sum in one fixed order: bitwise reproducible), no
+ * host sync.  The pass stages 256 pixel rows of each tensor in LDS while (ld_s + 1) + (ld_t + 1) <= 64 (the teacher's tile is left out
+ * when kd = 0) and walks the rows in global memory beyond that.
+ * bwd: record is fwd's; one pass that re-reads both tensors, dlogits [M][ld_d] (ld_d >= C), the student's gradient only:
+ *   g (ce w[t] / record[3] (p_k - [k = t]) on valid pixels  +  kd t2 tau / record[6] (ps_k - qs_k) on pixels of D),
+ * g = grad_out * scale; grad_out: one DEVICE float, nullable (1).  Rows outside both sets and columns [C, ld_d) are written as zeros. */
+int cvk_kd_loss_part_floats(int M);
+int cvk_kd_loss_record_floats(void);
+int cvk_kd_loss_fwd(const float* student, int ld_s, const float* teacher, int ld_t, const int64_t* target, const float* weight, float ce,
+                    float kd, float tau, float t2, int distill_ignored, float* part, float* record, int M, int C, int ignore_index,
+                    void* stream);
+int cvk_kd_loss_bwd(const float* student, int ld_s, const float* teacher, int ld_t, const int64_t* target, const float* weight, float ce,
+                    float kd, float tau, float t2, int distill_ignored, const float* record, const float* grad_out, float scale,
+                    float* dlogits, int ld_d, int M, int C, int ignore_index, void* stream);
+
 /* ---- OHEM cross-entropy: online hard example mining with an on-device k-th-largest select ---------------------------------------
  * logits: dense NHWC rows [M][ld] (ld >= C, 0 < C <= 128), target int64 [M], weight float [C] nullable (all ones): all DEVICE.
  * A pixel's loss l = lse - x[t] is the unweighted fp32 cross-entropy (>= 0).  V = the valid pixels (t != ignore_index),

@@ -186,6 +186,12 @@ SIGNATURES = {
     "cvk_seg_loss_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_float, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "cvk_seg_loss_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_vp, c_vp, c_float, c_vp, c_int, c_int, c_int, c_int,
                                  c_vp]),
+    "cvk_kd_loss_part_floats": (c_int, [c_int]),
+    "cvk_kd_loss_record_floats": (c_int, []),
+    "cvk_kd_loss_fwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_float, c_int, c_vp, c_vp, c_int, c_int,
+                                c_int, c_vp]),
+    "cvk_kd_loss_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_float, c_float, c_float, c_float, c_int, c_vp, c_vp, c_float, c_vp,
+                                c_int, c_int, c_int, c_int, c_vp]),
     "cvk_ohem_scratch_bytes": (c_int, [c_int]),
     "cvk_ohem_record_floats": (c_int, []),
     "cvk_ohem_ce_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

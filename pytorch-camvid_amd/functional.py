@@ -487,6 +487,194 @@ def ohem_cross_entropy(logits, target, thresh, min_kept, weight=None, ignore_ind
     return _OhemCrossEntropy.apply(logits, target, weight, (lam, min_kept, ignore_index, 1.0))
 
 
+KD_RECORD = 9                                      # loss | valid | out of range | sum w[t] | H | K | |D| | agree | agree / |D|
+
+
+def distillation_scales(temperature):
+    """(tau, t2) = (float32(1 / T), float32(T * T)) of a temperature T > 0: each evaluated in double and rounded once, the two numbers
+    the distillation kernels take."""
+    import numpy as np
+    T = float(temperature)
+    if not 0.0 < T < float("inf"):
+        raise ValueError(f"temperature must be a finite number > 0. Got: {T}")
+    if not 1e-18 <= T <= 1e18:
+        raise ValueError(f"temperature {T} leaves float32's range as 1 / T or T * T")
+    return float(np.float32(1.0 / T)), float(np.float32(T * T))
+
+
+def _check_kd_options(ce, kd, temperature, weight):
+    ce, kd = _nonneg("ce", ce), _nonneg("kd", kd)
+    if ce == 0.0 and kd == 0.0:
+        raise ValueError("ce and kd must not both be 0")
+    if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dim() != 1):
+        raise ValueError("weight must be a 1-D tensor of one value per class")
+    return (ce, kd) + distillation_scales(temperature)
+
+
+class _Distillation(torch.autograd.Function):
+    """ce * cross-entropy + kd * T^2 KL(teacher || student) at temperature T in one forward and one backward pass over both logit
+    tensors (cvk_kd_loss_fwd / _bwd).  The teacher is a constant: its gradient is None."""
+
+    @staticmethod
+    def forward(ctx, logits, target, teacher, weight, opts):
+        ce, kd, tau, t2, distill_ignored, ignore_index, grad_scale = opts
+        lib = _lib.load()
+        if not logits.is_cuda:
+            raise RuntimeError("pytorch_camvid_amd.DistillationLoss needs HIP tensors (no CPU fallback)")
+        if logits.dim() != 4:
+            raise ValueError("expected logits of shape [N, C, H, W]")
+        if logits.dtype != torch.float32:
+            raise RuntimeError(f"expected float32 logits, got {logits.dtype}")
+        N, C, H, W = logits.shape
+        if target is None:
+            if ce > 0.0:
+                raise ValueError("target=None needs ce == 0 (distillation on unlabelled frames)")
+        else:
+            if target.dtype != torch.int64:
+                raise RuntimeError(f"expected float32 logits and int64 target, got {logits.dtype} / {target.dtype}")
+            if tuple(target.shape) != (N, H, W):
+                raise ValueError(f"Expected target size {[N, H, W]}, got {list(target.shape)}")
+            if target.device != logits.device:
+                raise RuntimeError(f"target is on {target.device} but the logits are on {logits.device}")
+        if teacher is None:
+            if kd > 0.0:
+                raise ValueError("teacher_logits=None needs kd == 0")
+        elif tuple(teacher.shape) != tuple(logits.shape) or teacher.dtype != logits.dtype or teacher.device != logits.device:
+            raise ValueError(f"the teacher's logits must match the student's: student {list(logits.shape)} {logits.dtype} on "
+                             f"{logits.device}, teacher {list(teacher.shape)} {teacher.dtype} on {teacher.device}")
+        if weight is not None:
+            if weight.dim() != 1 or weight.numel() != C:
+                raise RuntimeError(f"weight tensor should be defined either for all {C} classes or no classes but got weight tensor "
+                                   f"of shape: {list(weight.shape)}")
+            if weight.device != logits.device:
+                raise RuntimeError(f"weight is on {weight.device} but the logits are on {logits.device} (no implicit copy: the loss "
+                                   "stays capturable); move the loss module with .to(device)")
+            if weight.dtype != torch.float32:
+                raise RuntimeError(f"expected a float32 weight, got {weight.dtype}")
+            weight = weight.detach().contiguous()
+        M = N * H * W
+        if not 1 <= C <= 128 or M <= 0:
+            raise RuntimeError(f"pytorch_camvid_amd.DistillationLoss serves 1 to 128 classes and a non-empty batch, got C = {C}, M = {M}")
+        lg, ld = _as_nhwc(logits)
+        tg = target.contiguous() if target is not None else None
+        tc, ld_t = _as_nhwc(teacher.detach()) if teacher is not None and kd > 0.0 else (None, 0)
+        part = torch.empty(lib.cvk_kd_loss_part_floats(M), device=logits.device, dtype=torch.float32)
+        rec = torch.empty(lib.cvk_kd_loss_record_floats(), device=logits.device, dtype=torch.float32)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        from . import engine
+        engine._timed(None, "k_kd_fwd", 4.0 * M * (ld + ld_t) + 8.0 * M, lambda: check(
+            lib.cvk_kd_loss_fwd(lg.data_ptr(), ld, ptr(tc), ld_t, ptr(tg), ptr(weight), ce, kd, tau, t2, int(bool(distill_ignored)),
+                                part.data_ptr(), rec.data_ptr(), M, C, int(ignore_index), _stream(logits)), "cvk_kd_loss_fwd"), "byte")
+        ctx.save_for_backward(lg, tc, tg, rec, weight)
+        ctx.meta = (N, C, H, W, ld, ld_t, ce, kd, tau, t2, int(bool(distill_ignored)), float(grad_scale), int(ignore_index))
+        _CrossEntropy.last_status = rec
+        return rec[0].clone()           # not a view: rec is saved for backward (the two divisors) and published as the status
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        lg, tc, tg, rec, weight = ctx.saved_tensors
+        N, C, H, W, ld, ld_t, ce, kd, tau, t2, distill_ignored, grad_scale, ignore_index = ctx.meta
+        M = N * H * W
+        d = torch.empty((N, H, W, C), device=lg.device, dtype=torch.float32)
+        g = gout.contiguous()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        from . import engine
+        engine._timed(None, "k_kd_bwd", 4.0 * M * (ld + ld_t) + 8.0 * M + 4.0 * M * C, lambda: check(
+            lib.cvk_kd_loss_bwd(lg.data_ptr(), ld, ptr(tc), ld_t, ptr(tg), ptr(weight), ce, kd, tau, t2, distill_ignored, rec.data_ptr(),
+                                g.data_ptr(), grad_scale, d.data_ptr(), C, M, C, ignore_index, _stream(lg)), "cvk_kd_loss_bwd"), "byte")
+        return d.permute(0, 3, 1, 2), None, None, None, None
+
+
+class _BoundDistillation:
+    """`DistillationLoss.bind(buf)`: the two-argument `loss_fn(logits, target)` over a persistent teacher-logits buffer; `.loss` is the
+    module, `.teacher_logits` the buffer."""
+
+    def __init__(self, loss, buf):
+        self.loss, self.teacher_logits = loss, buf
+
+    def __call__(self, logits, target):
+        return self.loss(logits, target, self.teacher_logits)
+
+
+class DistillationLoss(nn.Module):
+    """Pixel-wise knowledge distillation (Hinton et al.) as one autograd node: `ce * H + kd * K`, one HIP pass over the student's and
+    the teacher's logits forward (plus a one-workgroup finish), one backward.  With x a pixel's student logits, z the teacher's,
+    T = `temperature`, tau = float32(1 / T) and t2 = float32(T * T) (`distillation_scales`):
+      H = sum w[t] (lse(x) - x[t]) / sum w[t] over the valid pixels (t != `ignore_index`): torch's weighted mean cross-entropy
+      K = t2 / |D| * sum over D of KL(softmax(tau z) || softmax(tau x))
+    D = the valid pixels, or every pixel of the batch with `distill_ignored=True` (CamVid's void class has no label, but the teacher
+    still has an opinion there).  `weight` (float32 [C] on the logits' device, a registered buffer) enters H only.  A term whose
+    coefficient is 0 is not computed: `kd=0` needs no teacher and is the weighted cross-entropy, `ce=0` needs no target
+    (`loss(logits, None, teacher_logits)`: unlabelled frames, every pixel in D).  The gradient goes to the student only; the teacher's
+    logits are a constant even if they require a gradient.  They must have the student's shape, dtype and device; channels_last (as the
+    package's networks return them, padded pixel stride included) is read in place, any other layout is copied once.
+    Conventions of CrossEntropyLoss hold: float32 logits [N, C, H, W] (C <= 128), int64 targets [N, H, W], a 0-dim loss, an out-of-range
+    target makes the loss NaN (such a pixel is in neither set) and `last_ce_status()` reports it, no valid pixel gives H = 0/0 = NaN,
+    `grad_scale` multiplies the backward only.  All sums run in a fixed order without float atomics: loss and gradient are bitwise
+    reproducible.  `ce`, `kd`, `temperature` and `distill_ignored` are read at every call, so a temperature schedule is an assignment
+    (a captured `GraphedStep` keeps the values it was captured with).
+    After a forward, device views for logging without a sync: `last_terms` ([H, K]), `last_agreement` (the share of D where student
+    and teacher agree on the arg-max, first maximum as `argmax_channels`) and `last_record` ([loss, valid, out of range, sum w[t], H,
+    K, |D|, agree, agree / |D|]).
+    `bind(buf)` gives the two-argument form every `loss_fn(logits, target)` interface takes (`GraphedStep`, `evaluate_report`,
+    `GradAccumulator`'s eager loop): `buf` is a persistent tensor of the logits' shape, and before each `step.replay(x, t)` the caller
+    writes `buf.copy_(teacher(x))` under `no_grad` on the same stream.  Not provided: the teacher's forward inside the captured
+    graph; the bound form together with `GraphedStep(accumulator=)` (one buffer cannot hold a window: the eager accumulation loop,
+    which passes each micro-batch's teacher logits, does work); per-class temperatures; feature- or attention-map distillation; an
+    EMA ("mean") teacher.  Under `ddp.DataParallel` the sums (and |D|) are per rank, as the Dice sums of SegmentationLoss are."""
+
+    def __init__(self, ce=1.0, kd=1.0, temperature=4.0, *, weight=None, ignore_index=-100, distill_ignored=False, grad_scale=1.0):
+        super().__init__()
+        self.ce, self.kd, _, _ = _check_kd_options(ce, kd, temperature, weight)
+        self.temperature = float(temperature)
+        self.distill_ignored = bool(distill_ignored)
+        self.ignore_index = ignore_index
+        self.grad_scale = grad_scale
+        self.register_buffer("weight", weight)
+        self._record = None
+
+    def forward(self, logits, target, teacher_logits=None):
+        ce, kd, tau, t2 = _check_kd_options(self.ce, self.kd, self.temperature, self.weight)
+        loss = _Distillation.apply(logits, target, teacher_logits, self.weight,
+                                   (ce, kd, tau, t2, self.distill_ignored, self.ignore_index, self.grad_scale))
+        self._record = _CrossEntropy.last_status
+        return loss
+
+    def bind(self, buf):
+        """`(logits, target) -> self(logits, target, buf)` over the persistent teacher-logits tensor `buf`."""
+        if not isinstance(buf, torch.Tensor) or buf.dim() != 4:
+            raise ValueError("bind() takes the persistent teacher-logits tensor, [N, C, H, W]")
+        return _BoundDistillation(self, buf)
+
+    def _rec(self):
+        if self._record is None:
+            raise RuntimeError("no forward has run yet")
+        return self._record
+
+    @property
+    def last_record(self):
+        """The device record of the most recent forward (float32 [9], no sync)."""
+        return self._rec()
+
+    @property
+    def last_terms(self):
+        """[H, K] of the most recent forward (device tensor, no sync)."""
+        return self._rec()[4:6]
+
+    @property
+    def last_agreement(self):
+        """Share of the pixels of D where student and teacher agree on the arg-max (0-dim device view, no sync)."""
+        return self._rec()[8]
+
+
+def distillation_loss(logits, target, teacher_logits, ce=1.0, kd=1.0, temperature=4.0, *, weight=None, ignore_index=-100,
+                      distill_ignored=False):
+    """Functional form of DistillationLoss (same kernels)."""
+    ce, kd, tau, t2 = _check_kd_options(ce, kd, temperature, weight)
+    return _Distillation.apply(logits, target, teacher_logits, weight, (ce, kd, tau, t2, bool(distill_ignored), ignore_index, 1.0))
+
+
 def last_ce_status():
     """(valid pixels, out-of-range targets) of the most recent cross-entropy forward — one device->host copy; raises
     IndexError like torch's `Target out of bounds` when the second number is not zero."""
