@@ -35,6 +35,19 @@ def synthetic_camvid(n, b, seed):
         yield np.clip(frames, 0, 255).astype(np.uint8), masks
 
 
+def validate(net, batches, tta, window, boundary):
+    """(accuracy, mIoU, boundary F1 or None) of one validation pass."""
+    if boundary is None:
+        acc, _, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window)
+        return acc, miou, None
+    rep = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window, boundary=boundary)
+    return rep["accuracy"], rep["miou"], rep["bf"]
+
+
+def bf_text(bf):
+    return "" if bf is None else f"  BF {bf:.4f}"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-net", "--net", default="unet")
@@ -84,8 +97,16 @@ def main():
                     help="validate by sliding-window inference with crops of this size, e.g. 360,480 (cvk.SlidingWindow); with --tta-scales / "
                     "--tta-flip every view is evaluated in windows")
     ap.add_argument("--window-stride", default=None, metavar="H,W", help="with --window-crop: the step between windows (default: two thirds of the crop)")
+    ap.add_argument("--boundary-f1", action="store_true", help="also report the boundary F1 measure (BF score) of the validation pass (cvk.BoundaryMeter)")
+    ap.add_argument("--bf-tolerance", type=float, default=0.0075, metavar="X",
+                    help="with --boundary-f1: the matching distance as a fraction of the image diagonal (default 0.75 %%)")
     a = ap.parse_args()
-    tta = window = None
+    tta = window = boundary = None
+    if a.boundary_f1:
+        try:
+            boundary = cvk.BoundaryMeter(num_classes=12, ignore_index=11, tolerance=a.bf_tolerance)
+        except ValueError as e:
+            ap.error(f"--bf-tolerance: {e}")
     if a.window_stride and not a.window_crop:
         ap.error("--window-stride needs --window-crop")
     if a.window_crop:
@@ -205,13 +226,13 @@ def main():
             print(f"  grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of {n.numel()} steps "
                   f"(max_norm {a.clip_grad_norm:g})")
         val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
-        acc, iou, miou = cvk.evaluate(net, val, num_classes=12, ignore_index=11, tta=tta, window=window)
-        print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}")
+        acc, miou, bf = validate(net, val, tta, window, boundary)
+        print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}{bf_text(bf)}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
                 val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)    # the same frames again
-                acc_e, _, miou_e = cvk.evaluate(net, val, num_classes=12, ignore_index=11, tta=tta, window=window)
-            print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
+                acc_e, miou_e, bf_e = validate(net, val, tta, window, boundary)
+            print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}{bf_text(bf_e)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
 
 
 if __name__ == "__main__":

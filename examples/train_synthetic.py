@@ -23,6 +23,19 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pytorch_camvid_amd as cvk  # noqa: E402
 
 
+def validate(net, batches, tta, window, boundary):
+    """(accuracy, mIoU, boundary F1 or None) of one validation pass."""
+    if boundary is None:
+        acc, _, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window)
+        return acc, miou, None
+    rep = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window, boundary=boundary)
+    return rep["accuracy"], rep["miou"], rep["bf"]
+
+
+def bf_text(bf):
+    return "" if bf is None else f"  BF {bf:.4f}"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-net", "--net", default="unet")
@@ -77,8 +90,16 @@ def main():
                     help="validate by sliding-window inference with crops of this size, e.g. 360,480 (cvk.SlidingWindow); with --tta-scales / "
                     "--tta-flip every view is evaluated in windows")
     ap.add_argument("--window-stride", default=None, metavar="H,W", help="with --window-crop: the step between windows (default: two thirds of the crop)")
+    ap.add_argument("--boundary-f1", action="store_true", help="also report the boundary F1 measure (BF score) of the validation pass (cvk.BoundaryMeter)")
+    ap.add_argument("--bf-tolerance", type=float, default=0.0075, metavar="X",
+                    help="with --boundary-f1: the matching distance as a fraction of the image diagonal (default 0.75 %%)")
     a = ap.parse_args()
-    tta = window = None
+    tta = window = boundary = None
+    if a.boundary_f1:
+        try:
+            boundary = cvk.BoundaryMeter(num_classes=12, ignore_index=11, tolerance=a.bf_tolerance)
+        except ValueError as e:
+            ap.error(f"--bf-tolerance: {e}")
     if a.window_stride and not a.window_crop:
         ap.error("--window-stride needs --window-crop")
     if a.window_crop:
@@ -233,14 +254,14 @@ def main():
             m = masks[it].to(dev)
             frames = ((m.unsqueeze(-1) * torch.tensor([20, 15, 10], device=dev)) % 256).clamp(0, 255).to(torch.uint8)
             batches.append((cvk.preprocess_uint8(frames), m))
-        acc, iou, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window)
+        acc, miou, bf = validate(net, batches, tta, window, boundary)
         if rank == 0:
-            print(f"          val acc {acc:.4f}  mIoU(11 classes) {miou:.4f}")
+            print(f"          val acc {acc:.4f}  mIoU(11 classes) {miou:.4f}{bf_text(bf)}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
-                acc_e, _, miou_e = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window)
+                acc_e, miou_e, bf_e = validate(net, batches, tta, window, boundary)
             if rank == 0:
-                print(f"          EMA acc {acc_e:.4f}  mIoU(11 classes) {miou_e:.4f}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
+                print(f"          EMA acc {acc_e:.4f}  mIoU(11 classes) {miou_e:.4f}{bf_text(bf_e)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
     if rank == 0:
         torch.save(net.state_dict(), "/tmp/cvk_synthetic.pth")             # train.py:232-240; loads into the reference too
         if a.ema_decay is not None:

@@ -566,6 +566,25 @@ int cvk_argmax_channels(const float* logits, int ld, int64_t* out, int M, int C,
 int cvk_confusion_accumulate(const int64_t* pred, const int64_t* label, int64_t* hist, int M, int num_classes,
                              int ignore_index, void* stream);
 
+/* ---- boundary F1 (BF score; Csurka et al., BMVC 2013): per-image, per-class contour counts (not in the reference) -------
+ * pred, label: DEVICE int64 [N][H][W]; 1 <= num_classes <= 32; r2: squared tolerance in pixels, 0 <= r2 <= 256.
+ * A pixel is void iff label == ignore_index, in both maps (the prediction is masked by the label).  A non-void pixel z of a map X
+ * (the masked prediction or the label) is a boundary pixel of class c iff X(z) = c, 0 <= c < num_classes, c != ignore_index, and at
+ * least one of its 4-neighbours inside the image is non-void and holds a value other than c.  A value outside [0, num_classes), or
+ * ignore_index at a non-void pixel, has no boundary of its own, is different from every class for its neighbours and indexes
+ * nothing.  A boundary pixel of class c in one map is matched iff the other map has a boundary pixel of class c at an integer
+ * offset (dy, dx), dy * dy + dx * dx <= r2, inside the same image.
+ * cvk_boundary_counts ADDS into DEVICE int64 counts[N][4][num_classes] (the caller zeroes it): row 0 = prediction boundary pixels,
+ * row 1 = those matched in the label map, row 2 = label boundary pixels, row 3 = those matched in the prediction map.  One launch,
+ * integer atomics only (exact: the result does not depend on the order or on the tiling), no allocation, no host sync.
+ * cvk_boundary_map writes the boundary map of `map` alone: out_u8 [N][H][W] = the class whose boundary the pixel carries, or 255.
+ * void_from (nullable) is the label map whose ignore_index pixels are void; NULL: map's own.  Both entry points evaluate one rule.
+ * N * H * W < 2^31. */
+int cvk_boundary_counts(const int64_t* pred, const int64_t* label, int64_t* counts, int N, int H, int W, int num_classes,
+                        int ignore_index, int r2, void* stream);
+int cvk_boundary_map(const int64_t* map, const int64_t* void_from, uint8_t* out_u8, int N, int H, int W, int num_classes,
+                     int ignore_index, void* stream);
+
 /* ---- multi-scale / flip test-time augmentation: the merge of the views' logits (not in the reference) ------------------
  * Bilinear resampling here is torch's F.interpolate(mode="bilinear", align_corners=False) with the sample position taken from
  * integers: for destination index d of `out` samples over `in` source samples, num = max((2 d + 1) in - out, 0), lower source

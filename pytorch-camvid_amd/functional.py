@@ -10,6 +10,9 @@
   ConfusionMeter    <- utils.intersect_and_union / mean_iou (utils.py:162-228) accumulated on device, with the
                        np.float crash (utils.py:210) and the per-batch-sum bug of train.py:192-206 not reproduced
                        (SURVEY.md §0.5): IoU = sum(intersection)/sum(union) per class over the whole set.
+  BoundaryMeter, label_boundaries, boundary_tolerance, boundary_scores
+                    <- the boundary F1 measure (BF score, Csurka et al. BMVC 2013; not in the reference): per-image, per-class
+                       contour counts from one launch, scores on the host
 """
 import torch
 import torch.nn as nn
@@ -736,6 +739,136 @@ class ConfusionMeter:
         return float(prec), float(rec)
 
 
+BOUNDARY_MAX_RADIUS2 = 256       # include/cvk.h: cvk_boundary_counts serves squared tolerances up to 16 * 16 pixels
+
+
+def boundary_tolerance(H, W, tolerance=0.0075):
+    """Squared matching distance of the boundary F1 measure for an H x W image, in pixels: floor((tolerance * diagonal)^2), in exact
+    rational arithmetic (`tolerance` is read through its decimal string).  The default is 0.75 % of the diagonal (Csurka et al., the
+    SegNet paper): 360 x 480 -> 20, 720 x 960 -> 81."""
+    from fractions import Fraction
+    q = Fraction(str(tolerance))
+    if q < 0:
+        raise ValueError(f"tolerance must not be negative. Got: {tolerance!r}")
+    r2 = (q * q * (int(H) * int(H) + int(W) * int(W))).__floor__()
+    if r2 > BOUNDARY_MAX_RADIUS2:
+        raise ValueError(f"a tolerance of {tolerance!r} on {H} x {W} pixels is a squared distance of {r2}; the kernel serves at most "
+                         f"{BOUNDARY_MAX_RADIUS2} (16 pixels)")
+    return int(r2)
+
+
+def _check_radius2(r2):
+    if isinstance(r2, bool) or not isinstance(r2, int) or r2 < 0:
+        raise ValueError(f"radius2 must be a non-negative integer. Got: {r2!r}")
+    if r2 > BOUNDARY_MAX_RADIUS2:
+        raise ValueError(f"radius2 {r2} is above the limit of {BOUNDARY_MAX_RADIUS2} (16 pixels)")
+    return r2
+
+
+def boundary_scores(counts, ignore_index=None):
+    """The boundary F1 scores of per-image, per-class counts [images, 4, K] (rows: prediction boundary pixels nP, those matched mP,
+    label boundary pixels nG, those matched mG), in float64 on the host.  A class is evaluated in an image iff nP + nG > 0;
+    P = mP / nP, R = mG / nG, F = 2 P R / (P + R), each 0 where its denominator is.  Returns
+      "bf": the mean over the images with an evaluated class of the image's mean F over its evaluated classes (NaN without one),
+      "bf_per_class", "precision", "recall": float64 [K], per class the mean F / P / R over the images where it is evaluated (NaN
+          where it never is, and at ignore_index),
+      "pooled": the image score of the counts summed over all images,
+      "images": how many images had an evaluated class."""
+    import numpy as np
+    c = np.asarray(counts, dtype=np.int64)
+    if c.ndim != 3 or c.shape[1] != 4:
+        raise ValueError(f"expected counts of shape [images, 4, K], got {list(c.shape)}")
+    K = c.shape[2]
+
+    def prf(c4):
+        nP, mP, nG, mG = (c4[..., r, :].astype(np.float64) for r in range(4))
+        ev = (nP + nG) > 0
+        P = np.divide(mP, nP, out=np.zeros_like(nP), where=nP > 0)
+        R = np.divide(mG, nG, out=np.zeros_like(nG), where=nG > 0)
+        F = np.divide(2.0 * P * R, P + R, out=np.zeros_like(P), where=(P + R) > 0)
+        return ev, P, R, F
+
+    def masked_mean(v, ev, axis):
+        n = ev.sum(axis=axis)
+        return np.divide(np.where(ev, v, 0.0).sum(axis=axis), n, out=np.full(n.shape, np.nan), where=n > 0)
+
+    ev, P, R, F = prf(c)
+    image = masked_mean(F, ev, 1)                         # [images], NaN where nothing is evaluated
+    scored = ~np.isnan(image)
+    per_class, prec, rec = masked_mean(F, ev, 0), masked_mean(P, ev, 0), masked_mean(R, ev, 0)
+    if ignore_index is not None and 0 <= ignore_index < K:
+        per_class[ignore_index] = prec[ignore_index] = rec[ignore_index] = np.nan
+    evp, _, _, Fp = prf(c.sum(axis=0))
+    return {"bf": float(image[scored].mean()) if scored.any() else float("nan"), "bf_per_class": per_class, "precision": prec,
+            "recall": rec, "pooled": float(Fp[evp].mean()) if evp.any() else float("nan"), "images": int(scored.sum())}
+
+
+def _check_boundary_maps(who, pred, label):
+    ok = all(isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.dim() == 3 for t in (pred, label))
+    if not ok or pred.shape != label.shape or pred.numel() == 0:
+        raise ValueError(f"{who}: expected int64 tensors of one shape [N, H, W]")
+    if not (pred.is_cuda and label.is_cuda) or pred.device != label.device:
+        raise ValueError(f"{who}: expected both tensors on one GPU (no CPU fallback)")
+
+
+class BoundaryMeter:
+    """Boundary F1 measure (BF score; Csurka et al., BMVC 2013; MATLAB's bfscore) of predictions against labels: per image and class,
+    the 4-connected contour pixels of both maps and how many of them have a contour pixel of the same class in the other map within
+    the tolerance, counted on the device by one launch per batch (cvk_boundary_counts, exact integers), no host sync until
+    `counts()` / `compute()`.  The tolerance is `tolerance` times the image diagonal of each batch (`boundary_tolerance`), or the
+    squared pixel distance `radius2`.  Pixels whose label is `ignore_index` are void in both maps."""
+
+    def __init__(self, num_classes=12, ignore_index=11, tolerance=0.0075, radius2=None):
+        if not 1 <= num_classes <= 32:
+            raise ValueError(f"BoundaryMeter serves 1 to 32 classes. Got: {num_classes}")
+        self.num_classes, self.ignore_index, self.tolerance = int(num_classes), int(ignore_index), tolerance
+        self.radius2 = None if radius2 is None else _check_radius2(radius2)
+        if radius2 is None:
+            boundary_tolerance(1, 1, tolerance)           # a bad tolerance fails here, not in the first batch
+        self._parts = []
+
+    def reset(self):
+        self._parts = []
+
+    def update(self, pred, label):
+        _check_boundary_maps("BoundaryMeter.update", pred, label)
+        lib = _lib.load()
+        N, H, W = pred.shape
+        r2 = self.radius2 if self.radius2 is not None else boundary_tolerance(H, W, self.tolerance)
+        p = pred.contiguous(); l = label.contiguous()
+        part = torch.zeros((N, 4, self.num_classes), device=p.device, dtype=torch.int64)
+        check(lib.cvk_boundary_counts(p.data_ptr(), l.data_ptr(), part.data_ptr(), N, H, W, self.num_classes, self.ignore_index, r2,
+                                      _stream(p)), "cvk_boundary_counts")
+        self._parts.append(part)
+
+    def counts(self):
+        """int64 [images, 4, num_classes] on the host (rows nP, mP, nG, mG), in the order of the updates — one device->host copy."""
+        if not self._parts:
+            return torch.zeros((0, 4, self.num_classes), dtype=torch.int64)
+        return (self._parts[0] if len(self._parts) == 1 else torch.cat(self._parts)).cpu()
+
+    def compute(self):
+        """`boundary_scores` of `counts()`: {"bf", "bf_per_class", "precision", "recall", "pooled", "images"}."""
+        return boundary_scores(self.counts().numpy(), self.ignore_index)
+
+
+def label_boundaries(labels, num_classes=12, ignore_index=11, void_from=None):
+    """uint8 [N,H,W]: the class whose 4-connected boundary each pixel of the int64 map `labels` carries under BoundaryMeter's rule, 255
+    where it carries none.  `void_from` is the label map whose `ignore_index` pixels are void (for a prediction map); None: the map's
+    own.  The kernel shares the rule's device function with the counting kernel."""
+    _check_boundary_maps("label_boundaries", labels, labels if void_from is None else void_from)
+    if not 1 <= num_classes <= 32:
+        raise ValueError(f"label_boundaries serves 1 to 32 classes. Got: {num_classes}")
+    lib = _lib.load()
+    m = labels.contiguous()
+    v = None if void_from is None else void_from.contiguous()
+    N, H, W = m.shape
+    out = torch.empty((N, H, W), device=m.device, dtype=torch.uint8)
+    check(lib.cvk_boundary_map(m.data_ptr(), None if v is None else v.data_ptr(), out.data_ptr(), N, H, W, int(num_classes),
+                               int(ignore_index), _stream(m)), "cvk_boundary_map")
+    return out
+
+
 WEIGHT_METHODS = ("median_frequency", "enet")
 
 
@@ -1097,8 +1230,9 @@ class TestTimeAugmentation:
         return self._merge(net, images)
 
 
-def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None):
-    """evaluate / evaluate_report with test-time augmentation: (meter, the per-batch losses of the loss view: empty without one)."""
+def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None, boundary=None):
+    """evaluate / evaluate_report with test-time augmentation: (meter, the per-batch losses of the loss view: empty without one).
+    `boundary` (a BoundaryMeter) sees the predictions the ConfusionMeter sees."""
     meter, losses = None, []
 
     def keep_loss(masks, want):
@@ -1113,6 +1247,8 @@ def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None):
         if meter is None:
             meter = ConfusionMeter(num_classes, ignore_index, pred.device)
         meter.update(pred, masks)
+        if boundary is not None:
+            boundary.update(pred, masks)
     return meter, losses
 
 
@@ -1154,18 +1290,30 @@ def evaluate(net, batches, num_classes=12, ignore_index=11, window=None, tta=Non
     return meter.compute()
 
 
-def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None, window=None, tta=None):
+def _with_boundary(report, boundary):
+    if boundary is not None:
+        bf = boundary.compute()
+        report["bf"], report["bf_per_class"] = bf["bf"], bf["bf_per_class"]
+    return report
+
+
+def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None, window=None, boundary=None, tta=None):
     """The report of reference eval.py:44-80: {"miou", "precision", "recall", "loss" (mean over batches), "accuracy",
     "iou" (per class)} for a set of (images, masks) batches on the GPU; eval-mode forward under no_grad, argmax and
     histograms on the device, one host copy at the end (the reference copies N*H*W int64 per batch, eval.py:60-62).
     With `tta` (a TestTimeAugmentation) the predictions are the merged ones and "loss" is `loss_fn` of the logits of the
     scale-1.0 unmirrored view at the label size: None when that view is not among the views.  With `window` (a SlidingWindow) the
     predictions and the logits `loss_fn` sees are the windows' merged ones.  One of the two: TestTimeAugmentation(..., window=) combines
-    them."""
+    them.  With `boundary` (a BoundaryMeter) the meter is reset, sees every batch's predictions and masks, and the report gains "bf"
+    (the boundary F1 measure) and "bf_per_class"; the meter keeps its counts for `boundary.compute()`."""
     _check_tta_window("evaluate_report", tta, window)
+    if boundary is not None and not isinstance(boundary, BoundaryMeter):
+        raise ValueError(f"boundary must be a BoundaryMeter or None. Got: {type(boundary).__name__}")
     loss_fn = loss_fn or CrossEntropyLoss()
+    if boundary is not None:
+        boundary.reset()
     if tta is not None:
-        meter, losses = _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn)
+        meter, losses = _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn, boundary)
         if meter is None:
             raise ValueError("evaluate_report(): no batches")
         acc, iou, miou = meter.compute()
@@ -1176,7 +1324,7 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
             for l in losses[1:]:
                 loss_sum = loss_sum + l
             loss = float(loss_sum) / len(losses)
-        return {"miou": miou, "precision": prec, "recall": rec, "loss": loss, "accuracy": acc, "iou": iou}
+        return _with_boundary({"miou": miou, "precision": prec, "recall": rec, "loss": loss, "accuracy": acc, "iou": iou}, boundary)
     was_training = net.training
     net.eval()
     meter, loss_sum, n = None, None, 0
@@ -1193,12 +1341,15 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
             loss_sum = l if loss_sum is None else loss_sum + l
             n += 1
             meter.update(pred, masks)
+            if boundary is not None:
+                boundary.update(pred, masks)
     net.train(was_training)
     if meter is None:
         raise ValueError("evaluate_report(): no batches")
     acc, iou, miou = meter.compute()
     prec, rec = meter.precision_recall()
-    return {"miou": miou, "precision": prec, "recall": rec, "loss": float(loss_sum) / n, "accuracy": acc, "iou": iou}
+    return _with_boundary({"miou": miou, "precision": prec, "recall": rec, "loss": float(loss_sum) / n, "accuracy": acc, "iou": iou},
+                          boundary)
 
 
 def predict(net, image_u8, out_size=None, mean=CAMVID_MEAN, std=CAMVID_STD, window=None, tta=None):
