@@ -59,13 +59,18 @@ def main():
     ap.add_argument("--class-weights", default="none", choices=["none", "median_frequency", "enet"],
                     help="class-weighted loss, weights from one pass over the training masks (cvk.class_weights)")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
-    ap.add_argument("--loss", default="ce", choices=["ce", "focal", "dice", "ce+dice", "ohem"],
+    ap.add_argument("--loss", default="ce", choices=["ce", "focal", "dice", "ce+dice", "ohem", "lovasz", "ce+lovasz"],
                     help="ce: cvk.CrossEntropyLoss (the reference's loss); focal, dice, ce+dice: cvk.SegmentationLoss, one fused pass; "
-                         "ohem: cvk.OhemCrossEntropyLoss, online hard example mining")
+                         "ohem: cvk.OhemCrossEntropyLoss, online hard example mining; lovasz, ce+lovasz: cvk.LovaszSoftmaxLoss, the "
+                         "Jaccard surrogate alone or added to the (weighted) cross-entropy")
     ap.add_argument("--focal-gamma", type=float, default=2.0, help="--loss focal: the focusing exponent")
     ap.add_argument("--dice-weight", type=float, default=0.5, help="--loss ce+dice: the Dice term's coefficient")
     ap.add_argument("--ohem-thresh", type=float, default=0.7, help="--loss ohem: keep the pixels whose target probability is below this")
     ap.add_argument("--ohem-min-kept", type=int, default=100000, help="--loss ohem: never keep fewer than this many of the hardest pixels")
+    ap.add_argument("--lovasz-weight", type=float, default=1.0, help="--loss lovasz, ce+lovasz: the Lovász term's coefficient")
+    ap.add_argument("--lovasz-per-image", action="store_true", help="--loss lovasz, ce+lovasz: one Lovász loss per image, averaged")
+    ap.add_argument("--lovasz-classes", default="present", choices=["present", "all"],
+                    help="--loss lovasz, ce+lovasz: average over the classes that occur in a segment, or over all of them")
     ap.add_argument("--teacher", default=None, choices=["unet", "segnet"],
                     help="knowledge distillation: train --net under this network's logits with cvk.DistillationLoss (cross-entropy on the "
                          "labels + --kd-weight * temperature-softened KL towards the teacher); the teacher runs in eval mode under no_grad")
@@ -161,6 +166,11 @@ def main():
             raise SystemExit("--label-smoothing belongs to --loss ce")
         if a.loss == "ohem":
             loss_fn = cvk.OhemCrossEntropyLoss(a.ohem_thresh, a.ohem_min_kept, weight=weight)
+        elif a.loss in ("lovasz", "ce+lovasz"):
+            if a.loss == "lovasz" and weight is not None:
+                raise SystemExit("--class-weights enter the cross-entropy term: use --loss ce+lovasz")
+            loss_fn = cvk.LovaszSoftmaxLoss(a.lovasz_weight, 1.0 if a.loss == "ce+lovasz" else 0.0, classes=a.lovasz_classes,
+                                            per_image=a.lovasz_per_image, weight=weight)
         else:
             ce, dice = {"focal": (1.0, 0.0), "dice": (0.0, 1.0), "ce+dice": (1.0, a.dice_weight)}[a.loss]
             loss_fn = cvk.SegmentationLoss(ce, dice, focal_gamma=a.focal_gamma if a.loss == "focal" else 0.0, weight=weight)

@@ -551,6 +551,55 @@ int cvk_ohem_ce_bwd(const float* logits, int ld, const int64_t* target, const fl
                     const float* loss_px, const float* grad_out, float scale, float* dlogits, int ld_d, int M, int C, int ignore_index,
                     void* stream);
 
+/* ---- Lovász-softmax loss (Berman, Triki, Blaschko, CVPR 2018) with an on-device segmented radix sort; not in the reference --------
+ * loss = lovasz * J + ce * H.  logits: dense NHWC rows [M][ld] (ld >= C, 0 < C <= 128), target int64 [M], weight float [C] nullable
+ * (all ones, enters H only): all DEVICE.  M = N * pixels_per_image.  A segment is the whole batch (per_image = 0) or one image
+ * (per_image = 1): S = 1 or N segments of P = M / S pixels.  Per segment and class c, over the valid pixels (t != ignore_index and t in
+ * [0, C)) in memory order i, with p = softmax(x) in fp32:
+ *   e_i = p_i[c] where t_i != c, and (sum_{j != c} exp_j) / sum_j exp_j where t_i = c;  G = the number of pixels with t_i = c
+ *   order the valid pixels by e descending, ties by ascending i; at position n with F foreground pixels strictly before it,
+ *   U = G + n - F, I = G - F:  g = 1 / U (foreground), g = I / (U (U + 1)) (background); G = 0: g = 1 at n = 0, else 0
+ *   (evaluated in fp64, rounded once to fp32);  L_c = sum e_i g_i in fp64 in sorted order.
+ * A (segment, class) pair is evaluated when the segment has a valid pixel and (classes_mode = CVK_LOVASZ_ALL or G > 0).  Segment loss =
+ * mean of L_c over its K evaluated classes; a segment with K = 0 is not counted; J = mean over the counted segments (none: 0).
+ * H = the weighted mean cross-entropy of cvk_softmax_ce_fwd_ex (label_smoothing 0), computed only when ce > 0 (0/0 = NaN when no pixel
+ * is valid).  lovasz > 0, ce >= 0, both finite; weight needs ce > 0.  A target outside [0, C) other than ignore_index makes the loss NaN
+ * and is counted; such a pixel and the ignored ones take part in no order and get a zero gradient row.
+ * The order comes from a stable LSD radix sort, CVK_LOVASZ_DIGIT_BITS bits a pass over the 32-bit key 0x3f800000 - bits(e) (ignored:
+ * 0xffffffff), S * C independent segments, work-groups of CVK_LOVASZ_SORT_TILE elements; histograms are integer counts, every float sum
+ * has one fixed order: loss and gradient are bitwise reproducible.  Limits: P < 2^30, S * C <= 65535, ceil(P / tile) <= 2^22.
+ * workspace: DEVICE, cvk_lovasz_workspace_bytes(M, C, segments) bytes (0: unsupported sizes), 16-byte aligned, contents need not be
+ *   initialised.  Bytes [0, 8 M C) hold the sorted elements after fwd: segment (s, c) at element (s C + c) P, each uint64 =
+ *   key << 32 | pixel index inside the segment << 1 | foreground bit.  Bytes [8 M C, 16 M C) are the second sort buffer.  Bytes
+ *   [16 M C, 20 M C) are room for a dense g map ([M][C] floats) that `gmap` may point to; tables follow.
+ * gmap: DEVICE float [M][ld_g] (ld_g >= C): g of every valid pixel and class in pixel order (0 for a pair that is not evaluated);
+ *   rows of other pixels and columns [C, ld_g) are not written.
+ * record: DEVICE float[cvk_lovasz_record_floats()] = float[264]: [0] = loss, [1] = valid pixels, [2] = out-of-range targets, [3] = J,
+ *   [4] = H (0 when ce = 0), [5] = evaluated (segment, class) pairs, [6] = counted segments, [7] = sum of w[t] over the valid pixels
+ *   (H's divisor, 0 when ce = 0); [8 + c] = L_c, the mean over the segments that evaluated class c (NaN: none did); [136 + c] = G_c
+ *   over the batch; c < C, the other slots are not written.
+ * bwd: dlogits [M][ld_d]: dx_j = p_j (s_j - sum_c s_c p_c) + ce g w[t] (p_j - [j = t]) / record[7], s_c = lovasz g sign_c gmap[c] /
+ *   (K counted segments), sign_c = -1 for c = t and +1 otherwise, g = grad_out * scale; grad_out: one DEVICE float, nullable (1).
+ *   Takes the workspace, record and gmap of the forward.  Rows of ignored or out-of-range pixels and columns [C, ld_d) are zeros.
+ * cvk_lovasz_sort_dest / cvk_lovasz_sort_count_index: the two index functions of the sort, the same code the kernels run, for host
+ *   tests: element index of (segment, digit base, work-group base, rank) in a buffer of segments of seg_len elements, and the index
+ *   of (segment, digit, work-group) in the count table; -1 when a piece is out of range (the kernels then store nothing). */
+#define CVK_LOVASZ_PRESENT 0
+#define CVK_LOVASZ_ALL 1
+#define CVK_LOVASZ_DIGIT_BITS 8
+#define CVK_LOVASZ_SORT_TILE 2048
+int64_t cvk_lovasz_workspace_bytes(int M, int C, int segments);
+int     cvk_lovasz_record_floats(void);
+int64_t cvk_lovasz_sort_dest(int64_t seg_len, int64_t segment, int64_t digit_base, int64_t wg_base, int64_t rank);
+int64_t cvk_lovasz_sort_count_index(int64_t work_groups, int64_t segment, int64_t digit, int64_t work_group);
+int cvk_lovasz_softmax_fwd(const float* logits, int ld, const int64_t* target, const float* weight, float lovasz, float ce,
+                           int classes_mode, int per_image, int N, int pixels_per_image, void* workspace, float* record, float* gmap,
+                           int ld_g, int C, int ignore_index, void* stream);
+int cvk_lovasz_softmax_bwd(const float* logits, int ld, const int64_t* target, const float* weight, float lovasz, float ce,
+                           int per_image, int N, int pixels_per_image, const void* workspace, const float* record, const float* gmap,
+                           int ld_g, const float* grad_out, float scale, float* dlogits, int ld_d, int C, int ignore_index,
+                           void* stream);
+
 /* ---- class statistics of label masks (class weights for the loss above; SegNet's median-frequency balancing) ----------
  * masks: DEVICE [N][HW] of mask_bytes = 1 (uint8) or 8 (int64) per label (cvk_augment_u8's convention); 0 < num_classes <= 256.
  * Accumulates into DEVICE int64 hist[2 * num_classes + 1] (the caller zeroes it once): hist[c] += pixels of class c,

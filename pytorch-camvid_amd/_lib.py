@@ -196,6 +196,14 @@ SIGNATURES = {
     "cvk_ohem_record_floats": (c_int, []),
     "cvk_ohem_ce_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "cvk_ohem_ce_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_float, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "cvk_lovasz_workspace_bytes": (ctypes.c_int64, [c_int, c_int, c_int]),
+    "cvk_lovasz_record_floats": (c_int, []),
+    "cvk_lovasz_sort_dest": (ctypes.c_int64, [ctypes.c_int64] * 5),
+    "cvk_lovasz_sort_count_index": (ctypes.c_int64, [ctypes.c_int64] * 4),
+    "cvk_lovasz_softmax_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int,
+                                       c_int, c_int, c_vp]),
+    "cvk_lovasz_softmax_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp,
+                                       c_float, c_vp, c_int, c_int, c_int, c_vp]),
     "cvk_class_histogram": (c_int, [c_vp, c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp]),
     "cvk_argmax_channels": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp]),
     "cvk_confusion_accumulate": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

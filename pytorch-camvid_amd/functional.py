@@ -490,6 +490,200 @@ def ohem_cross_entropy(logits, target, thresh, min_kept, weight=None, ignore_ind
     return _OhemCrossEntropy.apply(logits, target, weight, (lam, min_kept, ignore_index, 1.0))
 
 
+LOVASZ_CLASSES = {"present": 0, "all": 1}          # include/cvk.h CVK_LOVASZ_*
+LOVASZ_RECORD_HEAD = 8                             # loss | V | out of range | J | H | evaluated pairs | counted segments | sum w[t]
+LOVASZ_CLASS_SLOTS = 128                           # L_c at [8 + c], G_c at [8 + 128 + c]
+LOVASZ_SORT_TILE = 2048                            # include/cvk.h CVK_LOVASZ_SORT_TILE: elements a sort work-group covers
+
+
+def _check_lovasz_options(lovasz, ce, classes, per_image, weight):
+    lovasz, ce = _nonneg("lovasz", lovasz), _nonneg("ce", ce)
+    if lovasz == 0.0:
+        raise ValueError("lovasz must be greater than 0 (ce alone is CrossEntropyLoss)")
+    if classes not in LOVASZ_CLASSES:
+        raise ValueError(f"{classes} is not a valid value for classes (one of {sorted(LOVASZ_CLASSES)})")
+    if not isinstance(per_image, bool):
+        raise ValueError(f"per_image must be a bool. Got: {per_image!r}")
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 1:
+            raise ValueError("weight must be a 1-D tensor of one value per class")
+        if ce == 0.0:
+            raise ValueError("weight enters the cross-entropy term only and needs ce > 0 (class weights do not enter the Lovász term)")
+    return lovasz, ce
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    """lovasz * Lovász-softmax + ce * weighted cross-entropy (cvk_lovasz_softmax_fwd / _bwd)."""
+
+    _buffers = {}                                  # (M, C, segments, device) -> the workspace (sort buffers, g map, tables)
+
+    @staticmethod
+    def workspace(lib, M, C, S, device):
+        key = (M, C, S, str(device))
+        ws = _LovaszSoftmax._buffers.get(key)
+        if ws is None:
+            nbytes = lib.cvk_lovasz_workspace_bytes(M, C, S)
+            if nbytes <= 0:
+                raise RuntimeError(f"pytorch_camvid_amd.LovaszSoftmaxLoss serves 1 to 128 classes, segments of fewer than 2^30 pixels and "
+                                   f"at most 65535 (segment, class) pairs, got C = {C}, M = {M}, segments = {S}")
+            ws = _LovaszSoftmax._buffers[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        return ws
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, opts):
+        lovasz, ce, classes, per_image, ignore_index, grad_scale = opts
+        lib = _lib.load()
+        if not logits.is_cuda:
+            raise RuntimeError("pytorch_camvid_amd.LovaszSoftmaxLoss needs HIP tensors (no CPU fallback)")
+        if logits.dim() != 4:
+            raise ValueError("expected logits of shape [N, C, H, W]")
+        if logits.dtype != torch.float32 or target.dtype != torch.int64:
+            raise RuntimeError(f"expected float32 logits and int64 target, got {logits.dtype} / {target.dtype}")
+        N, C, H, W = logits.shape
+        if tuple(target.shape) != (N, H, W):
+            raise ValueError(f"Expected target size {[N, H, W]}, got {list(target.shape)}")
+        if weight is not None:
+            if weight.dim() != 1 or weight.numel() != C:
+                raise RuntimeError(f"weight tensor should be defined either for all {C} classes or no classes but got weight tensor "
+                                   f"of shape: {list(weight.shape)}")
+            if weight.device != logits.device:
+                raise RuntimeError(f"weight is on {weight.device} but the logits are on {logits.device} (no implicit copy: the loss "
+                                   "stays capturable); move the loss module with .to(device)")
+            if weight.dtype != torch.float32:
+                raise RuntimeError(f"expected a float32 weight, got {weight.dtype}")
+            weight = weight.detach().contiguous()
+        lg, ld = _as_nhwc(logits)
+        tg = target.contiguous()
+        M, S = N * H * W, (N if per_image else 1)
+        if not 1 <= C <= 128 or M <= 0:
+            raise RuntimeError(f"pytorch_camvid_amd.LovaszSoftmaxLoss serves 1 to 128 classes and a non-empty batch, got C = {C}, M = {M}")
+        ws = _LovaszSoftmax.workspace(lib, M, C, S, logits.device)
+        gmap = ws[16 * M * C:20 * M * C].view(torch.float32).view(M, C)        # the room include/cvk.h reserves for a dense g map
+        rec = torch.empty(lib.cvk_lovasz_record_floats(), device=logits.device, dtype=torch.float32)
+        wp = weight.data_ptr() if weight is not None else None
+        from . import engine
+        # bytes: the logits, the targets, the elements written once, 4 passes reading them twice and writing them once, the weight
+        # pass reading them twice (8 B each) and scattering g (4 B)
+        engine._timed(None, "k_lovasz_fwd", 4.0 * M * ld + 8.0 * M + 8.0 * M * C * (1 + 3 * 4 + 2) + 4.0 * M * C, lambda: check(
+            lib.cvk_lovasz_softmax_fwd(lg.data_ptr(), ld, tg.data_ptr(), wp, lovasz, ce, LOVASZ_CLASSES[classes], int(per_image), N, H * W,
+                                       ws.data_ptr(), rec.data_ptr(), gmap.data_ptr(), C, C, int(ignore_index), _stream(logits)),
+            "cvk_lovasz_softmax_fwd"), "byte")
+        ctx.save_for_backward(lg, tg, rec, weight)
+        ctx.ws = ws                                # shared by every call of this size: backward must run before the next forward
+        ctx.meta = (N, C, H, W, ld, lovasz, ce, int(per_image), float(grad_scale), int(ignore_index))
+        _CrossEntropy.last_status = rec
+        _LovaszSoftmax.last_sorted = (ws, S, C, M // S)
+        return rec[0].clone()           # not a view: rec is saved for backward (H's divisor) and published as the status
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        lg, tg, rec, weight = ctx.saved_tensors
+        N, C, H, W, ld, lovasz, ce, per_image, grad_scale, ignore_index = ctx.meta
+        M = N * H * W
+        ws = ctx.ws
+        gmap = ws[16 * M * C:20 * M * C]
+        d = torch.empty((N, H, W, C), device=lg.device, dtype=torch.float32)
+        g = gout.contiguous()
+        wp = weight.data_ptr() if weight is not None else None
+        from . import engine
+        engine._timed(None, "k_lovasz_bwd", 4.0 * M * ld + 8.0 * M + 8.0 * M * C, lambda: check(
+            lib.cvk_lovasz_softmax_bwd(lg.data_ptr(), ld, tg.data_ptr(), wp, lovasz, ce, per_image, N, H * W, ws.data_ptr(), rec.data_ptr(),
+                                       gmap.data_ptr(), C, g.data_ptr(), grad_scale, d.data_ptr(), C, C, ignore_index, _stream(lg)),
+            "cvk_lovasz_softmax_bwd"), "byte")
+        return d.permute(0, 3, 1, 2), None, None, None
+
+
+class LovaszSoftmaxLoss(nn.Module):
+    """`lovasz * J + ce * H` as one autograd node: J the Lovász-softmax loss (Berman, Triki and Blaschko, CVPR 2018; mmseg's `LovaszLoss`
+    with `loss_type="multi_class"`), the convex surrogate of the Jaccard index this project reports, and H the weighted mean
+    cross-entropy of CrossEntropyLoss(weight=) it is usually added to.  Per segment (the whole batch, or one image with `per_image=True`)
+    and class c, over the valid pixels (t != `ignore_index`) in memory order i, with p = softmax(logits) in fp32:
+      e_i = p_i[c] where t_i != c and 1 - p_i[c] where t_i = c (as the other classes' share of the sum, so it does not cancel)
+      the pixels are ordered by e descending, ties by ascending i; with G the class's pixel count, n a pixel's position and F the
+      foreground pixels before it, U = G + n - F and I = G - F, its weight is g = 1 / U (foreground) or I / (U (U + 1)) (background),
+      which is the step of the Jaccard loss 1 - I / U along the order (G = 0: g = 1 at n = 0, 0 elsewhere)
+      L_c = sum e_i g_i in fp64
+    A segment's loss is the mean of L_c over the classes that occur in it (`classes="present"`) or over all of them (`"all"`); a segment
+    without a valid pixel is not counted; J is the mean over the counted segments, 0 when there is none (never NaN).  `weight` (float32
+    [C] on the logits' device, a registered buffer) enters H only and needs `ce > 0`; with `ce == 0` H is not computed.
+    The order comes from a stable segmented LSD radix sort on the device (8 bits a pass over a 32-bit key, one 64-bit element per pixel
+    and class): no torch.sort, no allocation after the first call of a size, no host sync, so the loss can be captured by `GraphedStep`
+    (with `optimizer=` and `accumulator=`); every histogram is an integer count and every float sum has one fixed order, so the loss and
+    its gradient are bitwise reproducible, ties included.
+    Conventions of CrossEntropyLoss hold: float32 logits [N, C, H, W] (C <= 128; channels_last is read in place), int64 targets
+    [N, H, W], a 0-dim loss, an out-of-range target makes the loss NaN and `last_ce_status()` reports it, `grad_scale` multiplies the
+    backward only.  The workspace (two sort buffers of 8 bytes per pixel and class, the g map of 4, small tables) is kept per (pixels,
+    classes, segments, device) and shared by every loss of that size: run a forward's backward before the next forward of the same size.
+    After a forward, device views for logging without a sync: `last_record` ([loss, V, out of range, J, H, evaluated (segment, class)
+    pairs, counted segments, sum w[t], then L_c at 8 + c and G_c at 136 + c]), `last_terms` ([J, H]), `last_class_loss` ([C], NaN
+    where no segment evaluated the class) and `sorted_view()`.  Under `ddp.DataParallel` every rank sorts its own part of the batch:
+    the averaged gradient is the mean of the per-rank losses' gradients, not the gradient of a Lovász loss over the global batch, as
+    the Dice sums of SegmentationLoss and the selection of OhemCrossEntropyLoss are per rank.
+    Not provided: the binary Lovász hinge, per-class weights on the Lovász term, segments of 2^30 pixels or more, a sort shared across
+    ranks."""
+
+    def __init__(self, lovasz=1.0, ce=0.0, *, classes="present", per_image=False, weight=None, ignore_index=-100, grad_scale=1.0):
+        super().__init__()
+        self.lovasz, self.ce = _check_lovasz_options(lovasz, ce, classes, per_image, weight)
+        self.classes = classes
+        self.per_image = per_image
+        self.ignore_index = ignore_index
+        self.grad_scale = grad_scale
+        self.register_buffer("weight", weight)
+        self._record = self._sorted = None
+        self._C = 0
+
+    def forward(self, logits, target):
+        loss = _LovaszSoftmax.apply(logits, target, self.weight, (self.lovasz, self.ce, self.classes, self.per_image, self.ignore_index,
+                                                                   self.grad_scale))
+        self._record, self._sorted, self._C = _CrossEntropy.last_status, _LovaszSoftmax.last_sorted, logits.shape[1]
+        return loss
+
+    def _rec(self):
+        if self._record is None:
+            raise RuntimeError("no forward has run yet")
+        return self._record
+
+    @property
+    def last_record(self):
+        """The device record of the most recent forward (float32 [264], no sync)."""
+        return self._rec()
+
+    @property
+    def last_terms(self):
+        """[J, H] of the most recent forward (device tensor, no sync)."""
+        return self._rec()[3:5]
+
+    @property
+    def last_class_loss(self):
+        """L_c of the most recent forward, [C], NaN for a class no segment evaluated (device tensor, no sync)."""
+        return self._rec()[LOVASZ_RECORD_HEAD:LOVASZ_RECORD_HEAD + self._C]
+
+    @property
+    def last_class_pixels(self):
+        """G_c of the most recent forward, [C] (device tensor, no sync)."""
+        o = LOVASZ_RECORD_HEAD + LOVASZ_CLASS_SLOTS
+        return self._rec()[o:o + self._C]
+
+    def sorted_view(self):
+        """The sorted buffer of the most recent forward as (keys uint32, pixel index int64, fg bool), each [S, C, segment length]:
+        keys is a view of the workspace, the other two are unpacked from its payload words.  Position n of segment (s, c) holds the
+        pixel with the n-th largest error of class c; key = 0x3f800000 - bits(e), 0xffffffff for a pixel that is not valid.  The
+        workspace is shared: read it before another loss of the same size runs."""
+        self._rec()
+        ws, S, C, P = self._sorted
+        words = ws[:8 * S * C * P].view(torch.int32).view(S, C, P, 2)          # little endian: payload word, then key word
+        payload = words[..., 0].to(torch.int64) & 0xFFFFFFFF
+        return words[..., 1].view(torch.uint32), payload >> 1, (payload & 1).bool()
+
+
+def lovasz_softmax(logits, target, lovasz=1.0, ce=0.0, *, classes="present", per_image=False, weight=None, ignore_index=-100):
+    """Functional form of LovaszSoftmaxLoss (same kernels)."""
+    lovasz, ce = _check_lovasz_options(lovasz, ce, classes, per_image, weight)
+    return _LovaszSoftmax.apply(logits, target, weight, (lovasz, ce, classes, per_image, ignore_index, 1.0))
+
+
 KD_RECORD = 9                                      # loss | valid | out of range | sum w[t] | H | K | |D| | agree | agree / |D|
 
 
