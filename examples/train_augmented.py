@@ -59,10 +59,11 @@ def main():
     ap.add_argument("--class-weights", default="none", choices=["none", "median_frequency", "enet"],
                     help="class-weighted loss, weights from one pass over the training masks (cvk.class_weights)")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
-    ap.add_argument("--loss", default="ce", choices=["ce", "focal", "dice", "ce+dice", "ohem", "lovasz", "ce+lovasz"],
+    ap.add_argument("--loss", default="ce", choices=["ce", "focal", "dice", "ce+dice", "ohem", "lovasz", "ce+lovasz", "boundary", "ce+boundary"],
                     help="ce: cvk.CrossEntropyLoss (the reference's loss); focal, dice, ce+dice: cvk.SegmentationLoss, one fused pass; "
                          "ohem: cvk.OhemCrossEntropyLoss, online hard example mining; lovasz, ce+lovasz: cvk.LovaszSoftmaxLoss, the "
-                         "Jaccard surrogate alone or added to the (weighted) cross-entropy")
+                         "Jaccard surrogate alone or added to the (weighted) cross-entropy; boundary, ce+boundary: cvk.BoundaryLoss, Kervadec's "
+                         "boundary loss on distance maps computed on the device, alone or added to the (weighted) cross-entropy")
     ap.add_argument("--focal-gamma", type=float, default=2.0, help="--loss focal: the focusing exponent")
     ap.add_argument("--dice-weight", type=float, default=0.5, help="--loss ce+dice: the Dice term's coefficient")
     ap.add_argument("--ohem-thresh", type=float, default=0.7, help="--loss ohem: keep the pixels whose target probability is below this")
@@ -71,6 +72,11 @@ def main():
     ap.add_argument("--lovasz-per-image", action="store_true", help="--loss lovasz, ce+lovasz: one Lovász loss per image, averaged")
     ap.add_argument("--lovasz-classes", default="present", choices=["present", "all"],
                     help="--loss lovasz, ce+lovasz: average over the classes that occur in a segment, or over all of them")
+    ap.add_argument("--boundary-weight", type=float, default=1.0,
+                    help="--loss boundary, ce+boundary: the boundary term's coefficient (with --boundary-ramp: in the first epoch)")
+    ap.add_argument("--boundary-ramp", type=float, default=0.0, metavar="X",
+                    help="--loss boundary, ce+boundary: add X to the coefficient every epoch, up to 1 (Kervadec's schedule); the coefficient "
+                         "lives in a device buffer, so a --graphed step follows it without a re-capture")
     ap.add_argument("--teacher", default=None, choices=["unet", "segnet"],
                     help="knowledge distillation: train --net under this network's logits with cvk.DistillationLoss (cross-entropy on the "
                          "labels + --kd-weight * temperature-softened KL towards the teacher); the teacher runs in eval mode under no_grad")
@@ -171,6 +177,13 @@ def main():
                 raise SystemExit("--class-weights enter the cross-entropy term: use --loss ce+lovasz")
             loss_fn = cvk.LovaszSoftmaxLoss(a.lovasz_weight, 1.0 if a.loss == "ce+lovasz" else 0.0, classes=a.lovasz_classes,
                                             per_image=a.lovasz_per_image, weight=weight)
+        elif a.loss in ("boundary", "ce+boundary"):
+            if a.loss == "boundary" and weight is not None:
+                raise SystemExit("--class-weights enter the cross-entropy term: use --loss ce+boundary")
+            if a.boundary_weight < 0 or a.boundary_ramp < 0 or a.boundary_weight + a.boundary_ramp <= 0:
+                raise SystemExit("--boundary-weight and --boundary-ramp must not be negative, and one of them must be positive")
+            # which terms exist is fixed here; the coefficient itself is set at the start of every epoch
+            loss_fn = cvk.BoundaryLoss(1.0, 1.0 if a.loss == "ce+boundary" else 0.0, weight=weight).to(dev)
         else:
             ce, dice = {"focal": (1.0, 0.0), "dice": (0.0, 1.0), "ce+dice": (1.0, a.dice_weight)}[a.loss]
             loss_fn = cvk.SegmentationLoss(ce, dice, focal_gamma=a.focal_gamma if a.loss == "focal" else 0.0, weight=weight)
@@ -187,6 +200,8 @@ def main():
     step = None
     for epoch in range(1, a.epochs + 1):
         net.train()
+        if isinstance(loss_fn, cvk.BoundaryLoss):                           # a fill of the device buffer on this stream, no sync
+            loss_fn.boundary = min(1.0, a.boundary_weight + a.boundary_ramp * (epoch - 1)) if a.boundary_ramp else a.boundary_weight
         t0 = time.time()
         norms = []                                                          # device scalars: read once per epoch
         pending = []                                                        # --graphed --accumulate: the open window's batches
@@ -228,6 +243,9 @@ def main():
             kd_h, kd_k = kd.last_terms.tolist()
             print(f"  distillation: H {kd_h:.4f}  K {kd_k:.4f}  arg-max agreement with the teacher {kd.last_agreement.item():.4f}  "
                   f"(T {a.kd_temperature:g}, kd weight {a.kd_weight:g})")
+        if isinstance(loss_fn, cvk.BoundaryLoss):                   # device views of the last step's record
+            bl_b, bl_h = loss_fn.last_terms.tolist()
+            print(f"  boundary loss: B {bl_b:.4f}  H {bl_h:.4f}  (coefficient {loss_fn.boundary:g})")
         if step is not None:
             rows, _ = step.log()                                            # with clipping: 7 columns, the norm is column 5
             norms = list(torch.from_numpy(rows[:, 5].copy())) if a.clip_grad_norm is not None else []

@@ -600,6 +600,50 @@ int cvk_lovasz_softmax_bwd(const float* logits, int ld, const int64_t* target, c
                            int ld_g, const float* grad_out, float scale, float* dlogits, int ld_d, int C, int ignore_index,
                            void* stream);
 
+/* ---- exact Euclidean distance transform of a label batch, and the boundary loss on it (Kervadec et al., MIDL 2019); not in the
+ * reference -----------------------------------------------------------------------------------------------------------------------------
+ * labels: DEVICE int64 [N][H][W].  A pixel whose label is ignore_index or outside [0, num_classes) belongs to no class (void); it still
+ * counts as "not class c" for every c.  Everything is per image.  With M = N H W:
+ *   to_class [M][C] int32: the squared Euclidean distance to the nearest pixel of the image whose label is c, exact; -1 where the image
+ *     has no pixel of class c.
+ *   to_other [M] int32: the squared distance to the nearest pixel of the image whose category (class, or void) differs from this
+ *     pixel's; -1 where there is none.
+ *   phi [M][C] float (NHWC): +sqrt(to_class) where the pixel is not of class c, -(sqrt(to_other) - 1) where it is (Kervadec's
+ *     one_hot2dist), 0 wherever the needed distance is -1.  The root is the correctly rounded fp32 root of the exactly converted integer.
+ * Limits: 1 <= num_classes <= 32, H <= 65534, (H - 1)^2 + (W - 1)^2 < 2^24, N H W < 2^31.
+ * workspace: DEVICE, cvk_edt_workspace_bytes(N, H, W, num_classes) bytes (0: unsupported sizes), 16-byte aligned, contents need not be
+ *   initialised: the uint16 column distances [M][C + 1] (channel c: the vertical distance to the nearest pixel of class c in the column;
+ *   channel C: to the nearest pixel of the column with another category; 0xFFFF: none), then per image the class-presence word and the
+ *   void flag.  cvk_edt_squared and cvk_edt_signed run the same two passes and one device function makes the integers of both.
+ * Boundary loss: loss = cb B + cc H.  logits: dense NHWC rows [M][ld] (C <= ld <= 63, 1 <= C <= 32), target int64 [M], phi float [M][C]
+ * (cvk_edt_signed of the target with the same ignore_index), weight float [C] nullable (all ones, enters H only), coef float[2] =
+ * {cb, cc}: all DEVICE; the coefficients are read by the kernels, so a captured graph follows a change of them.
+ *   V = the pixels whose target is a class; S = the classes of class_mask (bit c); p = softmax(x) in fp32
+ *   B = 1 / |V| sum_{q in V} sum_{c in S} phi_c(q) p_c(q), 0 when V is empty;  H = the weighted mean cross-entropy of
+ *   cvk_softmax_ce_fwd_ex (label_smoothing 0; 0/0 = NaN when V is empty).  want_boundary / want_ce (0 or 1, not both 0) say which terms
+ *   exist: a term that is off is not computed and its coefficient is not read (phi may be null without the boundary term; weight needs
+ *   the cross-entropy term).  A target outside [0, C) other than ignore_index makes the loss NaN and is counted.
+ * part: DEVICE scratch, cvk_boundary_loss_part_floats(M, C) floats.
+ * record: DEVICE float[cvk_boundary_loss_record_floats()] = float[40]: [0] = loss, [1] = |V|, [2] = out-of-range targets, [3] = B,
+ *   [4] = H, [5] = cb and [6] = cc as the forward read them (0 for a term that is off), [7] = sum of w[t] over V (0 without H),
+ *   [8 + c] = class c's share of B (they sum to B; 0 for c >= C).
+ * bwd: dlogits [M][ld_d] (ld_d >= C): dx_k = g cb p_k (phi_k [k in S] - sum_{c in S} phi_c p_c) / |V| + g cc w[t] (p_k - [k = t]) /
+ *   record[7], g = grad_out * scale (grad_out: one DEVICE float, nullable = 1); cb, cc, |V| from the forward's record.  Rows of pixels
+ *   outside V and columns [C, ld_d) are zeros.  Every sum has one fixed order and there is no float atomic. */
+int64_t cvk_edt_workspace_bytes(int N, int H, int W, int num_classes);
+int cvk_edt_squared(const int64_t* labels, int N, int H, int W, int num_classes, int ignore_index, void* workspace, int32_t* to_class,
+                    int32_t* to_other, void* stream);
+int cvk_edt_signed(const int64_t* labels, int N, int H, int W, int num_classes, int ignore_index, void* workspace, float* phi,
+                   void* stream);
+int cvk_boundary_loss_part_floats(int M, int C);
+int cvk_boundary_loss_record_floats(void);
+int cvk_boundary_loss_fwd(const float* logits, int ld, const int64_t* target, const float* phi, const float* weight, const float* coef,
+                          int want_boundary, int want_ce, unsigned class_mask, float* part, float* record, int M, int C,
+                          int ignore_index, void* stream);
+int cvk_boundary_loss_bwd(const float* logits, int ld, const int64_t* target, const float* phi, const float* weight, int want_boundary,
+                          int want_ce, unsigned class_mask, const float* record, const float* grad_out, float scale, float* dlogits,
+                          int ld_d, int M, int C, int ignore_index, void* stream);
+
 /* ---- class statistics of label masks (class weights for the loss above; SegNet's median-frequency balancing) ----------
  * masks: DEVICE [N][HW] of mask_bytes = 1 (uint8) or 8 (int64) per label (cvk_augment_u8's convention); 0 < num_classes <= 256.
  * Accumulates into DEVICE int64 hist[2 * num_classes + 1] (the caller zeroes it once): hist[c] += pixels of class c,

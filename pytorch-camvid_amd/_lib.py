@@ -204,6 +204,15 @@ SIGNATURES = {
                                        c_int, c_int, c_vp]),
     "cvk_lovasz_softmax_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_float, c_float, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp,
                                        c_float, c_vp, c_int, c_int, c_int, c_vp]),
+    "cvk_edt_workspace_bytes": (ctypes.c_int64, [c_int, c_int, c_int, c_int]),
+    "cvk_edt_squared": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "cvk_edt_signed": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "cvk_boundary_loss_part_floats": (c_int, [c_int, c_int]),
+    "cvk_boundary_loss_record_floats": (c_int, []),
+    "cvk_boundary_loss_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_uint, c_vp, c_vp, c_int, c_int, c_int,
+                                      c_vp]),
+    "cvk_boundary_loss_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, ctypes.c_uint, c_vp, c_vp, c_float, c_vp, c_int, c_int,
+                                      c_int, c_int, c_vp]),
     "cvk_class_histogram": (c_int, [c_vp, c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp]),
     "cvk_argmax_channels": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_vp]),
     "cvk_confusion_accumulate": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

@@ -1216,6 +1216,363 @@ __global__ __launch_bounds__(256) void k_lv_bwd(const float* __restrict__ logits
     }
 }
 
+// ---- exact Euclidean distance transform of a label batch (cvk_edt_squared / cvk_edt_signed; definitions in include/cvk.h) ------------
+// A pixel's category is its class, or void (-1) when its label is ignore_index or outside [0, C).  Two passes, everything per image:
+//   k_edt_cols  work-group = (image, 16 columns), their categories staged in LDS; thread = (column, channel), one walk down the column
+//               and one up.  Channel c < C: the vertical distance to the nearest pixel of class c in the column; channel C: to the
+//               nearest pixel of the column whose category differs from this pixel's (0xFFFF: none).  uint16 [N][H][W][C + 1].  ORs the
+//               image's class-presence word (and its void flag) with an integer atomic.
+//   k_edt_rows  work-group = one row (n, y): the row's column distances (transposed to [C + 1][W]) and categories sit in LDS; thread =
+//               x, and per channel the outward search of edt_row_search: x - k and x + k for k = 0, 1, ... until k^2 >= best.  Every
+//               x' with |x - x'| < k has been visited and every other one costs at least k^2, so the minimum is exact.  A class absent
+//               from the image is skipped (-1).  For the distance to another category the column term of x' is channel C where x' has
+//               this pixel's category and 0 elsewhere.  The integers of a 256-pixel tile are put in LDS in [x][c] order and stored as
+//               contiguous words: int32 (SIGNED = false) or phi with sign and correctly rounded root applied (SIGNED = true).
+// LDS of k_edt_cols: 16 H B (5.6 KiB at H = 360).  LDS of k_edt_rows: 2 W (C + 2) B of rows + 1 KiB x (C | 1) of output tile (12.6 + 13 KiB at W = 480, C = 12); a row that would not
+// fit 64 KiB keeps only the categories (2 W B) in LDS and searches the column distances in global memory.
+constexpr int EDT_MAX_C = 32;
+constexpr int EDT_MAX_H = 65534;                   // a vertical distance is at most H - 1 < 0xFFFF
+constexpr unsigned EDT_NONE = 0xFFFFu;
+constexpr unsigned EDT_INF = 0xFFFFFFFFu;
+constexpr int EDT_MAX_D2 = 1 << 24;                // (H - 1)^2 + (W - 1)^2 below this: every squared distance converts to fp32 exactly
+constexpr size_t EDT_LDS_LIMIT = 64 * 1024;
+
+__host__ __device__ __forceinline__ int edt_category(long t, int C, int ignore_index) {
+    return t >= 0 && t < C && t != (long)ignore_index ? (int)t : -1;
+}
+
+// The correctly rounded fp32 root of an integer below 2^24 (exact in fp32).  sqrtf is IEEE-rounded in this build (no fast-math flag);
+// __fsqrt_rn is not used: without OCML_BASIC_ROUNDED_OPERATIONS the toolchain defines it as the native approximation.
+__device__ __forceinline__ float edt_root(int d2) { return __builtin_sqrtf((float)d2); }
+
+// mask[2 n] = classes present in image n (bit c), mask[2 n + 1] = 1 when it has a void pixel; cleared before the launch.
+// Work-group = (image, strip of EDT_COL_TX columns): the strip's categories, int8 [H][EDT_COL_TX] (H <= 4096: at most 64 KiB), are staged in
+// LDS by all threads; then a thread owns one (column, channel) of the strip, channel fastest, and walks the column in LDS down and up;
+// the map is stored on the way down and read back (its own stores) and lowered on the way up.
+constexpr int EDT_COL_TX = 16, EDT_COL_BATCH = 8;
+
+__global__ __launch_bounds__(256) void k_edt_cols(const int64_t* __restrict__ lab, unsigned short* __restrict__ col,
+                                                 unsigned* __restrict__ mask, int strips, int H, int W, int C, int ignore_index) {
+    extern __shared__ signed char edt_cat[];
+    const int K = C + 1;
+    const int n = blockIdx.x / strips, x0 = (blockIdx.x - n * strips) * EDT_COL_TX;
+    const int64_t* L = lab + (size_t)n * H * W;
+    for (int i = threadIdx.x; i < H * EDT_COL_TX; i += 256) {
+        const int y = i / EDT_COL_TX, x = x0 + (i - y * EDT_COL_TX);
+        edt_cat[i] = (signed char)(x < W ? edt_category((long)L[(size_t)y * W + x], C, ignore_index) : -1);
+    }
+    __syncthreads();
+    const size_t os = (size_t)W * K;
+    for (int item = threadIdx.x; item < EDT_COL_TX * K; item += 256) {
+        const int xx = item / K, c = item - xx * K;
+        if (x0 + xx >= W) continue;
+        const signed char* s = edt_cat + xx;
+        unsigned short* o = col + ((size_t)n * H * W + x0 + xx) * K + c;
+        // Two walks with no data-dependent inner loop (lanes of a wave hold different classes): down, storing the distance to the nearest
+        // match above; then up in batches of EDT_COL_BATCH rows, whose stored values are fetched together before they are lowered.
+        if (c < C) {
+            int last = -1;
+            for (int y = 0; y < H; ++y) {
+                if (s[y * EDT_COL_TX] == c) last = y;
+                o[y * os] = (unsigned short)(last < 0 ? EDT_NONE : (unsigned)(y - last));
+            }
+            int next = -1;
+            for (int y1 = H; y1 > 0; y1 -= EDT_COL_BATCH) {
+                unsigned v[EDT_COL_BATCH];
+#pragma unroll
+                for (int j = 0; j < EDT_COL_BATCH; ++j) v[j] = y1 - 1 - j >= 0 ? (unsigned)o[(y1 - 1 - j) * os] : 0u;
+#pragma unroll
+                for (int j = 0; j < EDT_COL_BATCH; ++j) {
+                    const int y = y1 - 1 - j;
+                    if (y < 0) break;
+                    if (s[y * EDT_COL_TX] == c) next = y;
+                    if (next >= 0 && (unsigned)(next - y) < v[j]) o[y * os] = (unsigned short)(next - y);
+                }
+            }
+            if (last >= 0) atomicOr(&mask[2 * n], 1u << c);
+        } else {
+            bool any_void = false;
+            int prev = 0, start = 0;                       // the run of equal categories that holds y starts at `start`
+            for (int y = 0; y < H; ++y) {
+                const int k = s[y * EDT_COL_TX];
+                any_void |= k < 0;
+                if (y > 0 && k != prev) start = y;
+                prev = k;
+                o[y * os] = (unsigned short)(start > 0 ? (unsigned)(y - start + 1) : EDT_NONE);
+            }
+            int end = H - 1;                               // ... and ends at `end`
+            for (int y1 = H; y1 > 0; y1 -= EDT_COL_BATCH) {
+                unsigned v[EDT_COL_BATCH];
+#pragma unroll
+                for (int j = 0; j < EDT_COL_BATCH; ++j) v[j] = y1 - 1 - j >= 0 ? (unsigned)o[(y1 - 1 - j) * os] : 0u;
+#pragma unroll
+                for (int j = 0; j < EDT_COL_BATCH; ++j) {
+                    const int y = y1 - 1 - j;
+                    if (y < 0) break;
+                    const int k = s[y * EDT_COL_TX];
+                    if (y < H - 1 && k != prev) end = y;
+                    prev = k;
+                    if (end < H - 1 && (unsigned)(end + 1 - y) < v[j]) o[y * os] = (unsigned short)(end + 1 - y);
+                }
+            }
+            if (any_void) atomicOr(&mask[2 * n + 1], 1u);
+        }
+    }
+}
+
+// min over x' of (x - x')^2 + g(x')^2, g(x') = col[x' * cstride] (0xFFFF: no such pixel in that column); OTHER: g(x') = 0 where
+// cat[x'] != t.  -1 when no column has a finite term.  The one producer of the integers that both outputs are made of.
+template <bool OTHER>
+__device__ __forceinline__ int edt_row_search(const unsigned short* col, int cstride, const short* cat, int t, int x, int W) {
+    unsigned best = EDT_INF;
+    const int kmax = max(x, W - 1 - x);
+    for (int k = 0; k <= kmax; ++k) {
+        const unsigned k2 = (unsigned)k * (unsigned)k;
+        if (k2 >= best) break;
+        const int xl = x - k, xr = x + k;
+        if (xl >= 0) {
+            unsigned v = col[(size_t)xl * cstride];
+            if (OTHER && cat[xl] != t) v = 0u;
+            if (v != EDT_NONE) best = min(best, k2 + v * v);
+        }
+        if (k > 0 && xr < W) {
+            unsigned v = col[(size_t)xr * cstride];
+            if (OTHER && cat[xr] != t) v = 0u;
+            if (v != EDT_NONE) best = min(best, k2 + v * v);
+        }
+    }
+    return best == EDT_INF ? -1 : (int)best;
+}
+
+// grid N * H.  SIGNED: phi [M][C] floats; else to_class [M][C] and to_other [M] int32.
+template <bool STAGED, bool SIGNED>
+__global__ __launch_bounds__(256) void k_edt_rows(const int64_t* __restrict__ lab, const unsigned short* __restrict__ col,
+                                                 const unsigned* __restrict__ mask, int* __restrict__ to_class,
+                                                 int* __restrict__ to_other, float* __restrict__ phi, int H, int W, int C,
+                                                 int ignore_index) {
+    extern __shared__ unsigned char edt_lds[];
+    const int K = C + 1, pitch = C | 1;
+    const size_t row = blockIdx.x;
+    const int n = (int)(row / H);
+    short* s_cat = reinterpret_cast<short*>(edt_lds);
+    unsigned short* s_col = reinterpret_cast<unsigned short*>(edt_lds) + W;                // [K][W], STAGED only
+    const size_t rows_bytes = ((size_t)2 * W * (STAGED ? K + 1 : 1) + 3) & ~(size_t)3;
+    int* s_out = reinterpret_cast<int*>(edt_lds + rows_bytes);                             // [256][pitch]
+    const unsigned short* g = col + row * W * K;
+    for (int x = threadIdx.x; x < W; x += 256) s_cat[x] = (short)edt_category((long)lab[row * W + x], C, ignore_index);
+    if (STAGED)
+        for (int i = threadIdx.x; i < W * K; i += 256) {
+            const int x = i / K, c = i - x * K;
+            s_col[c * W + x] = g[i];
+        }
+    const unsigned present = mask[2 * n];
+    const bool several = __popc(present) + (int)(mask[2 * n + 1] & 1u) > 1;
+    __syncthreads();
+    for (int x0 = 0; x0 < W; x0 += 256) {
+        const int x = x0 + threadIdx.x;
+        int other = -1;
+        if (x < W) {
+            const int t = s_cat[x];
+            if (several)
+                other = STAGED ? edt_row_search<true>(s_col + C * W, 1, s_cat, t, x, W) : edt_row_search<true>(g + C, K, s_cat, t, x, W);
+            for (int c = 0; c < C; ++c) {
+                int d = -1;
+                if (((present >> c) & 1u) && !(SIGNED && c == t))
+                    d = STAGED ? edt_row_search<false>(s_col + c * W, 1, s_cat, t, x, W) : edt_row_search<false>(g + c, K, s_cat, t, x, W);
+                if (SIGNED) {
+                    float v;
+                    if (c == t) v = other < 0 ? 0.f : -(edt_root(other) - 1.f);
+                    else        v = d < 0 ? 0.f : edt_root(d);
+                    s_out[threadIdx.x * pitch + c] = __builtin_bit_cast(int, v);
+                } else {
+                    s_out[threadIdx.x * pitch + c] = d;
+                }
+            }
+            if (!SIGNED) to_other[row * W + x] = other;
+        }
+        __syncthreads();
+        const int words = min(256, W - x0) * C;
+        int* dst = (SIGNED ? reinterpret_cast<int*>(phi) : to_class) + (row * W + x0) * C;
+        for (int j = threadIdx.x; j < words; j += 256) {
+            const int px = j / C;
+            dst[j] = s_out[px * pitch + (j - px * C)];
+        }
+        __syncthreads();
+    }
+}
+
+// ---- boundary loss (Kervadec et al., MIDL 2019; cvk_boundary_loss_fwd / _bwd) -----------------------------------------------------------
+// loss = cb B + cc H, B = 1 / |V| sum_{q in V} sum_{c in S} phi_c(q) p_c(q), p = softmax(x), H = the weighted mean cross-entropy of
+// k_ce_fwd_ex (label_smoothing 0), V = the pixels whose target is a class.  S is a bit mask.  phi is [M][C] dense.
+//   k_bdl_fwd     the staging of k_ce_fwd_ex, thread = pixel: the pixel's row in LDS is overwritten with phi_c p_c (zeros outside V and
+//                 S); then thread (c, r) = (tid % 32, tid / 32) sums column c over rows [32 r, 32 r + 32) of the tile in row order.
+//                 part[k][nb]: valid pixels | out-of-range targets | cross-entropy sum | sum w[t] | class c's sum at 4 + c
+//   k_bdl_finish  one work-group: every part row in fp64 (thread order, then one fixed tree); B = the sum of the class terms; reads the
+//                 two coefficients from device memory and leaves them in the record for the backward
+//   k_bdl_bwd     one pass, dlogits written once
+// LDS: the (ld + 1) KiB tile + 1.2 KiB.  No float atomic: loss and gradient are bitwise reproducible.
+constexpr int BDL_PART_HEAD = 4, BDL_REC_HEAD = 8, BDL_RECORD_FLOATS = BDL_REC_HEAD + EDT_MAX_C;
+
+__global__ __launch_bounds__(256) void k_bdl_fwd(const float* __restrict__ logits, int ld, const int64_t* __restrict__ target,
+                                                const float* __restrict__ phi, const float* __restrict__ weight, int want_ce,
+                                                unsigned cmask, float* __restrict__ part, int nb, int M, int C, int ignore_index) {
+    extern __shared__ float lds[];
+    __shared__ float red[4];
+    __shared__ float s_w[EDT_MAX_C];
+    __shared__ float s_cs[8][EDT_MAX_C];
+    ce_ex_stage_w(weight, s_w, C);                                   // visible after the first chunk's barriers
+    const int pitch = ld + 1;
+    const int cc = threadIdx.x & 31, cr = threadIdx.x >> 5;
+    float acc = 0.f, div = 0.f, cnt = 0.f, bad = 0.f, csum = 0.f;
+    const int base = blockIdx.x * CE_ROWS_PER_BLOCK;
+    for (int ch = 0; ch < CE_ROWS_PER_BLOCK / CE_CHUNK; ++ch) {
+        const int m0 = base + ch * CE_CHUNK;
+        if (m0 >= M) break;
+        const int rows = min(CE_CHUNK, M - m0);
+        __syncthreads();
+        ce_chunk_load(logits + (size_t)m0 * ld, lds, rows * ld, ld);
+        __syncthreads();
+        if ((int)threadIdx.x < rows) {
+            float* x = lds + threadIdx.x * pitch;
+            const size_t m = (size_t)m0 + threadIdx.x;
+            const long t = (long)target[m];
+            if (t != (long)ignore_index && t >= 0 && t < C) {
+                cnt += 1.f;
+                if (want_ce) {
+                    acc += ce_ex_pixel_loss(x, C, (int)t, s_w, 0.f);
+                    div += s_w[t];
+                }
+                float mx = x[0];
+                for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
+                float se = 0.f;
+                for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
+                const float inv = 1.f / se;
+                for (int c = 0; c < C; ++c) x[c] = ((cmask >> c) & 1u) ? phi[m * C + c] * (expf(x[c] - mx) * inv) : 0.f;
+            } else {
+                if (t != (long)ignore_index) bad += 1.f;
+                for (int c = 0; c < C; ++c) x[c] = 0.f;
+            }
+        }
+        __syncthreads();
+        if (cc < C) {
+            const int r1 = min(rows, cr * 32 + 32);
+            float s = 0.f;
+            for (int r = cr * 32; r < r1; ++r) s += lds[r * pitch + cc];
+            csum += s;
+        }
+    }
+    const float n = block_sum_256(cnt, red);
+    const float b = block_sum_256(bad, red);
+    const float s = block_sum_256(acc, red);
+    const float d = block_sum_256(div, red);
+    s_cs[cr][cc] = csum;
+    __syncthreads();
+    if ((int)threadIdx.x < C) {
+        float v = 0.f;
+        for (int r = 0; r < 8; ++r) v += s_cs[r][threadIdx.x];
+        part[(size_t)(BDL_PART_HEAD + threadIdx.x) * nb + blockIdx.x] = v;
+    }
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = n;
+        part[nb + blockIdx.x] = b;
+        part[2 * nb + blockIdx.x] = s;
+        part[3 * nb + blockIdx.x] = d;
+    }
+}
+
+// record: loss | |V| | out-of-range targets | B | H | cb | cc | sum w[t] | class c's share of B at 8 + c
+__global__ __launch_bounds__(256) void k_bdl_finish(const float* __restrict__ part, int nb, const float* __restrict__ coef,
+                                                   int want_b, int want_ce, int C, float* __restrict__ record) {
+    __shared__ double s_tot[BDL_PART_HEAD + EDT_MAX_C];
+    const int lane = threadIdx.x & 63;
+    for (int k = threadIdx.x >> 6; k < BDL_PART_HEAD + C; k += 4) {            // a wave owns every fourth row: lane order, then one fixed tree
+        double v = 0.0;
+        for (int i = lane; i < nb; i += 64) v += (double)part[(size_t)k * nb + i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) s_tot[k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double V = s_tot[0];
+        double bsum = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const double term = V > 0.0 ? s_tot[BDL_PART_HEAD + c] / V : 0.0;
+            record[BDL_REC_HEAD + c] = (float)term;
+            bsum += term;
+        }
+        for (int c = C; c < EDT_MAX_C; ++c) record[BDL_REC_HEAD + c] = 0.f;
+        const double H = want_ce ? s_tot[2] / s_tot[3] : 0.0;                  // 0/0 = NaN when no pixel is valid, as cvk_softmax_ce_fwd_ex
+        const float cb = want_b ? coef[0] : 0.f, cc = want_ce ? coef[1] : 0.f;
+        double loss = 0.0;
+        if (want_b) loss += (double)cb * bsum;
+        if (want_ce) loss += (double)cc * H;
+        record[0] = s_tot[1] > 0.0 ? __builtin_nanf("") : (float)loss;
+        record[1] = (float)V;
+        record[2] = (float)s_tot[1];
+        record[3] = (float)bsum;
+        record[4] = (float)H;
+        record[5] = cb;
+        record[6] = cc;
+        record[7] = want_ce ? (float)s_tot[3] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bdl_bwd(const float* __restrict__ logits, int ld, const int64_t* __restrict__ target,
+                                                const float* __restrict__ phi, const float* __restrict__ weight, int want_ce,
+                                                unsigned cmask, const float* __restrict__ record, const float* __restrict__ grad_out,
+                                                float scale, float* __restrict__ dl, int ld_d, int M, int C, int ignore_index) {
+    extern __shared__ float lds[];
+    __shared__ float s_w[EDT_MAX_C];
+    ce_ex_stage_w(weight, s_w, C);
+    const float go = (grad_out != nullptr ? *grad_out : 1.f) * scale;
+    const float kb = record[1] > 0.f ? record[5] * go / record[1] : 0.f;
+    const float gce0 = want_ce ? record[6] * go / record[7] : 0.f;
+    const int pitch = ld + 1;
+    const int base = blockIdx.x * CE_ROWS_PER_BLOCK;
+    for (int ch = 0; ch < CE_ROWS_PER_BLOCK / CE_CHUNK; ++ch) {
+        const int m0 = base + ch * CE_CHUNK;
+        if (m0 >= M) break;
+        const int rows = min(CE_CHUNK, M - m0);
+        __syncthreads();
+        ce_chunk_load(logits + (size_t)m0 * ld, lds, rows * ld, ld);
+        __syncthreads();
+        if ((int)threadIdx.x < rows) {
+            float* x = lds + threadIdx.x * pitch;
+            const size_t m = (size_t)m0 + threadIdx.x;
+            const long t = (long)target[m];
+            if (t == (long)ignore_index || t < 0 || t >= C) {
+                for (int c = 0; c < ld; ++c) x[c] = 0.f;
+            } else {
+                float mx = x[0];
+                for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
+                float se = 0.f;
+                for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
+                const float inv = 1.f / se;
+                float dot = 0.f;
+                for (int c = 0; c < C; ++c)
+                    if ((cmask >> c) & 1u) dot += phi[m * C + c] * (expf(x[c] - mx) * inv);
+                const float gce = want_ce ? gce0 * s_w[t] : 0.f;
+                for (int c = 0; c < C; ++c) {
+                    const float p = expf(x[c] - mx) * inv;
+                    const float f = ((cmask >> c) & 1u) ? phi[m * C + c] : 0.f;
+                    x[c] = p * (kb * (f - dot)) + gce * (p - (c == (int)t ? 1.f : 0.f));
+                }
+                for (int c = C; c < ld; ++c) x[c] = 0.f;
+            }
+        }
+        __syncthreads();
+        if (ld_d == ld) {
+            ce_chunk_store(dl + (size_t)m0 * ld_d, lds, rows * ld, ld);
+        } else {
+            for (int f = threadIdx.x; f < rows * ld_d; f += CE_CHUNK) {
+                const int r = f / ld_d, c = f - r * ld_d;
+                dl[(size_t)m0 * ld_d + f] = c < ld ? lds[r * pitch + c] : 0.f;
+            }
+        }
+    }
+}
+
 // ---- fused focal + soft-Dice loss (cvk_seg_loss_fwd / _bwd) ---------------------------------------------------------------------
 // L = ce F + dice D over the valid pixels of the batch, p = softmax(x), t = target, q = 1 - p[t]:
 //   F = sum w[t] q^gamma (lse - x[t]) / sum w[t]
@@ -3058,6 +3415,112 @@ extern "C" int cvk_lovasz_softmax_bwd(const float* logits, int ld, const int64_t
         hipLaunchKernelGGL(k_lv_bwd<false>, dim3(cvk_ce_blocks(M)), dim3(256), 0, s, logits, ld, target, weight, lovasz, ce, record, invk,
                            gmap, ld_g, grad_out, scale, dlogits, ld_d, M, p.P, C, ignore_index);
     CVK_LAUNCH_RETURN("cvk_lovasz_softmax_bwd");
+}
+
+static size_t edt_cols_bytes(int N, int H, int W, int C) { return ((size_t)2 * N * H * W * (C + 1) + 15) & ~(size_t)15; }
+
+static int edt_check_sizes(const char* who, int N, int H, int W, int C) {
+    CVK_CHECK_ARG(N > 0 && H > 0 && W > 0, "%s: sizes must be positive, got N %d, H %d, W %d", who, N, H, W);
+    CVK_CHECK_ARG(C >= 1 && C <= EDT_MAX_C, "%s: %d classes, the kernels serve 1 to %d", who, C, EDT_MAX_C);
+    CVK_CHECK_ARG(H <= EDT_MAX_H, "%s: H %d, a column distance is 16 bits wide (H <= %d)", who, H, EDT_MAX_H);
+    CVK_CHECK_ARG((int64_t)(H - 1) * (H - 1) + (int64_t)(W - 1) * (W - 1) < EDT_MAX_D2,
+                  "%s: image too large, (H - 1)^2 + (W - 1)^2 must stay below 2^24 for exact fp32 roots, got H %d, W %d", who, H, W);
+    CVK_CHECK_ARG((int64_t)N * H * W < 2147483648LL, "%s: 2^31 pixels or more", who);
+    return CVK_OK;
+}
+
+extern "C" int64_t cvk_edt_workspace_bytes(int N, int H, int W, int C) {
+    if (N <= 0 || H <= 0 || W <= 0 || C < 1 || C > EDT_MAX_C || H > EDT_MAX_H || (int64_t)N * H * W >= 2147483648LL ||
+        (int64_t)(H - 1) * (H - 1) + (int64_t)(W - 1) * (W - 1) >= EDT_MAX_D2)
+        return 0;
+    return (int64_t)(edt_cols_bytes(N, H, W, C) + 16 * (((size_t)8 * N + 15) / 16));
+}
+
+template <bool SIGNED>
+static void edt_launch(const int64_t* labels, int N, int H, int W, int C, int ignore_index, void* workspace, int* to_class, int* to_other,
+                       float* phi, hipStream_t s) {
+    unsigned short* col = static_cast<unsigned short*>(workspace);
+    unsigned* mask = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + edt_cols_bytes(N, H, W, C));
+    const int K = C + 1;
+    hipLaunchKernelGGL(k_lv_clear, dim3(cvk_cdiv(2 * (long)N, 256)), dim3(256), 0, s, mask, 2 * N);
+    const int strips = cvk_cdiv(W, EDT_COL_TX);
+    hipLaunchKernelGGL(k_edt_cols, dim3((unsigned)N * strips), dim3(256), (size_t)H * EDT_COL_TX, s, labels, col, mask, strips, H, W, C,
+                       ignore_index);
+    const size_t tile = (size_t)4 * 256 * (C | 1);
+    const size_t staged = (((size_t)2 * W * (K + 1) + 3) & ~(size_t)3) + tile, unstaged = (((size_t)2 * W + 3) & ~(size_t)3) + tile;
+    if (staged <= EDT_LDS_LIMIT)
+        hipLaunchKernelGGL((k_edt_rows<true, SIGNED>), dim3((unsigned)N * H), dim3(256), staged, s, labels, col, mask, to_class, to_other,
+                           phi, H, W, C, ignore_index);
+    else
+        hipLaunchKernelGGL((k_edt_rows<false, SIGNED>), dim3((unsigned)N * H), dim3(256), unstaged, s, labels, col, mask, to_class,
+                           to_other, phi, H, W, C, ignore_index);
+}
+
+extern "C" int cvk_edt_squared(const int64_t* labels, int N, int H, int W, int num_classes, int ignore_index, void* workspace,
+                               int32_t* to_class, int32_t* to_other, void* stream) {
+    CVK_CHECK_ARG(labels && workspace && to_class && to_other, "cvk_edt_squared: null pointer");
+    const int rc = edt_check_sizes("cvk_edt_squared", N, H, W, num_classes);
+    if (rc != CVK_OK) return rc;
+    CVK_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "cvk_edt_squared: the workspace must be 16-byte aligned");
+    edt_launch<false>(labels, N, H, W, num_classes, ignore_index, workspace, to_class, to_other, nullptr, (hipStream_t)stream);
+    CVK_LAUNCH_RETURN("cvk_edt_squared");
+}
+
+extern "C" int cvk_edt_signed(const int64_t* labels, int N, int H, int W, int num_classes, int ignore_index, void* workspace, float* phi,
+                              void* stream) {
+    CVK_CHECK_ARG(labels && workspace && phi, "cvk_edt_signed: null pointer");
+    const int rc = edt_check_sizes("cvk_edt_signed", N, H, W, num_classes);
+    if (rc != CVK_OK) return rc;
+    CVK_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "cvk_edt_signed: the workspace must be 16-byte aligned");
+    edt_launch<true>(labels, N, H, W, num_classes, ignore_index, workspace, nullptr, nullptr, phi, (hipStream_t)stream);
+    CVK_LAUNCH_RETURN("cvk_edt_signed");
+}
+
+extern "C" int cvk_boundary_loss_part_floats(int M, int C) {
+    return M > 0 && C >= 1 && C <= EDT_MAX_C ? (BDL_PART_HEAD + C) * cvk_ce_blocks(M) : 0;
+}
+
+extern "C" int cvk_boundary_loss_record_floats(void) { return BDL_RECORD_FLOATS; }
+
+static int bdl_check(const char* who, const float* phi, const float* weight, int want_boundary, int want_ce, unsigned class_mask, int ld,
+                     int M, int C) {
+    CVK_CHECK_ARG(M > 0, "%s: sizes must be positive, got M %d", who, M);
+    CVK_CHECK_ARG(C >= 1 && C <= EDT_MAX_C, "%s: %d classes, the kernels serve 1 to %d", who, C, EDT_MAX_C);
+    CVK_CHECK_ARG(ld >= C && ld <= CE_MAX_LD, "%s: the pixel stride must be in [C, %d], got %d", who, CE_MAX_LD, ld);
+    CVK_CHECK_ARG((want_boundary == 0 || want_boundary == 1) && (want_ce == 0 || want_ce == 1) && (want_boundary || want_ce),
+                  "%s: want_boundary and want_ce must be 0 or 1 and not both 0", who);
+    CVK_CHECK_ARG(!want_boundary || phi != nullptr, "%s: null pointer (the boundary term needs the distance maps)", who);
+    CVK_CHECK_ARG(!want_boundary || (class_mask != 0u && (C == 32 || (class_mask >> C) == 0u)),
+                  "%s: the class mask must name at least one class and none outside [0, C)", who);
+    CVK_CHECK_ARG(weight == nullptr || want_ce, "%s: class weights enter the cross-entropy term only, and it is off", who);
+    return CVK_OK;
+}
+
+extern "C" int cvk_boundary_loss_fwd(const float* logits, int ld, const int64_t* target, const float* phi, const float* weight,
+                                     const float* coef, int want_boundary, int want_ce, unsigned class_mask, float* part, float* record,
+                                     int M, int C, int ignore_index, void* stream) {
+    CVK_CHECK_ARG(logits && target && coef && part && record, "cvk_boundary_loss_fwd: null pointer");
+    const int rc = bdl_check("cvk_boundary_loss_fwd", phi, weight, want_boundary, want_ce, class_mask, ld, M, C);
+    if (rc != CVK_OK) return rc;
+    const int nb = cvk_ce_blocks(M);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_bdl_fwd, dim3(nb), dim3(256), CE_CHUNK * (ld + 1) * sizeof(float), s, logits, ld, target, phi, weight, want_ce,
+                       want_boundary ? class_mask : 0u, part, nb, M, C, ignore_index);
+    hipLaunchKernelGGL(k_bdl_finish, dim3(1), dim3(256), 0, s, part, nb, coef, want_boundary, want_ce, C, record);
+    CVK_LAUNCH_RETURN("cvk_boundary_loss_fwd");
+}
+
+extern "C" int cvk_boundary_loss_bwd(const float* logits, int ld, const int64_t* target, const float* phi, const float* weight,
+                                     int want_boundary, int want_ce, unsigned class_mask, const float* record, const float* grad_out,
+                                     float scale, float* dlogits, int ld_d, int M, int C, int ignore_index, void* stream) {
+    CVK_CHECK_ARG(logits && target && record && dlogits, "cvk_boundary_loss_bwd: null pointer");
+    const int rc = bdl_check("cvk_boundary_loss_bwd", phi, weight, want_boundary, want_ce, class_mask, ld, M, C);
+    if (rc != CVK_OK) return rc;
+    CVK_CHECK_ARG(ld_d >= C, "cvk_boundary_loss_bwd: the gradient's pixel stride must be at least C, got %d", ld_d);
+    hipLaunchKernelGGL(k_bdl_bwd, dim3(cvk_ce_blocks(M)), dim3(256), CE_CHUNK * (ld + 1) * sizeof(float), (hipStream_t)stream, logits, ld,
+                       target, phi, weight, want_ce, want_boundary ? class_mask : 0u, record, grad_out, scale, dlogits, ld_d, M, C,
+                       ignore_index);
+    CVK_LAUNCH_RETURN("cvk_boundary_loss_bwd");
 }
 
 extern "C" int cvk_seg_loss_part_floats(int M, int C) {

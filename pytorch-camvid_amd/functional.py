@@ -684,6 +684,275 @@ def lovasz_softmax(logits, target, lovasz=1.0, ce=0.0, *, classes="present", per
     return _LovaszSoftmax.apply(logits, target, weight, (lovasz, ce, classes, per_image, ignore_index, 1.0))
 
 
+BDL_RECORD_HEAD = 8                                # loss | |V| | out of range | B | H | boundary coef | ce coef | sum w[t], then B's class shares
+EDT_MAX_CLASSES = 32
+
+
+class _DistanceMaps:
+    """The device buffers of the distance transform, kept per (N, H, W, classes, device): the uint16 column maps (+ presence words) that
+    both entry points use as workspace, and the float32 phi maps the boundary loss reads."""
+
+    _buffers = {}
+
+    @staticmethod
+    def get(lib, N, H, W, C, device, want_phi):
+        key = (N, H, W, C, str(device))
+        ent = _DistanceMaps._buffers.get(key)
+        if ent is None:
+            nbytes = lib.cvk_edt_workspace_bytes(N, H, W, C)
+            if nbytes <= 0:
+                raise ValueError(f"the distance transform serves 1 to {EDT_MAX_CLASSES} classes, H <= 65534, (H - 1)^2 + (W - 1)^2 < 2^24 "
+                                 f"and fewer than 2^31 pixels, got N = {N}, H = {H}, W = {W}, classes = {C}")
+            ent = _DistanceMaps._buffers[key] = [torch.empty(nbytes, device=device, dtype=torch.uint8), None]
+        if want_phi and ent[1] is None:
+            ent[1] = torch.empty((N, H, W, C), device=device, dtype=torch.float32)
+        return ent
+
+    @staticmethod
+    def signed(lib, labels, C, ignore_index):
+        """phi of `labels` (contiguous int64 [N,H,W] on the GPU) in the shared [N,H,W,C] buffer of its shape."""
+        N, H, W = labels.shape
+        ws, phi = _DistanceMaps.get(lib, N, H, W, C, labels.device, True)
+        M = N * H * W
+        from . import engine
+        # bytes: the labels read by both passes, the column maps written and read, phi written
+        engine._timed(None, "k_edt_signed", 16.0 * M + 4.0 * M * (C + 1) + 4.0 * M * C, lambda: check(
+            lib.cvk_edt_signed(labels.data_ptr(), N, H, W, C, int(ignore_index), ws.data_ptr(), phi.data_ptr(), _stream(labels)),
+            "cvk_edt_signed"), "byte")
+        return phi
+
+
+def _check_label_maps(who, labels, num_classes):
+    if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int64 and labels.dim() == 3 and labels.numel() > 0):
+        raise ValueError(f"{who}: expected an int64 tensor of shape [N, H, W]")
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= EDT_MAX_CLASSES:
+        raise ValueError(f"{who} serves 1 to {EDT_MAX_CLASSES} classes. Got: {num_classes}")
+    if not labels.is_cuda:
+        raise ValueError(f"{who}: expected a tensor on the GPU (no CPU fallback)")
+
+
+def squared_distance_maps(labels, num_classes=12, ignore_index=11):
+    """The exact squared Euclidean distance transform of an int64 label batch [N,H,W] on the GPU, per image:
+    `to_class` int32 [N,H,W,C], the squared distance to the nearest pixel whose label is c (-1 where the image has none), and `to_other`
+    int32 [N,H,W], the squared distance to the nearest pixel whose label differs from this pixel's (-1 where there is none).  A label
+    that is `ignore_index` or outside [0, num_classes) is void: such a pixel belongs to no class but is a pixel, so it is "not class c"
+    for every c and differs from every class pixel.  Two launches (columns, then rows), no host sync; the result tensors are new."""
+    _check_label_maps("squared_distance_maps", labels, num_classes)
+    lib = _lib.load()
+    m = labels.contiguous()
+    N, H, W = m.shape
+    ws, _ = _DistanceMaps.get(lib, N, H, W, num_classes, m.device, False)
+    to_class = torch.empty((N, H, W, num_classes), device=m.device, dtype=torch.int32)
+    to_other = torch.empty((N, H, W), device=m.device, dtype=torch.int32)
+    check(lib.cvk_edt_squared(m.data_ptr(), N, H, W, num_classes, int(ignore_index), ws.data_ptr(), to_class.data_ptr(),
+                              to_other.data_ptr(), _stream(m)), "cvk_edt_squared")
+    return to_class, to_other
+
+
+def signed_distance_maps(labels, num_classes=12, ignore_index=11):
+    """Kervadec's signed distance maps phi of an int64 label batch [N,H,W] on the GPU, float32 [N,C,H,W] (a channels_last view of a new
+    tensor): +sqrt(to_class) where the pixel is not of class c, -(sqrt(to_other) - 1) where it is, 0 where the needed distance does not
+    exist (the class is absent from the image, or the image is all one class).  The integers are those of `squared_distance_maps`; the
+    root is the correctly rounded fp32 root."""
+    _check_label_maps("signed_distance_maps", labels, num_classes)
+    lib = _lib.load()
+    m = labels.contiguous()
+    return _DistanceMaps.signed(lib, m, num_classes, ignore_index).clone().permute(0, 3, 1, 2)
+
+
+def _check_boundary_loss_options(boundary, ce, classes, weight):
+    boundary, ce = _nonneg("boundary", boundary), _nonneg("ce", ce)
+    if boundary == 0.0 and ce == 0.0:
+        raise ValueError("boundary and ce are both 0: the loss has no term")
+    if classes is not None:
+        classes = tuple(classes)
+        if not classes or any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c < EDT_MAX_CLASSES for c in classes):
+            raise ValueError(f"classes must be None or a non-empty sequence of class indices in [0, {EDT_MAX_CLASSES}). Got: {classes!r}")
+        if len(set(classes)) != len(classes):
+            raise ValueError(f"classes must be distinct. Got: {classes!r}")
+        if boundary == 0.0:
+            raise ValueError("classes selects the classes of the boundary term, and boundary is 0")
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 1:
+            raise ValueError("weight must be a 1-D tensor of one value per class")
+        if ce == 0.0:
+            raise ValueError("weight enters the cross-entropy term only and needs ce > 0 (class weights do not enter the boundary term)")
+    return boundary, ce, classes
+
+
+class _BoundaryLoss(torch.autograd.Function):
+    """coef[0] * boundary loss + coef[1] * weighted cross-entropy (cvk_edt_signed, cvk_boundary_loss_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, coef, opts):
+        want_b, want_ce, classes, ignore_index, grad_scale = opts
+        lib = _lib.load()
+        if not logits.is_cuda:
+            raise RuntimeError("pytorch_camvid_amd.BoundaryLoss needs HIP tensors (no CPU fallback)")
+        if logits.dim() != 4:
+            raise ValueError("expected logits of shape [N, C, H, W]")
+        if logits.dtype != torch.float32 or target.dtype != torch.int64:
+            raise RuntimeError(f"expected float32 logits and int64 target, got {logits.dtype} / {target.dtype}")
+        N, C, H, W = logits.shape
+        if tuple(target.shape) != (N, H, W):
+            raise ValueError(f"Expected target size {[N, H, W]}, got {list(target.shape)}")
+        if not 1 <= C <= EDT_MAX_CLASSES or N * H * W <= 0:
+            raise RuntimeError(f"pytorch_camvid_amd.BoundaryLoss serves 1 to {EDT_MAX_CLASSES} classes and a non-empty batch, got C = {C}, "
+                               f"M = {N * H * W}")
+        if classes is not None and max(classes) >= C:
+            raise ValueError(f"classes names class {max(classes)} but the logits have {C} channels")
+        if weight is not None:
+            if weight.dim() != 1 or weight.numel() != C:
+                raise RuntimeError(f"weight tensor should be defined either for all {C} classes or no classes but got weight tensor "
+                                   f"of shape: {list(weight.shape)}")
+            if weight.device != logits.device:
+                raise RuntimeError(f"weight is on {weight.device} but the logits are on {logits.device} (no implicit copy: the loss "
+                                   "stays capturable); move the loss module with .to(device)")
+            if weight.dtype != torch.float32:
+                raise RuntimeError(f"expected a float32 weight, got {weight.dtype}")
+            weight = weight.detach().contiguous()
+        if coef.device != logits.device or coef.dtype != torch.float32 or coef.numel() != 2:
+            raise RuntimeError(f"the coefficient buffer must be 2 float32 values on {logits.device}")
+        lg, ld = _as_nhwc(logits)
+        if ld > 63:                                # the kernels stage a pixel row of at most 63 floats
+            lg, ld = lg.contiguous(), C
+        tg = target.contiguous()
+        M = N * H * W
+        cmask = sum(1 << c for c in (range(C) if classes is None else classes)) if want_b else 0
+        phi = _DistanceMaps.signed(lib, tg, C, ignore_index) if want_b else None
+        part = torch.empty(lib.cvk_boundary_loss_part_floats(M, C), device=logits.device, dtype=torch.float32)
+        rec = torch.empty(lib.cvk_boundary_loss_record_floats(), device=logits.device, dtype=torch.float32)
+        wp = weight.data_ptr() if weight is not None else None
+        pp = phi.data_ptr() if phi is not None else None
+        from . import engine
+        engine._timed(None, "k_bdl_fwd", 4.0 * M * ld + 8.0 * M + (4.0 * M * C if want_b else 0.0), lambda: check(
+            lib.cvk_boundary_loss_fwd(lg.data_ptr(), ld, tg.data_ptr(), pp, wp, coef.data_ptr(), want_b, want_ce, cmask, part.data_ptr(),
+                                      rec.data_ptr(), M, C, int(ignore_index), _stream(logits)), "cvk_boundary_loss_fwd"), "byte")
+        ctx.save_for_backward(lg, tg, rec, weight)
+        ctx.phi = phi                              # shared by every call of this shape: backward must run before the next forward
+        ctx.meta = (N, C, H, W, ld, want_b, want_ce, cmask, float(grad_scale), int(ignore_index))
+        _CrossEntropy.last_status = rec
+        _BoundaryLoss.last_maps = phi
+        return rec[0].clone()           # not a view: rec is saved for backward and published as the status
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        lg, tg, rec, weight = ctx.saved_tensors
+        N, C, H, W, ld, want_b, want_ce, cmask, grad_scale, ignore_index = ctx.meta
+        M = N * H * W
+        d = torch.empty((N, H, W, C), device=lg.device, dtype=torch.float32)
+        g = gout.contiguous()
+        wp = weight.data_ptr() if weight is not None else None
+        pp = ctx.phi.data_ptr() if ctx.phi is not None else None
+        from . import engine
+        engine._timed(None, "k_bdl_bwd", 4.0 * M * ld + 8.0 * M + (4.0 * M * C if want_b else 0.0) + 4.0 * M * C, lambda: check(
+            lib.cvk_boundary_loss_bwd(lg.data_ptr(), ld, tg.data_ptr(), pp, wp, want_b, want_ce, cmask, rec.data_ptr(), g.data_ptr(),
+                                      grad_scale, d.data_ptr(), C, M, C, ignore_index, _stream(lg)), "cvk_boundary_loss_bwd"), "byte")
+        return d.permute(0, 3, 1, 2), None, None, None, None
+
+
+class BoundaryLoss(nn.Module):
+    """`boundary * B + ce * H` as one autograd node: B the boundary loss of Kervadec et al. ("Boundary loss for highly unbalanced
+    segmentation", MIDL 2019) and H the weighted mean cross-entropy of CrossEntropyLoss(weight=) it is usually ramped in next to.
+      B = 1 / |V| sum over the pixels q of V of sum over the classes c of S of phi_c(q) softmax(logits)_c(q)
+    V = the pixels whose target is not `ignore_index`, S = `classes` (Kervadec's `idc`; None: every class), phi_c = the signed Euclidean
+    distance map of the target's class-c region, computed per image on the device at every call by an exact distance transform
+    (`signed_distance_maps`: positive outside the region, -(distance - 1) inside, 0 where the class is absent from the image or fills
+    it).  Ignored pixels are void: they belong to no class, get a zero gradient row, and bound the regions next to them.  V empty
+    gives B = 0 and a zero gradient (H alone is 0/0 = NaN there, as CrossEntropyLoss).  `weight` (float32 [C] on the logits' device, a
+    registered buffer) enters H only and needs `ce > 0`.
+    The two coefficients live in a registered 2-float device buffer (`coef`) that the kernels read: `loss.boundary = 0.02` and
+    `loss.ce = ...` fill it on the current stream without a sync, so a captured `GraphedStep` follows a schedule without a re-capture.
+    Which terms exist is fixed at construction: a coefficient that was 0 there is never computed, and raising it later is a ValueError.
+    Conventions of CrossEntropyLoss hold: float32 logits [N, C, H, W] (C <= 32; channels_last is read in place), int64 targets
+    [N, H, W], a 0-dim loss, an out-of-range target makes the loss NaN and `last_ce_status()` reports it, `grad_scale` multiplies the
+    backward only.  No float atomic, allocation after the first call of a shape, or host sync: the loss is bitwise reproducible and
+    can be captured (with `optimizer=` and `accumulator=`).  The column maps (2 bytes per pixel and class + 1) and phi (4 bytes per pixel
+    and class) are kept per (shape, classes, device) and shared by every loss of that shape: run a forward's backward before the next
+    forward of the same shape.  After a forward, device views without a sync: `last_record` ([loss, |V|, out of range, B, H, the two
+    coefficients used, sum w[t], then each class's share of B]), `last_terms` ([B, H]), `last_class_terms` ([C]) and `last_maps` (phi,
+    [N, C, H, W]).  Under `ddp.DataParallel` |V| is per rank, as for the other losses.
+    Not provided: 3-D or anisotropic spacing, a Hausdorff / HD95 loss, chamfer approximations, per-class weights on B, maps cached
+    across epochs."""
+
+    def __init__(self, boundary=1.0, ce=0.0, *, classes=None, weight=None, ignore_index=-100, grad_scale=1.0):
+        super().__init__()
+        self._boundary, self._ce, self.classes = _check_boundary_loss_options(boundary, ce, classes, weight)
+        self._terms = (int(self._boundary > 0.0), int(self._ce > 0.0))          # fixed here
+        self.ignore_index = ignore_index
+        self.grad_scale = grad_scale
+        self.register_buffer("weight", weight)
+        self.register_buffer("coef", torch.tensor([self._boundary, self._ce], dtype=torch.float32))
+        self._record = self._maps = None
+        self._C = 0
+
+    def _set(self, slot, name, v):
+        v = _nonneg(name, v)
+        if v > 0.0 and not self._terms[slot]:
+            raise ValueError(f"{name} was 0 at construction, so that term is not computed: construct the loss with {name} > 0")
+        self.coef[slot:slot + 1].fill_(v)          # on the current stream, no sync: the kernels read it from there
+        return v
+
+    @property
+    def boundary(self):
+        return self._boundary
+
+    @boundary.setter
+    def boundary(self, v):
+        self._boundary = self._set(0, "boundary", v)
+
+    @property
+    def ce(self):
+        return self._ce
+
+    @ce.setter
+    def ce(self, v):
+        self._ce = self._set(1, "ce", v)
+
+    def forward(self, logits, target):
+        if self.coef.device != logits.device and logits.is_cuda:
+            self.coef = self.coef.to(logits.device)        # once, at the first call (before any capture)
+        loss = _BoundaryLoss.apply(logits, target, self.weight, self.coef,
+                                   (self._terms[0], self._terms[1], self.classes, self.ignore_index, self.grad_scale))
+        self._record, self._maps, self._C = _CrossEntropy.last_status, _BoundaryLoss.last_maps, logits.shape[1]
+        return loss
+
+    def _rec(self):
+        if self._record is None:
+            raise RuntimeError("no forward has run yet")
+        return self._record
+
+    @property
+    def last_record(self):
+        """The device record of the most recent forward (float32 [40], no sync)."""
+        return self._rec()
+
+    @property
+    def last_terms(self):
+        """[B, H] of the most recent forward (device tensor, no sync)."""
+        return self._rec()[3:5]
+
+    @property
+    def last_class_terms(self):
+        """Each class's share of B in the most recent forward, [C]; they sum to B (device tensor, no sync)."""
+        return self._rec()[BDL_RECORD_HEAD:BDL_RECORD_HEAD + self._C]
+
+    @property
+    def last_maps(self):
+        """phi of the most recent forward, float32 [N, C, H, W] (a channels_last view of the shared buffer; None without the boundary
+        term).  Read it before another loss of the same shape runs."""
+        self._rec()
+        return None if self._maps is None else self._maps.permute(0, 3, 1, 2)
+
+
+def boundary_loss(logits, target, boundary=1.0, ce=0.0, *, classes=None, weight=None, ignore_index=-100):
+    """Functional form of BoundaryLoss (same kernels; the two coefficients are copied to the device at every call)."""
+    boundary, ce, classes = _check_boundary_loss_options(boundary, ce, classes, weight)
+    coef = torch.tensor([boundary, ce], dtype=torch.float32).to(logits.device)
+    return _BoundaryLoss.apply(logits, target, weight, coef, (int(boundary > 0.0), int(ce > 0.0), classes, ignore_index, 1.0))
+
+
 KD_RECORD = 9                                      # loss | valid | out of range | sum w[t] | H | K | |D| | agree | agree / |D|
 
 
