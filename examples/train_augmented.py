@@ -35,17 +35,23 @@ def synthetic_camvid(n, b, seed):
         yield np.clip(frames, 0, 255).astype(np.uint8), masks
 
 
-def validate(net, batches, tta, window, boundary):
-    """(accuracy, mIoU, boundary F1 or None) of one validation pass."""
-    if boundary is None:
+def validate(net, batches, tta, window, boundary, surface=None):
+    """(accuracy, mIoU, the contour scores of one validation pass: boundary F1 and / or HD95 and ASSD, None without a meter)."""
+    if boundary is None and surface is None:
         acc, _, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window)
         return acc, miou, None
-    rep = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window, boundary=boundary)
-    return rep["accuracy"], rep["miou"], rep["bf"]
+    rep = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window,
+                              boundary=[m for m in (boundary, surface) if m is not None])
+    return rep["accuracy"], rep["miou"], {k: rep[k] for k in ("bf", "hd95", "assd") if k in rep}
 
 
-def bf_text(bf):
-    return "" if bf is None else f"  BF {bf:.4f}"
+def bf_text(scores, percentile=95):
+    if scores is None:
+        return ""
+    out = f"  BF {scores['bf']:.4f}" if "bf" in scores else ""
+    if "hd95" in scores:
+        out += f"  HD{percentile:g} {scores['hd95']:.2f} px  ASSD {scores['assd']:.2f} px"
+    return out
 
 
 def main():
@@ -111,8 +117,17 @@ def main():
     ap.add_argument("--boundary-f1", action="store_true", help="also report the boundary F1 measure (BF score) of the validation pass (cvk.BoundaryMeter)")
     ap.add_argument("--bf-tolerance", type=float, default=0.0075, metavar="X",
                     help="with --boundary-f1: the matching distance as a fraction of the image diagonal (default 0.75 %%)")
+    ap.add_argument("--surface-distance", action="store_true",
+                    help="also report HD95 and the average symmetric surface distance of the validation pass, in pixels (cvk.SurfaceDistanceMeter)")
+    ap.add_argument("--hd-percentile", type=float, default=95.0, metavar="Q",
+                    help="with --surface-distance: the percentile of the Hausdorff distance, 0..100 (default 95; 100 is the Hausdorff distance)")
     a = ap.parse_args()
-    tta = window = boundary = None
+    tta = window = boundary = surface = None
+    if a.surface_distance:
+        try:
+            surface = cvk.SurfaceDistanceMeter(num_classes=12, ignore_index=11, percentile=a.hd_percentile)
+        except ValueError as e:
+            ap.error(f"--hd-percentile: {e}")
     if a.boundary_f1:
         try:
             boundary = cvk.BoundaryMeter(num_classes=12, ignore_index=11, tolerance=a.bf_tolerance)
@@ -254,13 +269,13 @@ def main():
             print(f"  grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of {n.numel()} steps "
                   f"(max_norm {a.clip_grad_norm:g})")
         val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
-        acc, miou, bf = validate(net, val, tta, window, boundary)
-        print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}{bf_text(bf)}")
+        acc, miou, bf = validate(net, val, tta, window, boundary, surface)
+        print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}{bf_text(bf, a.hd_percentile)}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
                 val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)    # the same frames again
-                acc_e, miou_e, bf_e = validate(net, val, tta, window, boundary)
-            print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}{bf_text(bf_e)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
+                acc_e, miou_e, bf_e = validate(net, val, tta, window, boundary, surface)
+            print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}{bf_text(bf_e, a.hd_percentile)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
 
 
 if __name__ == "__main__":

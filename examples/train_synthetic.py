@@ -23,17 +23,23 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pytorch_camvid_amd as cvk  # noqa: E402
 
 
-def validate(net, batches, tta, window, boundary):
-    """(accuracy, mIoU, boundary F1 or None) of one validation pass."""
-    if boundary is None:
+def validate(net, batches, tta, window, boundary, surface=None):
+    """(accuracy, mIoU, the contour scores of one validation pass: boundary F1 and / or HD95 and ASSD, None without a meter)."""
+    if boundary is None and surface is None:
         acc, _, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window)
         return acc, miou, None
-    rep = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window, boundary=boundary)
-    return rep["accuracy"], rep["miou"], rep["bf"]
+    rep = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window,
+                              boundary=[m for m in (boundary, surface) if m is not None])
+    return rep["accuracy"], rep["miou"], {k: rep[k] for k in ("bf", "hd95", "assd") if k in rep}
 
 
-def bf_text(bf):
-    return "" if bf is None else f"  BF {bf:.4f}"
+def bf_text(scores, percentile=95):
+    if scores is None:
+        return ""
+    out = f"  BF {scores['bf']:.4f}" if "bf" in scores else ""
+    if "hd95" in scores:
+        out += f"  HD{percentile:g} {scores['hd95']:.2f} px  ASSD {scores['assd']:.2f} px"
+    return out
 
 
 def main():
@@ -104,8 +110,17 @@ def main():
     ap.add_argument("--boundary-f1", action="store_true", help="also report the boundary F1 measure (BF score) of the validation pass (cvk.BoundaryMeter)")
     ap.add_argument("--bf-tolerance", type=float, default=0.0075, metavar="X",
                     help="with --boundary-f1: the matching distance as a fraction of the image diagonal (default 0.75 %%)")
+    ap.add_argument("--surface-distance", action="store_true",
+                    help="also report HD95 and the average symmetric surface distance of the validation pass, in pixels (cvk.SurfaceDistanceMeter)")
+    ap.add_argument("--hd-percentile", type=float, default=95.0, metavar="Q",
+                    help="with --surface-distance: the percentile of the Hausdorff distance, 0..100 (default 95; 100 is the Hausdorff distance)")
     a = ap.parse_args()
-    tta = window = boundary = None
+    tta = window = boundary = surface = None
+    if a.surface_distance:
+        try:
+            surface = cvk.SurfaceDistanceMeter(num_classes=12, ignore_index=11, percentile=a.hd_percentile)
+        except ValueError as e:
+            ap.error(f"--hd-percentile: {e}")
     if a.boundary_f1:
         try:
             boundary = cvk.BoundaryMeter(num_classes=12, ignore_index=11, tolerance=a.bf_tolerance)
@@ -282,14 +297,14 @@ def main():
             m = masks[it].to(dev)
             frames = ((m.unsqueeze(-1) * torch.tensor([20, 15, 10], device=dev)) % 256).clamp(0, 255).to(torch.uint8)
             batches.append((cvk.preprocess_uint8(frames), m))
-        acc, miou, bf = validate(net, batches, tta, window, boundary)
+        acc, miou, bf = validate(net, batches, tta, window, boundary, surface)
         if rank == 0:
-            print(f"          val acc {acc:.4f}  mIoU(11 classes) {miou:.4f}{bf_text(bf)}")
+            print(f"          val acc {acc:.4f}  mIoU(11 classes) {miou:.4f}{bf_text(bf, a.hd_percentile)}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
-                acc_e, miou_e, bf_e = validate(net, batches, tta, window, boundary)
+                acc_e, miou_e, bf_e = validate(net, batches, tta, window, boundary, surface)
             if rank == 0:
-                print(f"          EMA acc {acc_e:.4f}  mIoU(11 classes) {miou_e:.4f}{bf_text(bf_e)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
+                print(f"          EMA acc {acc_e:.4f}  mIoU(11 classes) {miou_e:.4f}{bf_text(bf_e, a.hd_percentile)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
     if rank == 0:
         torch.save(net.state_dict(), "/tmp/cvk_synthetic.pth")             # train.py:232-240; loads into the reference too
         if a.ema_decay is not None:

@@ -678,6 +678,39 @@ int cvk_boundary_counts(const int64_t* pred, const int64_t* label, int64_t* coun
 int cvk_boundary_map(const int64_t* map, const int64_t* void_from, uint8_t* out_u8, int N, int H, int W, int num_classes,
                      int ignore_index, void* stream);
 
+/* ---- surface distances: Hausdorff distance, its percentile (HD95) and the average symmetric surface distance (not in the reference) ---
+ * pred, label: DEVICE int64 [N][H][W]; 1 <= num_classes <= 32.  Void pixels, the masked prediction and "contour pixel of class c" are
+ * those of cvk_boundary_counts / cvk_boundary_map above, exactly: void iff label == ignore_index, in both maps; 4-connected; the image
+ * border makes no contour; a value that is no class has no contour of its own but bounds its neighbours.  Everything is per image.
+ * For a contour pixel z of class c of the prediction, d2_PG(z) is the squared Euclidean distance, an exact integer, to the nearest
+ * contour pixel of class c of the label map of the same image, -1 when the label map has none; d2_GP is the same with the maps
+ * exchanged.  Limits, those of the distance transform: H <= 65534, (H - 1)^2 + (W - 1)^2 < 2^24, N H W < 2^31.
+ *   d2: DEVICE int32 [2][N][H][W]: plane 0 holds d2_PG at the prediction's contour pixels, plane 1 d2_GP at the label's; every other
+ *     pixel holds -2.
+ *   record: DEVICE int64 [N][2][num_classes][8], WRITTEN (not added into); direction 0 = P -> G, 1 = G -> P.  Of the segment (image,
+ *     direction, class c), whose values are the d2 of the source map's contour pixels of class c:
+ *       [0] n = contour pixels of class c in the source map,  [1] m = those in the other map;
+ *           the segment is "evaluated" iff n > 0 and m > 0 (then every d2 of it is >= 0);
+ *       [2] the largest d2 (-1 unless evaluated);
+ *       [3] Q = the sum over the segment of isqrt(d2 << 32), the largest integer q with q * q <= d2 * 2^32: the distance in 2^-16 pixels,
+ *           defined by integers alone (0 unless evaluated; q < 2^28 and fewer than 2^31 pixels, so Q fits);
+ *       [4] k = floor((n - 1) qnum / qden),  [5] r = ((n - 1) qnum) mod qden;
+ *       [6] d2_lo = the k-th smallest d2 of the segment (0-based),
+ *       [7] d2_hi = the min(k + 1, n - 1)-th smallest when r > 0, else d2_lo;     [4]..[7] are -1 unless evaluated.
+ *     qnum / qden is the percentile as a fraction, 0 <= qnum <= qden <= 10000 (95, 100 for HD95).  With a = sqrt(d2_lo), b = sqrt(d2_hi)
+ *     the percentile of the distances under numpy's default "linear" rule is a + (b - a) r / qden; the Hausdorff distance of a class is
+ *     the larger sqrt([2]) of the two directions; ASSD = (Q_PG + Q_GP) / 65536 / (n_P + n_G).
+ * workspace: DEVICE, cvk_surface_workspace_bytes(N, H, W, num_classes) bytes (0: unsupported sizes), 16-byte aligned, contents need not
+ *   be initialised: the entry point clears what it needs on the given stream.  It holds the uint16 column distances [2][M][C] to the
+ *   contours of either map, the contour bytes [2][M], and per segment the integer sums and the two histograms of the select.
+ * cvk_surface_record_slots() = 8.  Integer atomics only: the outputs do not depend on the order of arrival, two runs agree bit for bit.
+ * No allocation, no host sync.  The rank values come from an exact histogram select per segment: one bin per value below 4096, above
+ * it one bin per 4096 values and a second level over the low 12 bits. */
+int64_t cvk_surface_workspace_bytes(int N, int H, int W, int num_classes);
+int cvk_surface_record_slots(void);
+int cvk_surface_distances(const int64_t* pred, const int64_t* label, int N, int H, int W, int num_classes, int ignore_index, int qnum,
+                          int qden, void* workspace, int32_t* d2, int64_t* record, void* stream);
+
 /* ---- multi-scale / flip test-time augmentation: the merge of the views' logits (not in the reference) ------------------
  * Bilinear resampling here is torch's F.interpolate(mode="bilinear", align_corners=False) with the sample position taken from
  * integers: for destination index d of `out` samples over `in` source samples, num = max((2 d + 1) in - out, 0), lower source

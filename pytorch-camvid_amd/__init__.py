@@ -13,7 +13,8 @@ from .functional import (ConfusionMeter, CrossEntropyLoss, argmax_channels, cros
                          LovaszSoftmaxLoss, lovasz_softmax,
                          BoundaryLoss, boundary_loss, squared_distance_maps, signed_distance_maps,
                          DistillationLoss, distillation_loss, distillation_scales, BoundaryMeter, label_boundaries,
-                         boundary_tolerance, boundary_scores)
+                         boundary_tolerance, boundary_scores, SurfaceDistanceMeter, surface_distances, surface_distance_scores,
+                         surface_percentile)
 from .optim import FlatAdamW, FlatSGD, clip_grad_norm_, ema_alpha  # noqa: F401
 from .accumulate import GradAccumulator  # noqa: F401
 from . import ddp  # noqa: F401
@@ -24,5 +25,5 @@ from .checkpoint import (save_checkpoint, load_checkpoint, latest_checkpoint, ch
                          save_policy, reference_state_dict)
 
 __all__ = ["UNet", "SegNet", "BasicConv2d", "BasicConv", "UpSample2d", "get_model", "set_conv_precision", "set_split_operands", "CrossEntropyLoss",
-           "SegmentationLoss", "FocalLoss", "DiceLoss", "segmentation_loss", "OhemCrossEntropyLoss", "ohem_cross_entropy", "ohem_loss_threshold", "LovaszSoftmaxLoss", "lovasz_softmax", "BoundaryLoss", "boundary_loss", "squared_distance_maps", "signed_distance_maps", "DistillationLoss", "distillation_loss", "distillation_scales", "cross_entropy", "last_ce_status", "argmax_channels", "ConfusionMeter", "BoundaryMeter", "label_boundaries", "boundary_tolerance", "boundary_scores", "ClassFrequencyMeter", "class_weights", "weights_from_counts", "evaluate", "evaluate_report", "predict", "TestTimeAugmentation", "SlidingWindow", "preprocess_uint8", "DevicePrefetcher", "transforms", "FlatAdamW", "FlatSGD", "clip_grad_norm_", "ema_alpha", "GradAccumulator", "ddp", "GraphedStep", "mark_weights_dirty", "save_checkpoint", "load_checkpoint", "latest_checkpoint", "checkpoint_epoch", "resume", "save_policy",
+           "SegmentationLoss", "FocalLoss", "DiceLoss", "segmentation_loss", "OhemCrossEntropyLoss", "ohem_cross_entropy", "ohem_loss_threshold", "LovaszSoftmaxLoss", "lovasz_softmax", "BoundaryLoss", "boundary_loss", "squared_distance_maps", "signed_distance_maps", "DistillationLoss", "distillation_loss", "distillation_scales", "cross_entropy", "last_ce_status", "argmax_channels", "ConfusionMeter", "BoundaryMeter", "label_boundaries", "boundary_tolerance", "boundary_scores", "SurfaceDistanceMeter", "surface_distances", "surface_distance_scores", "surface_percentile", "ClassFrequencyMeter", "class_weights", "weights_from_counts", "evaluate", "evaluate_report", "predict", "TestTimeAugmentation", "SlidingWindow", "preprocess_uint8", "DevicePrefetcher", "transforms", "FlatAdamW", "FlatSGD", "clip_grad_norm_", "ema_alpha", "GradAccumulator", "ddp", "GraphedStep", "mark_weights_dirty", "save_checkpoint", "load_checkpoint", "latest_checkpoint", "checkpoint_epoch", "resume", "save_policy",
            "reference_state_dict", "build_library", "load_library", "CvkError"]

@@ -1332,6 +1332,168 @@ def label_boundaries(labels, num_classes=12, ignore_index=11, void_from=None):
     return out
 
 
+SURFACE_RECORD_SLOTS = 8         # include/cvk.h: n, m, max d2, Q, k, r, d2_lo, d2_hi
+SURFACE_MAX_DENOMINATOR = 10000
+
+
+def surface_percentile(percentile=95):
+    """The percentile of the surface-distance meter as the fraction (qnum, qden) = percentile / 100 in lowest terms, in exact rational
+    arithmetic (`percentile` is read through its decimal string, as `boundary_tolerance` reads its tolerance): 95 -> (19, 20),
+    "97.5" -> (39, 40).  It must lie in [0, 100] and the denominator must not exceed 10000."""
+    from fractions import Fraction
+    try:
+        if isinstance(percentile, bool):
+            raise ValueError
+        q = Fraction(str(percentile)) / 100
+    except (ValueError, ZeroDivisionError):
+        raise ValueError(f"percentile must be a number in [0, 100]. Got: {percentile!r}") from None
+    if not 0 <= q <= 1:
+        raise ValueError(f"percentile must lie in [0, 100]. Got: {percentile!r}")
+    if q.denominator > SURFACE_MAX_DENOMINATOR:
+        raise ValueError(f"percentile {percentile!r} / 100 has denominator {q.denominator}; the kernel serves at most "
+                         f"{SURFACE_MAX_DENOMINATOR}")
+    return int(q.numerator), int(q.denominator)
+
+
+def surface_distance_scores(records, ignore_index=None, percentile=95):
+    """Hausdorff distance, its percentile and the average symmetric surface distance from the records of `surface_distances` /
+    `SurfaceDistanceMeter.records()`, int64 [images, 2, K, 8] (include/cvk.h: n, m, max d2, Q, k, r, d2_lo, d2_hi per image, direction
+    and class), in float64 on the host.  `percentile` must be the one the records were made with (their slots hold k and r, not the
+    denominator; a percentile that does not fit them raises ValueError).  A class is evaluated in an image iff both maps have a contour of it; then
+      hd   = the larger sqrt(max d2) of the two directions,
+      hdq  = the larger a + (b - a) r / qden of the two directions, a = sqrt(d2_lo), b = sqrt(d2_hi): numpy's default "linear"
+             percentile of the distances per direction, then the larger one (MONAI's rule),
+      assd = (Q_PG + Q_GP) / 65536 / (n_P + n_G).
+    A class with a contour in exactly one map of an image is unmatched: it is counted and takes part in no mean (public libraries
+    return inf or NaN there).  An image's score is the mean over its evaluated classes, the set's score the mean over the images that
+    have one (NaN without one).  Returns "hd95" (the percentile score, whatever `percentile` is), "hd", "assd", "hd95_per_class",
+    "hd_per_class", "assd_per_class" (float64 [K]: the mean over the images where the class is evaluated, NaN where it never is and at
+    ignore_index), "unmatched" (int64 [K]), "images" (how many images had an evaluated class) and "percentile"."""
+    import numpy as np
+    from fractions import Fraction
+    qnum, qden = surface_percentile(percentile)
+    rec = np.asarray(records, dtype=np.int64)
+    if rec.ndim != 4 or rec.shape[1] != 2 or rec.shape[3] != SURFACE_RECORD_SLOTS:
+        raise ValueError(f"expected records of shape [images, 2, K, {SURFACE_RECORD_SLOTS}], got {list(rec.shape)}")
+    K = rec.shape[2]
+    nP, nG = rec[:, 0, :, 0], rec[:, 1, :, 0]
+    ev = (nP > 0) & (nG > 0)                                            # [images, K]
+    unmatched = ((nP > 0) ^ (nG > 0)).sum(axis=0).astype(np.int64)
+    n1 = rec[..., 0] - 1
+    if (np.where(ev[:, None, :], rec[..., 4] * qden + rec[..., 5] - n1 * qnum, 0) != 0).any():
+        raise ValueError(f"these records were not made with percentile {percentile!r}: their ranks k, r do not satisfy "
+                         f"k * {qden} + r = (n - 1) * {qnum}")
+    f = np.where(ev[:, None, :, None], rec, 0).astype(np.float64)      # unevaluated slots (-1) must not reach a root
+    hd = np.sqrt(f[..., 2]).max(axis=1)
+    a, b = np.sqrt(f[..., 6]), np.sqrt(f[..., 7])
+    hdq = (a + (b - a) * f[..., 5] / float(qden)).max(axis=1)
+    assd = np.divide((f[:, 0, :, 3] + f[:, 1, :, 3]) / 65536.0, (nP + nG).astype(np.float64), out=np.zeros(ev.shape), where=ev)
+
+    def masked_mean(v, axis):
+        n = ev.sum(axis=axis)
+        return np.divide(np.where(ev, v, 0.0).sum(axis=axis), n, out=np.full(n.shape, np.nan), where=n > 0)
+
+    out = {}
+    scored = ev.any(axis=1)
+    for name, v in (("hd95", hdq), ("hd", hd), ("assd", assd)):
+        image = masked_mean(v, 1)
+        per_class = masked_mean(v, 0)
+        if ignore_index is not None and 0 <= ignore_index < K:
+            per_class[ignore_index] = np.nan
+        out[name] = float(image[scored].mean()) if scored.any() else float("nan")
+        out[name + "_per_class"] = per_class
+    out["unmatched"], out["images"] = unmatched, int(scored.sum())
+    out["percentile"] = float(Fraction(qnum, qden) * 100)
+    return out
+
+
+class _SurfaceBuffers:
+    """The device buffers of cvk_surface_distances, kept per (N, H, W, classes, device): the workspace and the meter's d2 planes."""
+
+    _buffers = {}
+
+    @staticmethod
+    def get(lib, N, H, W, C, device, want_d2):
+        key = (N, H, W, C, str(device))
+        ent = _SurfaceBuffers._buffers.get(key)
+        if ent is None:
+            nbytes = lib.cvk_surface_workspace_bytes(N, H, W, C)
+            if nbytes <= 0:
+                raise ValueError(f"surface distances serve 1 to {EDT_MAX_CLASSES} classes, H <= 65534, (H - 1)^2 + (W - 1)^2 < 2^24 and "
+                                 f"fewer than 2^31 pixels, got N = {N}, H = {H}, W = {W}, classes = {C}")
+            ent = _SurfaceBuffers._buffers[key] = [torch.empty(nbytes, device=device, dtype=torch.uint8), None]
+        if want_d2 and ent[1] is None:
+            ent[1] = torch.empty((2, N, H, W), device=device, dtype=torch.int32)
+        return ent
+
+
+def _surface_call(who, pred, label, num_classes, ignore_index, frac, d2):
+    """One cvk_surface_distances call; d2 None: the kept planes of this shape.  Returns (d2, record)."""
+    _check_boundary_maps(who, pred, label)
+    lib = _lib.load()
+    N, H, W = pred.shape
+    ws, kept = _SurfaceBuffers.get(lib, N, H, W, num_classes, pred.device, d2 is None)
+    if d2 is None:
+        d2 = kept
+    p = pred.contiguous(); l = label.contiguous()
+    record = torch.empty((N, 2, num_classes, SURFACE_RECORD_SLOTS), device=p.device, dtype=torch.int64)
+    check(lib.cvk_surface_distances(p.data_ptr(), l.data_ptr(), N, H, W, num_classes, ignore_index, frac[0], frac[1], ws.data_ptr(),
+                                    d2.data_ptr(), record.data_ptr(), _stream(p)), "cvk_surface_distances")
+    return d2, record
+
+
+def _check_surface_classes(who, num_classes):
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= EDT_MAX_CLASSES:
+        raise ValueError(f"{who} serves 1 to {EDT_MAX_CLASSES} classes. Got: {num_classes}")
+    return num_classes
+
+
+def surface_distances(pred, label, num_classes=12, ignore_index=11, percentile=95):
+    """Contour-to-contour distances of int64 maps [N,H,W] on the GPU, per image and class, under BoundaryMeter's contour rule
+    (include/cvk.h, cvk_surface_distances): `d2` int32 [2,N,H,W], plane 0 the exact squared Euclidean distance from each contour pixel
+    of the prediction to the nearest contour pixel of its class in the label map (-1: the label map has none), plane 1 the same from
+    the label's contour pixels to the prediction's, -2 at every other pixel; `record` int64 [N,2,num_classes,8], per (image, direction,
+    class): n, m, max d2, Q (the sum of the distances in 2^-16 pixels, by integers), and the ranks and values of the `percentile`:
+    k, r, d2_lo, d2_hi.  Both are new device tensors; no host sync.  `surface_distance_scores` turns records into scores."""
+    _check_surface_classes("surface_distances", num_classes)
+    frac = surface_percentile(percentile)
+    _check_boundary_maps("surface_distances", pred, label)
+    d2 = torch.empty((2,) + tuple(pred.shape), device=pred.device, dtype=torch.int32)
+    return _surface_call("surface_distances", pred, label, num_classes, int(ignore_index), frac, d2)
+
+
+class SurfaceDistanceMeter:
+    """Hausdorff distance (HD), its percentile (HD95 by default; MONAI's compute_hausdorff_distance(percentile=95), medpy's hd95) and
+    the average symmetric surface distance (ASSD) of predictions against labels, per image and class, between the 4-connected contours
+    of BoundaryMeter's rule.  Distances, sums and the exact order statistics are made on the device by one cvk_surface_distances call
+    per batch (integers only: two runs agree bit for bit); no host sync until `records()` / `compute()`.  Pixels whose label is
+    `ignore_index` are void in both maps.  A class whose contour exists in only one map of an image is counted as unmatched and enters
+    no mean."""
+
+    def __init__(self, num_classes=12, ignore_index=11, percentile=95):
+        self.num_classes = _check_surface_classes("SurfaceDistanceMeter", num_classes)
+        self.ignore_index, self.percentile = int(ignore_index), percentile
+        self._frac = surface_percentile(percentile)
+        self._parts = []
+
+    def reset(self):
+        self._parts = []
+
+    def update(self, pred, label):
+        _, record = _surface_call("SurfaceDistanceMeter.update", pred, label, self.num_classes, self.ignore_index, self._frac, None)
+        self._parts.append(record)
+
+    def records(self):
+        """int64 [images, 2, num_classes, 8] on the host, in the order of the updates — one device->host copy."""
+        if not self._parts:
+            return torch.zeros((0, 2, self.num_classes, SURFACE_RECORD_SLOTS), dtype=torch.int64)
+        return (self._parts[0] if len(self._parts) == 1 else torch.cat(self._parts)).cpu()
+
+    def compute(self):
+        """`surface_distance_scores` of `records()`."""
+        return surface_distance_scores(self.records().numpy(), self.ignore_index, self.percentile)
+
+
 WEIGHT_METHODS = ("median_frequency", "enet")
 
 
@@ -1693,9 +1855,9 @@ class TestTimeAugmentation:
         return self._merge(net, images)
 
 
-def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None, boundary=None):
+def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None, contour_meters=()):
     """evaluate / evaluate_report with test-time augmentation: (meter, the per-batch losses of the loss view: empty without one).
-    `boundary` (a BoundaryMeter) sees the predictions the ConfusionMeter sees."""
+    `contour_meters` (BoundaryMeter, SurfaceDistanceMeter) see the predictions the ConfusionMeter sees."""
     meter, losses = None, []
 
     def keep_loss(masks, want):
@@ -1710,8 +1872,8 @@ def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None, bo
         if meter is None:
             meter = ConfusionMeter(num_classes, ignore_index, pred.device)
         meter.update(pred, masks)
-        if boundary is not None:
-            boundary.update(pred, masks)
+        for m in contour_meters:
+            m.update(pred, masks)
     return meter, losses
 
 
@@ -1753,10 +1915,26 @@ def evaluate(net, batches, num_classes=12, ignore_index=11, window=None, tta=Non
     return meter.compute()
 
 
-def _with_boundary(report, boundary):
-    if boundary is not None:
-        bf = boundary.compute()
-        report["bf"], report["bf_per_class"] = bf["bf"], bf["bf_per_class"]
+SURFACE_REPORT_KEYS = ("hd95", "hd", "assd", "hd95_per_class", "hd_per_class", "assd_per_class")
+
+
+def _contour_meters(boundary):
+    """The meters behind evaluate_report's `boundary`: None, one meter, or a tuple / list with at most one meter of either kind."""
+    meters = list(boundary) if isinstance(boundary, (tuple, list)) else [] if boundary is None else [boundary]
+    for m in meters:
+        if not isinstance(m, (BoundaryMeter, SurfaceDistanceMeter)):
+            raise ValueError("boundary must be a BoundaryMeter or None, or a SurfaceDistanceMeter, or a tuple or list of one of each. "
+                             f"Got: {type(m).__name__}")
+    if len({type(m) for m in meters}) != len(meters):
+        raise ValueError("boundary holds two meters of one kind: their scores would share the report's keys")
+    return meters
+
+
+def _with_boundary(report, contour_meters):
+    for m in contour_meters:
+        scores = m.compute()
+        for k in SURFACE_REPORT_KEYS if isinstance(m, SurfaceDistanceMeter) else ("bf", "bf_per_class"):
+            report[k] = scores[k]
     return report
 
 
@@ -1768,15 +1946,17 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
     scale-1.0 unmirrored view at the label size: None when that view is not among the views.  With `window` (a SlidingWindow) the
     predictions and the logits `loss_fn` sees are the windows' merged ones.  One of the two: TestTimeAugmentation(..., window=) combines
     them.  With `boundary` (a BoundaryMeter) the meter is reset, sees every batch's predictions and masks, and the report gains "bf"
-    (the boundary F1 measure) and "bf_per_class"; the meter keeps its counts for `boundary.compute()`."""
+    (the boundary F1 measure) and "bf_per_class"; the meter keeps its counts for `boundary.compute()`.  `boundary` also takes a
+    SurfaceDistanceMeter, or a tuple or list with one meter of either kind: a SurfaceDistanceMeter is reset and fed the same way, and
+    the report gains "hd95", "hd", "assd" and their "_per_class" arrays; the meter's `compute()` has the rest (unmatched classes,
+    images)."""
     _check_tta_window("evaluate_report", tta, window)
-    if boundary is not None and not isinstance(boundary, BoundaryMeter):
-        raise ValueError(f"boundary must be a BoundaryMeter or None. Got: {type(boundary).__name__}")
+    contour_meters = _contour_meters(boundary)
     loss_fn = loss_fn or CrossEntropyLoss()
-    if boundary is not None:
-        boundary.reset()
+    for m in contour_meters:
+        m.reset()
     if tta is not None:
-        meter, losses = _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn, boundary)
+        meter, losses = _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn, contour_meters)
         if meter is None:
             raise ValueError("evaluate_report(): no batches")
         acc, iou, miou = meter.compute()
@@ -1787,7 +1967,7 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
             for l in losses[1:]:
                 loss_sum = loss_sum + l
             loss = float(loss_sum) / len(losses)
-        return _with_boundary({"miou": miou, "precision": prec, "recall": rec, "loss": loss, "accuracy": acc, "iou": iou}, boundary)
+        return _with_boundary({"miou": miou, "precision": prec, "recall": rec, "loss": loss, "accuracy": acc, "iou": iou}, contour_meters)
     was_training = net.training
     net.eval()
     meter, loss_sum, n = None, None, 0
@@ -1804,15 +1984,15 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
             loss_sum = l if loss_sum is None else loss_sum + l
             n += 1
             meter.update(pred, masks)
-            if boundary is not None:
-                boundary.update(pred, masks)
+            for m in contour_meters:
+                m.update(pred, masks)
     net.train(was_training)
     if meter is None:
         raise ValueError("evaluate_report(): no batches")
     acc, iou, miou = meter.compute()
     prec, rec = meter.precision_recall()
     return _with_boundary({"miou": miou, "precision": prec, "recall": rec, "loss": float(loss_sum) / n, "accuracy": acc, "iou": iou},
-                          boundary)
+                          contour_meters)
 
 
 def predict(net, image_u8, out_size=None, mean=CAMVID_MEAN, std=CAMVID_STD, window=None, tta=None):
