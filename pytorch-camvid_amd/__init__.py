@@ -6,13 +6,14 @@ train.py's loss): UNet, SegNet, BasicConv2d, BasicConv, UpSample2d, get_model, C
 """
 from ._lib import CvkError, build as build_library, load as load_library          # noqa: F401
 from .modules import BasicConv, BasicConv2d, SegNet, UNet, UpSample2d, get_model, set_conv_precision, set_split_operands   # noqa: F401
-from .functional import (ConfusionMeter, CrossEntropyLoss, argmax_channels, cross_entropy, evaluate,  # noqa: F401
-                         evaluate_report, predict, preprocess_uint8, DevicePrefetcher, last_ce_status, TestTimeAugmentation, SlidingWindow,
-                         ClassFrequencyMeter, class_weights, weights_from_counts, SegmentationLoss, FocalLoss,
-                         DiceLoss, segmentation_loss, OhemCrossEntropyLoss, ohem_cross_entropy, ohem_loss_threshold,
-                         LovaszSoftmaxLoss, lovasz_softmax,
-                         BoundaryLoss, boundary_loss, squared_distance_maps, signed_distance_maps,
-                         DistillationLoss, distillation_loss, distillation_scales, BoundaryMeter, label_boundaries,
+from .losses import (CrossEntropyLoss, cross_entropy, last_ce_status, SegmentationLoss, FocalLoss,  # noqa: F401
+                     DiceLoss, segmentation_loss, OhemCrossEntropyLoss, ohem_cross_entropy, ohem_loss_threshold,
+                     LovaszSoftmaxLoss, lovasz_softmax,
+                     BoundaryLoss, boundary_loss, squared_distance_maps, signed_distance_maps,
+                     DistillationLoss, distillation_loss, distillation_scales)
+from .functional import (ConfusionMeter, argmax_channels, evaluate,  # noqa: F401
+                         evaluate_report, predict, preprocess_uint8, DevicePrefetcher, TestTimeAugmentation, SlidingWindow,
+                         ClassFrequencyMeter, class_weights, weights_from_counts, BoundaryMeter, label_boundaries,
                          boundary_tolerance, boundary_scores, SurfaceDistanceMeter, surface_distances, surface_distance_scores,
                          surface_percentile)
 from .optim import FlatAdamW, FlatSGD, clip_grad_norm_, ema_alpha  # noqa: F401
