@@ -177,6 +177,10 @@ int cvk_w6_wgrad_ksplit(int T, int Cin_pad, int Cout);
 int cvk_w6_dy_transform(const float* dy, int ld_dy, float* E, int N, int H, int W, int Cout, void* stream);
 int cvk_w6_dy_transform_both(const float* dy, int ld_dy, float* Vp, float* E, int N, int H, int W, int Cout, void* stream);
 int cvk_w6_gemm_tn(const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, void* stream);
+/* cvk_w2d_gemm_tn / cvk_w6_gemm_tn on at most max_workgroups workgroups (rounded down to a multiple of 8; 0 = one per (tile, depth range) job): a
+ * capped grid walks the jobs in a loop; a job owns its depth range and its plane of P, so P is bitwise independent of the cap */
+int cvk_w2d_gemm_tn_wg(const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, int max_workgroups, void* stream);
+int cvk_w6_gemm_tn_wg(const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, int max_workgroups, void* stream);
 /* OPT-IN SPLIT-OPERAND PATH (round 5; the executor's default fp32 path is exact-fp32 MFMA — this one runs only under runner.w2d_split): the
  * GEMM stage above on the 16-bit matrix pipe with split fp32 operands, accumulated in fp32 (csrc/split3.hip, csrc/split_fmt.h, tools/study/).
  *   fmt 3: x = x1 + x2 + x3 in bf16, the six largest cross-products (v_mfma_f32_16x16x32_bf16): fp32-MFMA accuracy at 0.375 of its matrix time;
@@ -328,6 +332,23 @@ int cvk_bn_bwd_dx_e4p(cvk_view dout, const float* y, int ldy, const float* scale
 int cvk_wgradp_dy_slack(int W);
 int cvk_wgradp_gemm_sm_dy(const float* E4p, const float* dy, const float* V6sm, float* dw, int N, int H, int W, int Cin, int Cin_pad, int Cout,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* The three plane GEMMs on a CAPPED grid: at most max_workgroups one-wave workgroups (rounded down to a multiple of 8; 0 = one per task, the launch
+ * of the entry points above), which walk the tasks in a job loop.  A task owns its run of depth steps and its slab whichever workgroup runs it, so
+ * dw is bitwise independent of the cap.  For callers that run bandwidth-bound work beside the GEMM (cvk_side_begin) or leave CUs to RCCL. */
+int cvk_wgradp_gemm_wg(const float* E6, const float* V6, float* dw, int N, int H, int W, int Cin, int Cin_pad, int Cout, void* workspace,
+                       size_t workspace_bytes, int max_workgroups, void* stream);
+int cvk_wgradp_gemm_sm_wg(const float* E6, const float* V6sm, float* dw, int N, int H, int W, int Cin, int Cin_pad, int Cout, void* workspace,
+                          size_t workspace_bytes, int max_workgroups, void* stream);
+int cvk_wgradp_gemm_sm_dy_wg(const float* E4p, const float* dy, const float* V6sm, float* dw, int N, int H, int W, int Cin, int Cin_pad, int Cout,
+                             void* workspace, size_t workspace_bytes, int max_workgroups, void* stream);
+/* Fork / join of the library's side stream (csrc/side.cpp; one per device, created on first use, non-blocking, lowest priority).
+ * cvk_side_begin(main) orders everything queued on `main` so far before whatever is launched from now on on the stream it returns (NULL: error);
+ * cvk_side_join(main) orders everything launched on the side stream so far before whatever is queued on `main` from now on.  The caller keeps every
+ * buffer the side stream's launches touch alive until the join.  cvk_side_launches(): how often the side stream was handed out in this process
+ * (every group of launches that reaches it starts with one cvk_side_begin). */
+void* cvk_side_begin(void* main_stream);
+int cvk_side_join(void* main_stream);
+long cvk_side_launches(void);
 int cvk_bn_bwd_dx_e6(cvk_view dout, const float* y, int ldy, const float* scale, const float* shift, const float* mean,
                      const float* rstd, const float* dgamma, const float* dbeta, float* dy, int ld_dy, float* E6, float* part,
                      int N, int H, int W, int C, int use_batch_stats, void* stream);

@@ -85,6 +85,14 @@ SIGNATURES = {
                                   c_int, c_int, c_int, c_int, c_int, c_vp]),
     "cvk_wgradp_dy_slack": (c_int, [c_int]),
     "cvk_wgradp_gemm_sm_dy": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_size, c_vp]),
+    "cvk_wgradp_gemm_wg": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_size, c_int, c_vp]),
+    "cvk_wgradp_gemm_sm_wg": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_size, c_int, c_vp]),
+    "cvk_wgradp_gemm_sm_dy_wg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_size, c_int, c_vp]),
+    "cvk_w2d_gemm_tn_wg": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "cvk_w6_gemm_tn_wg": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "cvk_side_begin": (c_vp, [c_vp]),
+    "cvk_side_join": (c_int, [c_vp]),
+    "cvk_side_launches": (ctypes.c_long, []),
     "cvk_conv3x3_wino4f_vplanes": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "cvk_bn_bwd_dx_e6": (c_int, [View, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
                                  c_int, c_int, c_int, c_int, c_int, c_vp]),
@@ -339,7 +347,7 @@ class CvkError(RuntimeError):
 
 
 def build(verbose=False):
-    """Compile csrc/*.hip for gfx950 into lib/libcvk.so (hipcc cross-compiles without a GPU)."""
+    """Compile csrc/*.hip and csrc/side.cpp (host code) for gfx950 into lib/libcvk.so (hipcc cross-compiles without a GPU)."""
     r = subprocess.run(["make", "-C", CSRC, "-j4"], capture_output=True, text=True)
     if verbose or r.returncode != 0:
         print(r.stdout[-4000:])

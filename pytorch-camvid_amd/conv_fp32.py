@@ -252,6 +252,7 @@ class WeightGrad:
 
     def __init__(self, R, s, x, dy, gw, N, H, W, cin, k_ch, cout, ldy, flops):
         self.R, self.lib, self.s, self.x, self.dy, self.gw = R, R.lib, s, x, dy, gw
+        self.keep = []      # tensors made here that the launches still read after run() has returned (s may be the side stream)
         self.N, self.H, self.W, self.M, self.cin, self.k_ch, self.cout, self.ldy, self.flops = N, H, W, N * H * W, cin, k_ch, cout, ldy, flops
 
     def run(self, fam, tile=0, fmt=0, V=None, am_v=None, E=None, dy_e=False, Eb=None, am_dy=None):
@@ -272,6 +273,7 @@ class WeightGrad:
         f = w2fn(lib, tile, "wgrad_ksplit")(T, k_ch, C)
         if V is None:           # the forward pass ran another family: transform x now
             V = _empty(plane_elems(NX, Tp, k_ch), x.device)
+            self.keep.append(V)
             _timed(R, "k_w2d_input", 4.0 * (M + NX * T) * k_ch, lambda: check(
                 w2fn(lib, tile, "input_transform")(x.data_ptr(), V.data_ptr(), N, H, W, k_ch, s), "cvk_w2d_input_transform(wgrad)"), "byte")
         ws = R.workspace(4 * ((0 if Eb is not None else efl) + f * NX * C * k_ch), x.device)
@@ -594,6 +596,8 @@ class ConvBnRelu(Op):
         flops = 18.0 * M * C * self.cin
         if src.id in st.grad:
             raise NotImplementedError("conv data-grad must be the first writer of its input's gradient buffer")
+        # the previous block's weight-grad ran beside this block's passes; the data-grad is matrix-bound and takes the shared workspace: join first
+        R.side_join(st)
         w = st.params[4 * self.pslot]
         wc = channels_last(w)
 
@@ -629,9 +633,18 @@ class ConvBnRelu(Op):
 
     def _weight_grad(self, R, st, saved, dy, gw, E, Eb, am_dy):
         """Stage 5: the weight-grad through the route's family (WeightGrad)."""
-        src, rt = self.src, saved.rt
-        WeightGrad(R, st.stream, st.act[src.id], dy, gw, src.N, src.H, src.W, self.cin, src.ld, self.cout, pad4(self.cout),
-                   18.0 * src.M * self.cout * self.cin).run(rt.wgrad, rt.tile, rt.split, *(saved.kept or (None, None)), E, rt.bn_bwd == "dx+E4p", Eb, am_dy)
+        src, rt, s = self.src, saved.rt, st.stream
+        x = st.act[src.id]
+        side = st.side and rt.wgrad in R.side_families
+        if side:        # a leaf: nothing reads gw before backward ends -> the side stream, beside the next block's passes (joined by its data-grad)
+            s = R.side_begin(st, x, dy, E, Eb, am_dy, saved)
+        else:           # on the pass's stream: it takes the shared workspace, which an earlier block's forked weight-grad may still hold
+            R.side_join(st)
+        wg = WeightGrad(R, s, x, dy, gw, src.N, src.H, src.W, self.cin, src.ld, self.cout, pad4(self.cout), 18.0 * src.M * self.cout * self.cin)
+        wg.run(rt.wgrad, rt.tile, rt.split, *(saved.kept or (None, None)), E, rt.bn_bwd == "dx+E4p", Eb, am_dy)
+        if side:
+            st.side_keep.extend(wg.keep)                        # operands the launches above made for themselves
+            st.side_keep.append(R.workspace(0, x.device))       # their slabs / partial planes
 
     def bwd(self, R, st):
         saved = st.saved.pop(self.idx, None)

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void k_wgradp_zero_pads(float* __restrict__ P,
 template <bool VSM, bool EDY>
 __global__ __launch_bounds__(64, 2) void k_wgradp_gemm(const float* __restrict__ E6, const float* __restrict__ V6, float* __restrict__ slab,
                                                       int H, int Wtp, int Cin_ld, int Cout, long rows, int Q, int runs, int nci, int nco,
-                                                      const float* __restrict__ dy, int W) {
+                                                      const float* __restrict__ dy, int W, int njobs) {
     __shared__ __attribute__((aligned(1024))) char smem[12 * 1024];
     const unsigned smem_addr = cvk_lds_addr(smem);
     const int lane = threadIdx.x;
@@ -149,121 +149,127 @@ __global__ __launch_bounds__(64, 2) void k_wgradp_gemm(const float* __restrict__
 
     // tasks of one run are neighbours (same pixels: one L2), transform index fastest
     const int per = 6 * nci * nco;
-    const int id = cvk_xcd_remap(blockIdx.x, gridDim.x);
-    const int run = id / per, u = id - run * per;
-    const int xi = u % 6, cit = (u / 6) % nci, cot = u / (6 * nci);
-    const int qb = (int)((long)run * Q / runs), qe = (int)((long)(run + 1) * Q / runs);
-    if (qb >= qe) return;
-    const int so = Wtp >> 3;                               // strips per image
+    // job loop: the launch is one workgroup per task (gridDim.x == njobs: one pass), or a capped grid (cvk_wgradp_gemm*_wg) whose workgroups take
+    // the tasks job, job + gridDim.x, ...  A task owns its run and its slab whichever workgroup runs it: the slabs, and dw, are bitwise the same.
+    for (int job = blockIdx.x; job < njobs; job += gridDim.x) {
+        // a workgroup's next task: the previous one's LDS reads and slab stores have retired before the prologue refills the ring
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        const int id = cvk_xcd_remap(job, njobs);
+        const int run = id / per, u = id - run * per;
+        const int xi = u % 6, cit = (u / 6) % nci, cot = u / (6 * nci);
+        const int qb = (int)((long)run * Q / runs), qe = (int)((long)(run + 1) * Q / runs);
+        if (qb >= qe) continue;
+        const int so = Wtp >> 3;                               // strips per image
 
-    const bool edy = EDY && (xi == 0 || xi == 5);
-    const float* const Eb = edy ? dy + cot * 64 + (xi == 5 ? 3 * Cout : 0) : E6 + (size_t)(EDY ? xi - 1 : xi) * rows * Cout + cot * 64;
-    const int epitch = edy ? 4 * Cout : Cout;              // floats between consecutive E rows
-    const float* const Vb = V6 + (size_t)xi * rows * Cin_ld + (VSM ? (size_t)cit * 4 * rows * 16 : (size_t)cit * 64);
-    const int vpitch = VSM ? 16 : Cin_ld;                  // floats between consecutive plane rows of V
-    // a 2 KiB block = 8 plane rows x 256 B (64 channels): two DMA pieces of 4 rows; lane -> row lane / 16, 16-byte chunk lane % 16
-    const unsigned evoff = (unsigned)(((lane >> 4) * epitch + (lane & 15) * 4) * 4);
-    const unsigned vvoff = VSM ? (unsigned)((((unsigned long)((lane & 15) >> 2) * (unsigned long)rows + (lane >> 4)) * 16 + (lane & 3) * 4) * 4)
-                               : (unsigned)(((lane >> 4) * Cin_ld + (lane & 15) * 4) * 4);
-    auto block_row = [&](int strip, int yp) -> long {       // first plane row of (strip, padded image row yp)
-        const int n = strip / so, xg = strip - n * so;
-        return (long)Wtp + ((long)n * (H + 2) + yp) * Wtp + 8 * xg;
-    };
-    auto dma_V = [&](int strip, int yp) {                   // -> ring slot yp & 3
-        const float* src = Vb + (size_t)block_row(strip, yp) * vpitch;
-        const unsigned dst = smem_addr + (yp & 3) * 2048;
-        p_dma16(src, vvoff, dst);
-        p_dma16(src + 4 * (size_t)vpitch, vvoff, dst + 1024);
-    };
-    auto dma_E = [&](int strip, int yp, int slot) {
-        const int en = strip / so, exg = strip - en * so;
-        const float* src = edy ? Eb + (((size_t)en * H + (yp - 1)) * W + 32 * (size_t)exg) * Cout : Eb + (size_t)block_row(strip, yp) * Cout;
-        const unsigned dst = smem_addr + 8192 + slot * 2048;
-        p_dma16(src, evoff, dst);
-        p_dma16(src + 4 * (size_t)epitch, evoff, dst + 1024);
-    };
+        const bool edy = EDY && (xi == 0 || xi == 5);
+        const float* const Eb = edy ? dy + cot * 64 + (xi == 5 ? 3 * Cout : 0) : E6 + (size_t)(EDY ? xi - 1 : xi) * rows * Cout + cot * 64;
+        const int epitch = edy ? 4 * Cout : Cout;              // floats between consecutive E rows
+        const float* const Vb = V6 + (size_t)xi * rows * Cin_ld + (VSM ? (size_t)cit * 4 * rows * 16 : (size_t)cit * 64);
+        const int vpitch = VSM ? 16 : Cin_ld;                  // floats between consecutive plane rows of V
+        // a 2 KiB block = 8 plane rows x 256 B (64 channels): two DMA pieces of 4 rows; lane -> row lane / 16, 16-byte chunk lane % 16
+        const unsigned evoff = (unsigned)(((lane >> 4) * epitch + (lane & 15) * 4) * 4);
+        const unsigned vvoff = VSM ? (unsigned)((((unsigned long)((lane & 15) >> 2) * (unsigned long)rows + (lane >> 4)) * 16 + (lane & 3) * 4) * 4)
+                                   : (unsigned)(((lane >> 4) * Cin_ld + (lane & 15) * 4) * 4);
+        auto block_row = [&](int strip, int yp) -> long {       // first plane row of (strip, padded image row yp)
+            const int n = strip / so, xg = strip - n * so;
+            return (long)Wtp + ((long)n * (H + 2) + yp) * Wtp + 8 * xg;
+        };
+        auto dma_V = [&](int strip, int yp) {                   // -> ring slot yp & 3
+            const float* src = Vb + (size_t)block_row(strip, yp) * vpitch;
+            const unsigned dst = smem_addr + (yp & 3) * 2048;
+            p_dma16(src, vvoff, dst);
+            p_dma16(src + 4 * (size_t)vpitch, vvoff, dst + 1024);
+        };
+        auto dma_E = [&](int strip, int yp, int slot) {
+            const int en = strip / so, exg = strip - en * so;
+            const float* src = edy ? Eb + (((size_t)en * H + (yp - 1)) * W + 32 * (size_t)exg) * Cout : Eb + (size_t)block_row(strip, yp) * Cout;
+            const unsigned dst = smem_addr + 8192 + slot * 2048;
+            p_dma16(src, evoff, dst);
+            p_dma16(src + 4 * (size_t)epitch, evoff, dst + 1024);
+        };
 
-    f32x4 acc[3][16];
+        f32x4 acc[3][16];
 #pragma unroll
-    for (int r = 0; r < 3; ++r)
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int b = 0; b < 16; ++b) acc[r][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int b = 0; b < 16; ++b) acc[r][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int frag = kq * 256 + lj * 16;                    // depth row kq of a 4-row group, 16-byte chunk lj
+        const int frag = kq * 256 + lj * 16;                    // depth row kq of a 4-row group, 16-byte chunk lj
 
-    int strip = qb / H, y = qb - strip * H;                 // current step: image row y (padded row y + 1)
-    // prologue of a strip: V rows y, y+1, y+2 (padded) and E row y+1; then per step one V block + one E block arrive
-    dma_V(strip, y);
-    dma_V(strip, y + 1);
-    dma_V(strip, y + 2);
-    dma_E(strip, y + 1, 0);
-    int es = 0;
-    for (int q = qb; q < qe; ++q) {
-        // issue the next step's blocks (its V rows y+1, y+2 are here; y+3 and E row y+2 are new) — or, at the end of a strip,
-        // nothing: the next strip starts with its own prologue below
-        const bool last_in_strip = (y == H - 1);
-        const bool more = q + 1 < qe;
-        // the slot being refilled (V row y+3 -> slot (y+3)&3 = (y-1)&3) was last read in the PREVIOUS step: all of this wave's LDS
-        // reads of that step have returned (its MFMAs consumed them) -> only drain the counter before overwriting
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (more && !last_in_strip) {
-            dma_V(strip, y + 3);
-            dma_E(strip, y + 2, es ^ 1);
-            cvk_wait_vm<4>();                               // everything older than these four pieces has landed
-        } else {
-            cvk_wait_vm<0>();
+        int strip = qb / H, y = qb - strip * H;                 // current step: image row y (padded row y + 1)
+        // prologue of a strip: V rows y, y+1, y+2 (padded) and E row y+1; then per step one V block + one E block arrive
+        dma_V(strip, y);
+        dma_V(strip, y + 1);
+        dma_V(strip, y + 2);
+        dma_E(strip, y + 1, 0);
+        int es = 0;
+        for (int q = qb; q < qe; ++q) {
+            // issue the next step's blocks (its V rows y+1, y+2 are here; y+3 and E row y+2 are new) — or, at the end of a strip,
+            // nothing: the next strip starts with its own prologue below
+            const bool last_in_strip = (y == H - 1);
+            const bool more = q + 1 < qe;
+            // the slot being refilled (V row y+3 -> slot (y+3)&3 = (y-1)&3) was last read in the PREVIOUS step: all of this wave's LDS
+            // reads of that step have returned (its MFMAs consumed them) -> only drain the counter before overwriting
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (more && !last_in_strip) {
+                dma_V(strip, y + 3);
+                dma_E(strip, y + 2, es ^ 1);
+                cvk_wait_vm<4>();                               // everything older than these four pieces has landed
+            } else {
+                cvk_wait_vm<0>();
+            }
+            __builtin_amdgcn_s_setprio(1);                     // the step's 96 MFMAs ahead of the SIMD's other wave's DMA issue / counted wait (round 6:
+            const char* const eblk = smem + 8192 + es * 2048;
+            const char* const v0 = smem + ((y + 0) & 3) * 2048;      // padded rows y, y+1, y+2 = image rows y-1, y, y+1 = kernel rows 0, 1, 2
+            const char* const v1 = smem + ((y + 1) & 3) * 2048;
+            const char* const v2 = smem + ((y + 2) & 3) * 2048;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(eblk + ks * 1024 + frag);
+                const f32x4 b0 = *reinterpret_cast<const f32x4*>(v0 + ks * 1024 + frag);
+                const f32x4 b1 = *reinterpret_cast<const f32x4*>(v1 + ks * 1024 + frag);
+                const f32x4 b2 = *reinterpret_cast<const f32x4*>(v2 + ks * 1024 + frag);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        acc[0][i * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b0[j], acc[0][i * 4 + j], 0, 0, 0);
+                        acc[1][i * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b1[j], acc[1][i * 4 + j], 0, 0, 0);
+                        acc[2][i * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b2[j], acc[2][i * 4 + j], 0, 0, 0);
+                    }
+            }
+            __builtin_amdgcn_s_setprio(0);                     //  3.61 -> 3.55 ms for the eight launches, 0.808 -> 0.822 executed)
+            if (more) {
+                if (last_in_strip) {                           // next strip: refill the ring (one exposed DMA round trip per strip)
+                    ++strip;
+                    y = 0;
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    dma_V(strip, 0);
+                    dma_V(strip, 1);
+                    dma_V(strip, 2);
+                    dma_E(strip, 1, es ^ 1);
+                } else {
+                    ++y;
+                }
+                es ^= 1;
+            }
         }
-        __builtin_amdgcn_s_setprio(1);                     // the step's 96 MFMAs ahead of the SIMD's other wave's DMA issue / counted wait (round 6:
-        const char* const eblk = smem + 8192 + es * 2048;
-        const char* const v0 = smem + ((y + 0) & 3) * 2048;      // padded rows y, y+1, y+2 = image rows y-1, y, y+1 = kernel rows 0, 1, 2
-        const char* const v1 = smem + ((y + 1) & 3) * 2048;
-        const char* const v2 = smem + ((y + 2) & 3) * 2048;
+
+        // P block -> slab[run][xi][co][r * Cin_ld + ci]: row block i, register e, lane (lj, kq): co = 4 (4 kq + e) + i;
+        // column blocks j = 0..3 at lane lj: ci = 4 lj + j  -> one 16-byte store per (r, i, e)
+        const int K3 = 3 * Cin_ld;
+        float* const out = slab + ((size_t)(run * 6 + xi) * Cout + cot * 64) * K3 + cit * 64 + 4 * lj;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(eblk + ks * 1024 + frag);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(v0 + ks * 1024 + frag);
-            const f32x4 b1 = *reinterpret_cast<const f32x4*>(v1 + ks * 1024 + frag);
-            const f32x4 b2 = *reinterpret_cast<const f32x4*>(v2 + ks * 1024 + frag);
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc[0][i * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b0[j], acc[0][i * 4 + j], 0, 0, 0);
-                    acc[1][i * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b1[j], acc[1][i * 4 + j], 0, 0, 0);
-                    acc[2][i * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b2[j], acc[2][i * 4 + j], 0, 0, 0);
+                for (int e = 0; e < 4; ++e) {
+                    const int co = 4 * (4 * kq + e) + i;
+                    const f32x4 v = {acc[r][i * 4 + 0][e], acc[r][i * 4 + 1][e], acc[r][i * 4 + 2][e], acc[r][i * 4 + 3][e]};
+                    *reinterpret_cast<f32x4*>(out + (size_t)co * K3 + r * Cin_ld) = v;
                 }
-        }
-        __builtin_amdgcn_s_setprio(0);                     //  3.61 -> 3.55 ms for the eight launches, 0.808 -> 0.822 executed)
-        if (more) {
-            if (last_in_strip) {                           // next strip: refill the ring (one exposed DMA round trip per strip)
-                ++strip;
-                y = 0;
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                dma_V(strip, 0);
-                dma_V(strip, 1);
-                dma_V(strip, 2);
-                dma_E(strip, 1, es ^ 1);
-            } else {
-                ++y;
-            }
-            es ^= 1;
-        }
     }
-
-    // P block -> slab[run][xi][co][r * Cin_ld + ci]: row block i, register e, lane (lj, kq): co = 4 (4 kq + e) + i;
-    // column blocks j = 0..3 at lane lj: ci = 4 lj + j  -> one 16-byte store per (r, i, e)
-    const int K3 = 3 * Cin_ld;
-    float* const out = slab + ((size_t)(run * 6 + xi) * Cout + cot * 64) * K3 + cit * 64 + 4 * lj;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int co = 4 * (4 * kq + e) + i;
-                const f32x4 v = {acc[r][i * 4 + 0][e], acc[r][i * 4 + 1][e], acc[r][i * 4 + 2][e], acc[r][i * 4 + 3][e]};
-                *reinterpret_cast<f32x4*>(out + (size_t)co * K3 + r * Cin_ld) = v;
-            }
 }
 
 // dw[co][r][s][ci] from the slabs: P_xi = sum over runs in a FIXED order, then G^T (same arithmetic as wino4.hip's reduce).
@@ -400,8 +406,9 @@ extern "C" size_t cvk_wgradp_gemm_workspace_bytes(int N, int H, int W, int Cin_l
 
 // dw from the planes E6 [6][rows][Cout] and V6 [6][rows][Cin_ld]: GEMM into slabs (workspace) + fixed-order reduction with G^T
 static int wgradp_gemm_go(bool vsm, const float* E6, const float* V6, float* dw, int N, int H, int W, int Cin, int Cin_ld, int Cout,
-                          void* workspace, size_t workspace_bytes, void* stream, const float* dy = nullptr) {
+                          void* workspace, size_t workspace_bytes, void* stream, const float* dy = nullptr, int max_workgroups = 0) {
     CVK_CHECK_ARG(E6 && V6 && dw && workspace, "cvk_wgradp_gemm: null pointer");
+    CVK_CHECK_ARG(max_workgroups >= 0, "cvk_wgradp_gemm: max_workgroups must be >= 0");
     CVK_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cin <= Cin_ld && Cin_ld % 64 == 0 && Cout % 64 == 0 && Cout >= 64,
                   "cvk_wgradp_gemm: Cin_ld=%d and Cout=%d must be multiples of 64", Cin_ld, Cout);
     CVK_CHECK_ARG(cvk_aligned16(E6) && cvk_aligned16(V6) && cvk_aligned16(workspace), "cvk_wgradp_gemm: pointers must be 16-byte aligned");
@@ -413,12 +420,16 @@ static int wgradp_gemm_go(bool vsm, const float* E6, const float* V6, float* dw,
     hipStream_t s = (hipStream_t)stream;
     float* slab = (float*)workspace;
     const int per = 6 * p.nci * p.nco;
+    // one workgroup per task, or the cap (whole multiples of the 8 XCDs, so that a workgroup's tasks stay in one XCD's chunk of the task order)
+    const int njobs = per * p.runs;
+    int wgs = njobs;
+    if (max_workgroups > 0 && max_workgroups < njobs) wgs = max_workgroups >= 8 ? max_workgroups / 8 * 8 : max_workgroups;
     if (vsm) {
         CVK_CHECK_ARG(3L * p.rows * 64 + 4096 < (1L << 32), "cvk_wgradp_gemm_sm: %ld plane rows exceed the 32-bit lane offset of the slice-major V block", p.rows);
-        if (dy) hipLaunchKernelGGL((k_wgradp_gemm<true, true>), dim3(per * p.runs), dim3(64), 0, s, E6, V6, slab, H, p.Wtp, Cin_ld, Cout, p.rows, p.Q, p.runs, p.nci, p.nco, dy, W);
-        else hipLaunchKernelGGL((k_wgradp_gemm<true, false>), dim3(per * p.runs), dim3(64), 0, s, E6, V6, slab, H, p.Wtp, Cin_ld, Cout, p.rows, p.Q, p.runs, p.nci, p.nco, dy, W);
+        if (dy) hipLaunchKernelGGL((k_wgradp_gemm<true, true>), dim3(wgs), dim3(64), 0, s, E6, V6, slab, H, p.Wtp, Cin_ld, Cout, p.rows, p.Q, p.runs, p.nci, p.nco, dy, W, njobs);
+        else hipLaunchKernelGGL((k_wgradp_gemm<true, false>), dim3(wgs), dim3(64), 0, s, E6, V6, slab, H, p.Wtp, Cin_ld, Cout, p.rows, p.Q, p.runs, p.nci, p.nco, dy, W, njobs);
     } else {
-        hipLaunchKernelGGL((k_wgradp_gemm<false, false>), dim3(per * p.runs), dim3(64), 0, s, E6, V6, slab, H, p.Wtp, Cin_ld, Cout, p.rows, p.Q, p.runs, p.nci, p.nco, dy, W);
+        hipLaunchKernelGGL((k_wgradp_gemm<false, false>), dim3(wgs), dim3(64), 0, s, E6, V6, slab, H, p.Wtp, Cin_ld, Cout, p.rows, p.Q, p.runs, p.nci, p.nco, dy, W, njobs);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -449,6 +460,23 @@ extern "C" int cvk_wgradp_gemm_sm_dy(const float* E4p, const float* dy, const fl
     // a ragged last column group (W % 4 != 0) has E5 = 0 where dy's next row begins: only whole groups are columns of dy
     CVK_CHECK_ARG(W % 4 == 0, "cvk_wgradp_gemm_sm_dy: W=%d must be a multiple of 4 (use cvk_wgradp_gemm_sm with six planes)", W);
     return wgradp_gemm_go(true, E4p, V6sm, dw, N, H, W, Cin, Cin_ld, Cout, workspace, workspace_bytes, stream, dy);
+}
+
+// the three GEMM entry points on at most max_workgroups one-wave workgroups (0 = one per task, as above): a capped grid walks the tasks in a job
+// loop and leaves CUs to whatever runs beside it; dw is bitwise independent of the cap
+extern "C" int cvk_wgradp_gemm_wg(const float* E6, const float* V6, float* dw, int N, int H, int W, int Cin, int Cin_ld, int Cout,
+                                  void* workspace, size_t workspace_bytes, int max_workgroups, void* stream) {
+    return wgradp_gemm_go(false, E6, V6, dw, N, H, W, Cin, Cin_ld, Cout, workspace, workspace_bytes, stream, nullptr, max_workgroups);
+}
+extern "C" int cvk_wgradp_gemm_sm_wg(const float* E6, const float* V6sm, float* dw, int N, int H, int W, int Cin, int Cin_ld, int Cout,
+                                     void* workspace, size_t workspace_bytes, int max_workgroups, void* stream) {
+    return wgradp_gemm_go(true, E6, V6sm, dw, N, H, W, Cin, Cin_ld, Cout, workspace, workspace_bytes, stream, nullptr, max_workgroups);
+}
+extern "C" int cvk_wgradp_gemm_sm_dy_wg(const float* E4p, const float* dy, const float* V6sm, float* dw, int N, int H, int W, int Cin, int Cin_ld,
+                                        int Cout, void* workspace, size_t workspace_bytes, int max_workgroups, void* stream) {
+    CVK_CHECK_ARG(dy && cvk_aligned16(dy), "cvk_wgradp_gemm_sm_dy_wg: dy must be a 16-byte aligned pointer");
+    CVK_CHECK_ARG(W % 4 == 0, "cvk_wgradp_gemm_sm_dy_wg: W=%d must be a multiple of 4 (use cvk_wgradp_gemm_sm_wg with six planes)", W);
+    return wgradp_gemm_go(true, E4p, V6sm, dw, N, H, W, Cin, Cin_ld, Cout, workspace, workspace_bytes, stream, dy, max_workgroups);
 }
 
 // one call: E6_pre NULL (the E planes are built from dy in the workspace) or the six planes written by cvk_wgradp_zero_pads +

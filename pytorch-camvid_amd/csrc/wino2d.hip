@@ -764,7 +764,7 @@ __global__ __launch_bounds__(256) void k_w2d_dy_both(const float* __restrict__ D
 template <int ABL = 0>       // ABL (experiments build, WRONG results): 1 no barrier, 2 no DMA in the loop, 3 no stores, 4 no LDS reads
 __global__ __launch_bounds__(256, 2) void k_w2d_gemm_tn(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                        float* __restrict__ D, int Kp, int Mm, int Nn, int tilesM, int tilesN,
-                                                       int f, int NX) {
+                                                       int f, int NX, int njobs) {
     constexpr int STAGE = 32 * 256 * 4, PPW = 8;        // 32 KiB per stage: depth rows [k][A 128 | B 128]... kept as two 16 KiB halves
     __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
     const unsigned smem_addr = cvk_lds_addr(smem);
@@ -772,83 +772,92 @@ __global__ __launch_bounds__(256, 2) void k_w2d_gemm_tn(const float* __restrict_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;
-    const int id = cvk_xcd_remap(blockIdx.x, gridDim.x);
-    const int part = id % f, tile = id / f;
-    const int tn = tile % tilesN, tm = (tile / tilesN) % tilesM, xi = tile / (tilesN * tilesM);
-    const int nK = Kp / 32, kb = part * nK / f, ke = (part + 1) * nK / f;
-    A += (size_t)xi * Kp * lda + tm * 128;
-    B += (size_t)xi * Kp * ldb + tn * 128;
-    D += ((size_t)part * NX + xi) * Mm * Nn;
+    const float* const A0 = A;
+    const float* const B0 = B;
+    float* const D0 = D;
+    // job loop: one workgroup per (tile, depth range) (gridDim.x == njobs: one pass), or a capped grid (cvk_w2d_gemm_tn_wg / cvk_w6_gemm_tn_wg) whose
+    // workgroups take the jobs job, job + gridDim.x, ...  A job owns its depth range and its plane of D whichever workgroup runs it: bitwise the same.
+    for (int job = blockIdx.x; job < njobs; job += gridDim.x) {
+        // a workgroup's next job: every wave has read the last slice of the previous one before the first DMA overwrites stage 0
+        if (job != (int)blockIdx.x) cvk_lds_retire_barrier();
+        const int id = cvk_xcd_remap(job, njobs);
+        const int part = id % f, tile = id / f;
+        const int tn = tile % tilesN, tm = (tile / tilesN) % tilesM, xi = tile / (tilesN * tilesM);
+        const int nK = Kp / 32, kb = part * nK / f, ke = (part + 1) * nK / f;
+        A = A0 + (size_t)xi * Kp * lda + tm * 128;
+        B = B0 + (size_t)xi * Kp * ldb + tn * 128;
+        D = D0 + ((size_t)part * NX + xi) * Mm * Nn;
 
-    // DMA: piece p = wave*8 + q; pieces 0..15 = A depth rows 2p, 2p+1 (LDS bytes [0, 16 KiB)), 16..31 = B (LDS [16, 32 KiB));
-    // lane = depth row lane/32 of the pair, floats 4*(lane%32) .. +3 of the 128.  Columns beyond the matrix read the
-    // neighbouring bytes of the plane (in bounds: the planes carry a slack row); their products are never stored.
-    const float* src[PPW];
-    int sstep[PPW];
+        // DMA: piece p = wave*8 + q; pieces 0..15 = A depth rows 2p, 2p+1 (LDS bytes [0, 16 KiB)), 16..31 = B (LDS [16, 32 KiB));
+        // lane = depth row lane/32 of the pair, floats 4*(lane%32) .. +3 of the 128.  Columns beyond the matrix read the
+        // neighbouring bytes of the plane (in bounds: the planes carry a slack row); their products are never stored.
+        const float* src[PPW];
+        int sstep[PPW];
 #pragma unroll
-    for (int q = 0; q < PPW; ++q) {
-        const int p = wave * PPW + q, pa = p & 15;
-        const int krow = pa * 2 + (lane >> 5), col = (lane & 31) * 4;
-        src[q] = p < 16 ? A + (size_t)krow * lda + col : B + (size_t)krow * ldb + col;
-        sstep[q] = p < 16 ? 32 * lda : 32 * ldb;
-    }
-    auto issue = [&](int ks, int buf) {
+        for (int q = 0; q < PPW; ++q) {
+            const int p = wave * PPW + q, pa = p & 15;
+            const int krow = pa * 2 + (lane >> 5), col = (lane & 31) * 4;
+            src[q] = p < 16 ? A + (size_t)krow * lda + col : B + (size_t)krow * ldb + col;
+            sstep[q] = p < 16 ? 32 * lda : 32 * ldb;
+        }
+        auto issue = [&](int ks, int buf) {
 #pragma unroll
-        for (int q = 0; q < PPW; ++q) cvk_dma16(src[q] + (size_t)ks * sstep[q], smem_addr + buf * STAGE + (wave * PPW + q) * 1024);
-    };
-    f32x16 acc[2][2];
+            for (int q = 0; q < PPW; ++q) cvk_dma16(src[q] + (size_t)ks * sstep[q], smem_addr + buf * STAGE + (wave * PPW + q) * 1024);
+        };
+        f32x16 acc[2][2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    const int a_off = h * 512 + (wm * 64 + 2 * r) * 4, b_off = 16384 + h * 512 + (wn * 64 + 2 * r) * 4;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
+                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        const int a_off = h * 512 + (wm * 64 + 2 * r) * 4, b_off = 16384 + h * 512 + (wn * 64 + 2 * r) * 4;
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-    if (kb < ke) issue(kb, 0);
-    int buf = 0;
-    for (int ks = kb; ks < ke; ++ks) {
-        if (ABL != 2) cvk_wait_vm<0>();
-        if (ABL != 1) cvk_lds_retire_barrier();
-        const int ksn = ABL == 5 ? kb : min(ks + 1, ke - 1);          // ABL 5: every DMA re-reads the first slice (cache-hot)
-        if (!CVK_TN_SPLIT_ISSUE && ABL != 2) issue(ksn, buf ^ 1);
-        __builtin_amdgcn_s_setprio(1);                   // MFMA phase of the slice (as k_w2d_gemm, round 6: 3.21 -> 3.14 ms for the 13 launches, 0.761 -> 0.778)
-        const char* const st = smem + buf * STAGE;
+        if (kb < ke) issue(kb, 0);
+        int buf = 0;
+        for (int ks = kb; ks < ke; ++ks) {
+            if (ABL != 2) cvk_wait_vm<0>();
+            if (ABL != 1) cvk_lds_retire_barrier();
+            const int ksn = ABL == 5 ? kb : min(ks + 1, ke - 1);          // ABL 5: every DMA re-reads the first slice (cache-hot)
+            if (!CVK_TN_SPLIT_ISSUE && ABL != 2) issue(ksn, buf ^ 1);
+            __builtin_amdgcn_s_setprio(1);                   // MFMA phase of the slice (as k_w2d_gemm, round 6: 3.21 -> 3.14 ms for the 13 launches, 0.761 -> 0.778)
+            const char* const st = smem + buf * STAGE;
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            f32x2 a, b;
-            if (ABL == 4) { a = f32x2{acc[0][0][0], 1.f}; b = f32x2{acc[0][0][1], 2.f}; asm volatile("" : "+v"(a), "+v"(b)); }
-            else {
-                a = *reinterpret_cast<const f32x2*>(st + a_off + q * 1024);
-                b = *reinterpret_cast<const f32x2*>(st + b_off + q * 1024);
+            for (int q = 0; q < 16; ++q) {
+                f32x2 a, b;
+                if (ABL == 4) { a = f32x2{acc[0][0][0], 1.f}; b = f32x2{acc[0][0][1], 2.f}; asm volatile("" : "+v"(a), "+v"(b)); }
+                else {
+                    a = *reinterpret_cast<const f32x2*>(st + a_off + q * 1024);
+                    b = *reinterpret_cast<const f32x2*>(st + b_off + q * 1024);
+                }
+                if (CVK_TN_SPLIT_ISSUE && ABL != 2 && (q == 0 || q == 4)) {          // the next slice's DMA pieces behind the first fragment reads, in two halves (as k_w2d_gemm)
+#pragma unroll
+                    for (int p = (q ? PPW / 2 : 0); p < (q ? PPW : PPW / 2); ++p)
+                        cvk_dma16(src[p] + (size_t)ksn * sstep[p], smem_addr + (buf ^ 1) * STAGE + (wave * PPW + p) * 1024);
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
             }
-            if (CVK_TN_SPLIT_ISSUE && ABL != 2 && (q == 0 || q == 4)) {          // the next slice's DMA pieces behind the first fragment reads, in two halves (as k_w2d_gemm)
-#pragma unroll
-                for (int p = (q ? PPW / 2 : 0); p < (q ? PPW : PPW / 2); ++p)
-                    cvk_dma16(src[p] + (size_t)ksn * sstep[p], smem_addr + (buf ^ 1) * STAGE + (wave * PPW + p) * 1024);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_s_setprio(0);
+            buf ^= 1;
         }
-        __builtin_amdgcn_s_setprio(0);
-        buf ^= 1;
+        cvk_wait_vm<0>();
+        const int col = tn * 128 + wn * 64 + 2 * r;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = tm * 128 + wm * 64 + 2 * ((e & 3) + 8 * (e >> 2) + 4 * h) + i;
+                if (ABL == 3 ? (row < Mm && acc[i][0][e] == 123.456f) : row < Mm) {
+                    float* const dp = D + (size_t)row * Nn + col;
+                    if (col + 1 < Nn) { const f32x2 v = {acc[i][0][e], acc[i][1][e]}; *reinterpret_cast<f32x2*>(dp) = v; }
+                    else if (col < Nn) dp[0] = acc[i][0][e];
+                }
+            }
     }
-    cvk_wait_vm<0>();
-    const int col = tn * 128 + wn * 64 + 2 * r;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int row = tm * 128 + wm * 64 + 2 * ((e & 3) + 8 * (e >> 2) + 4 * h) + i;
-            if (ABL == 3 ? (row < Mm && acc[i][0][e] == 123.456f) : row < Mm) {
-                float* const dp = D + (size_t)row * Nn + col;
-                if (col + 1 < Nn) { const f32x2 v = {acc[i][0][e], acc[i][1][e]}; *reinterpret_cast<f32x2*>(dp) = v; }
-                else if (col < Nn) dp[0] = acc[i][0][e];
-            }
-        }
 }
 
 // dw [Co][3][3][Ci] = G^T (sum of the f planes of P [NX][Co][Cip]) G; one thread = one (co, ci)
@@ -1181,13 +1190,19 @@ static int w2i_dy_transform(int mt, const char* who, const float* dy, int ld_dy,
     CVK_LAUNCH_RETURN(who);
 }
 
-static int w2i_gemm_tn(int mt, const char* who, const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, void* stream) {
+// max_workgroups > 0 caps the grid (whole multiples of the 8 XCDs): the workgroups then walk the (tile, depth range) jobs in a loop
+static int w2i_gemm_tn(int mt, const char* who, const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, void* stream,
+                       int max_workgroups = 0) {
     CVK_CHECK_ARG(E && V && P && T > 0 && Cin_pad > 0 && Cin_pad % 4 == 0 && Cout > 0 && Cout % 4 == 0, "%s: bad arguments", who);
     CVK_CHECK_ARG(cvk_aligned16(E) && cvk_aligned16(V) && cvk_aligned16(P), "%s: pointers must be 16-byte aligned", who);
+    CVK_CHECK_ARG(max_workgroups >= 0, "%s: max_workgroups must be >= 0", who);
     const int nx = w2_nx(mt);
     const W2WPlan p = plan_w2d_wgrad(nx, T, Cin_pad, Cout);
+    const int njobs = nx * p.tilesM * p.tilesN * p.f;
+    int wgs = njobs;
+    if (max_workgroups > 0 && max_workgroups < njobs) wgs = max_workgroups >= 8 ? max_workgroups / 8 * 8 : max_workgroups;
 #ifdef CVK_EXPERIMENTS
-#define CVK_TN_ABL_GO(A_) hipLaunchKernelGGL(k_w2d_gemm_tn<A_>, dim3(nx * p.tilesM * p.tilesN * p.f), dim3(256), 0, (hipStream_t)stream, E, Cout, V, Cin_pad, P, p.Tpad, Cout, Cin_pad, p.tilesM, p.tilesN, p.f, nx)
+#define CVK_TN_ABL_GO(A_) hipLaunchKernelGGL(k_w2d_gemm_tn<A_>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, E, Cout, V, Cin_pad, P, p.Tpad, Cout, Cin_pad, p.tilesM, p.tilesN, p.f, nx, njobs)
     switch (cvk_knob("CVK_W2D_TN_ABL", 0)) {
         case 1: CVK_TN_ABL_GO(1); CVK_LAUNCH_RETURN(who);
         case 2: CVK_TN_ABL_GO(2); CVK_LAUNCH_RETURN(who);
@@ -1197,8 +1212,8 @@ static int w2i_gemm_tn(int mt, const char* who, const float* E, const float* V, 
         default: break;
     }
 #endif
-    hipLaunchKernelGGL(k_w2d_gemm_tn<0>, dim3(nx * p.tilesM * p.tilesN * p.f), dim3(256), 0, (hipStream_t)stream, E, Cout, V, Cin_pad, P, p.Tpad,
-                       Cout, Cin_pad, p.tilesM, p.tilesN, p.f, nx);
+    hipLaunchKernelGGL(k_w2d_gemm_tn<0>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, E, Cout, V, Cin_pad, P, p.Tpad,
+                       Cout, Cin_pad, p.tilesM, p.tilesN, p.f, nx, njobs);
     CVK_LAUNCH_RETURN(who);
 }
 
@@ -1502,6 +1517,10 @@ extern "C" int cvk_w2d_dy_transform_both(const float* dy, int ld_dy, float* Vp, 
 extern "C" int cvk_w2d_gemm_tn(const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, void* stream) {
     return w2i_gemm_tn(4, "cvk_w2d_gemm_tn", E, V, P, T, Cin_pad, Cout, stream);
 }
+// ... on at most max_workgroups workgroups (0 = one per job, as above); P is bitwise independent of the cap
+extern "C" int cvk_w2d_gemm_tn_wg(const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, int max_workgroups, void* stream) {
+    return w2i_gemm_tn(4, "cvk_w2d_gemm_tn_wg", E, V, P, T, Cin_pad, Cout, stream, max_workgroups);
+}
 extern "C" int cvk_w2d_wgrad_output(const float* P, float* dw, int T, int Cin, int Cin_pad, int Cout, void* stream) {
     return w2i_wgrad_output(4, "cvk_w2d_wgrad_output", P, dw, T, Cin, Cin_pad, Cout, stream);
 }
@@ -1558,6 +1577,9 @@ extern "C" int cvk_w6_dy_transform_both(const float* dy, int ld_dy, float* Vp, f
 }
 extern "C" int cvk_w6_gemm_tn(const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, void* stream) {
     return w2i_gemm_tn(6, "cvk_w6_gemm_tn", E, V, P, T, Cin_pad, Cout, stream);
+}
+extern "C" int cvk_w6_gemm_tn_wg(const float* E, const float* V, float* P, int T, int Cin_pad, int Cout, int max_workgroups, void* stream) {
+    return w2i_gemm_tn(6, "cvk_w6_gemm_tn_wg", E, V, P, T, Cin_pad, Cout, stream, max_workgroups);
 }
 extern "C" int cvk_w6_wgrad_output(const float* P, float* dw, int T, int Cin, int Cin_pad, int Cout, void* stream) {
     return w2i_wgrad_output(6, "cvk_w6_wgrad_output", P, dw, T, Cin, Cin_pad, Cout, stream);

@@ -97,6 +97,9 @@ class RunState:
         self.amax_spare = []        # zeroed amax blocks for the backward pass (|dy| maxima)
         self.scratch = []           # dgamma / dbeta temporaries of blocks with frozen BatchNorm parameters (ConvBnRelu._grad_targets)
         self.fold = None            # the gradient-accumulation fold of this backward pass (accumulate.GradAccumulator), or None
+        self.side = False           # this backward pass forks its weight-grads onto the side stream (Runner.side_allowed)
+        self.side_open = False      # ... and has launches there that no join covers yet
+        self.side_keep = []         # what those launches touch, referenced until the join (Runner.side_begin)
 
 
 def _empty(n, dev, dtype=_F32):
@@ -138,6 +141,11 @@ WGRADP_DEFAULT = {"0": False, "1": True, "always": "always"}[os.environ.get("CVK
 # Round 6: the fused F(4,3) forward launch also writes the weight-grad's V planes (cvk_conv3x3_wino4f_vplanes, slice-major) — the plane GEMM then
 # takes every F(4,3) weight-grad, not only the 64-input-channel ones, and the x -> V pass is gone.  "0" off, "1" on.
 VPLANES_DEFAULT = os.environ.get("CVK_VPLANES", "1") != "0"
+# CVK_WGRAD_SIDE: "1" runs the fp32 weight-grads on the library's side stream beside the next block's passes, "0" keeps the single-stream order
+WGRAD_SIDE_DEFAULT = "1"
+# ... for the weight-grad families (route.ConvRoute.wgrad) measured to gain from it together (the plane GEMM, the transposed 2-D GEMM,
+# the thin stem / head kernels); the families nobody measured (w4, w2, direct, the split-operand GEMMs) stay on the pass's stream
+WGRAD_SIDE_FAMILIES = frozenset(("wgradp", "wgradp_sm", "w2d", "thin"))
 
 
 def amax_blocks(lib, n, dev):
@@ -614,6 +622,33 @@ class Runner:
         self._pass_token = 0        # 0: eval / no-grad passes (entries shared across calls); > 0: the training pass being executed
         self._passes = 0
         self.wcache_builds = 0      # derived tensors built since creation (tests / diagnostics)
+        # fp32 weight-grads on the library's side stream, beside the next block's bandwidth-bound passes (csrc/side.cpp): the weight-grad
+        # families (route.ConvRoute.wgrad) that gained in the probe (tools/bench_wgrad_side.py); the others stay on the pass's stream
+        self.wgrad_side = os.environ.get("CVK_WGRAD_SIDE", WGRAD_SIDE_DEFAULT) != "0"
+        self.side_families = WGRAD_SIDE_FAMILIES
+
+    def side_allowed(self, fold):
+        """This backward pass may fork weight-grads onto the side stream: switched on, and none of the cases that keep the single-stream order:
+        a stream capture, a gradient synchroniser attached (its buckets leave in layer order), gradient accumulation, a recording profile."""
+        return (self.wgrad_side and not self.bf16 and self.grad_sync is None and self.accumulator is None and fold is None and PROF is None
+                and not torch.cuda.is_current_stream_capturing())
+
+    def side_begin(self, st, *keep):
+        """Fork: the side stream, ordered behind everything queued on the pass's stream so far.  `keep`: what the side launches read or write;
+        referenced until the join, so that the caching allocator cannot hand their blocks to work on the pass's stream meanwhile."""
+        s = self.lib.cvk_side_begin(st.stream)
+        if not s:
+            check(-1, "cvk_side_begin")
+        st.side_keep.extend(k for k in keep if k is not None)
+        st.side_open = True
+        return s
+
+    def side_join(self, st):
+        """Join: whatever is queued on the pass's stream from now on runs after the side stream's launches (no-op when nothing was forked)."""
+        if st.side_open:
+            check(self.lib.cvk_side_join(st.stream), "cvk_side_join")
+            st.side_open = False
+            st.side_keep.clear()
 
     def persistent_wgs(self):
         """Workgroup cap of the persistent (one-workgroup-per-CU) kernels: 0 = every CU.  Under data-parallel training
@@ -898,11 +933,17 @@ class Runner:
         fold = st.fold = self.accumulator.open_pass(st, plan, total) if self.accumulator is not None else None
         st.sync = self.begin_sync(st, plan, fold)
         self._collectives_in_flight = False
+        st.side = self.side_allowed(fold)
         st.grad[plan.output.buf.id] = self.import_nchw(st, gout, plan.output.buf, _F32, zero_pad=True)
-        for op in reversed(plan.ops):
-            _CUR_OP[0] = (op.idx, "bwd")
-            op.bwd(self, st)
-        _CUR_OP[0] = None
+        try:
+            for op in reversed(plan.ops):
+                _CUR_OP[0] = (op.idx, "bwd")
+                op.bwd(self, st)
+        finally:
+            _CUR_OP[0] = None
+            # the last blocks' weight-grads: before anything reads the flat gradient buffer — and, when an op raised, before the pass's
+            # tensors are released while side-stream kernels may still read them
+            self.side_join(st)
         self.flush_colsums(st)
         self.flush_wreduces(st)
         if fold is not None and st.sync is None:        # with a synchroniser every bucket was folded before it left
