@@ -1,59 +1,26 @@
-// loss_eval_optim.hip — per-pixel softmax cross-entropy (nn.CrossEntropyLoss(): reference train.py:105,130-131),
-// the evaluation reductions (argmax train.py:191; intersection/union histograms utils.py:162-190) and a flat fused
-// AdamW step (torch.optim.AdamW: train.py:100,133).  NHWC logits rows are [M][ld] with C valid classes; one thread
-// per pixel reads its C contiguous logits (a wave covers 64*ld contiguous floats: fully used cache lines).
+// loss_eval_optim.hip: the six losses (softmax cross-entropy: nn.CrossEntropyLoss(), reference train.py:105,130-131; OHEM; Lovász;
+// boundary; focal + Dice; distillation), the two inference merges and image ingest: kernels in the namespace below, their entry
+// points after it, then the library-wide pieces.  What the losses share is in loss_rows.h.
+// Every other subject is a self-contained header (own includes, own namespace; kernels, argument checks and entry points together)
+// compiled as part of this translation unit:
+//   loss_rows.h     workgroup geometry, chunk staging and weighted pixel terms of the losses; k_lv_clear
+//   edt.h           exact Euclidean distance transform of label maps
+//   boundary_f1.h   boundary F1 contour map and counts
+//   surface_dist.h  Hausdorff, HD95 and ASSD (uses edt.h and boundary_f1.h)
+//   eval_meters.h   class histogram, arg-max, confusion counts
+//   optim_flat.h    AdamW, momentum SGD, the per-iteration log row
+//   grad_flat.h     global-norm clipping and gradient accumulation
+// A new subject gets a header of that kind, not lines here.
 #include "cvk_common.h"
+#include "loss_rows.h"
+#include "edt.h"
+#include "boundary_f1.h"
+#include "surface_dist.h"
+#include "eval_meters.h"
+#include "optim_flat.h"
+#include "grad_flat.h"
 
 namespace {
-
-constexpr int CE_ROWS_PER_BLOCK = 1024;  // 4 chunks of 256 pixels per workgroup
-constexpr int CE_CHUNK = 256;            // one pixel per thread per chunk
-constexpr int CE_MAX_LD = 63;            // widest pixel row staged through LDS ((ld + 1) * 1 KiB of dynamic LDS <= 64 KiB)
-
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// Global <-> LDS movement of one chunk: the chunk's CE_CHUNK pixel rows are `n` contiguous floats in HBM (rows of ld
-// floats); every wave instruction moves 64 consecutive float4 (1 KiB, fully used lines).  In LDS a pixel row has pitch
-// ld + 1 floats, so the per-thread row walk below (thread = pixel, column c) is bank-conflict free.
-__device__ __forceinline__ void ce_chunk_load(const float* __restrict__ g, float* lds, int n, int ld) {
-    const int pitch = ld + 1;
-    if ((ld & 3) == 0 && ((uintptr_t)g & 15u) == 0) {
-        for (int f = threadIdx.x * 4; f < n; f += CE_CHUNK * 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(g + f);
-            const int r = f / ld, c = f - r * ld;                  // ld % 4 == 0: the four floats share a row
-            float* q = lds + r * pitch + c;
-            q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3];
-        }
-    } else {
-        for (int f = threadIdx.x; f < n; f += CE_CHUNK) {
-            const int r = f / ld;
-            lds[r * pitch + (f - r * ld)] = g[f];
-        }
-    }
-}
-
-__device__ __forceinline__ void ce_chunk_store(float* __restrict__ g, const float* lds, int n, int ld) {
-    const int pitch = ld + 1;
-    if ((ld & 3) == 0 && ((uintptr_t)g & 15u) == 0) {
-        for (int f = threadIdx.x * 4; f < n; f += CE_CHUNK * 4) {
-            const int r = f / ld, c = f - r * ld;
-            const float* q = lds + r * pitch + c;
-            const f32x4 v = {q[0], q[1], q[2], q[3]};
-            *reinterpret_cast<f32x4*>(g + f) = v;
-        }
-    } else {
-        for (int f = threadIdx.x; f < n; f += CE_CHUNK) {
-            const int r = f / ld;
-            g[f] = lds[r * pitch + (f - r * ld)];
-        }
-    }
-}
 
 // part[b] = sum of -log softmax(logits)[target] over the block's valid pixels, part[nb + b] = number of valid pixels,
 // part[2 nb + b] = number of pixels whose target is neither in [0, C) nor ignore_index.
@@ -220,43 +187,7 @@ __global__ __launch_bounds__(256) void k_ce_bwd_rows(const float* __restrict__ l
 // ---- cross-entropy with class weights, label smoothing and a reduction (cvk_softmax_ce_fwd_ex / _bwd_ex) ----------------------
 // Same memory scheme as k_ce_fwd / k_ce_bwd (256 pixel rows staged per chunk, one thread per pixel; a thread walks its row in
 // global memory when ld > CE_MAX_LD); the weight vector (all ones when absent) is staged in LDS once per workgroup.
-// For a pixel with target t, lse = log sum exp and W = sum_c w[c]:
-//   loss = (1 - eps) w[t] (lse - x[t]) + (eps / C) sum_c w[c] (lse - x[c])
-//   dx_k = g (softmax_k ((1 - eps) w[t] + (eps / C) W) - (1 - eps) w[t] [k = t] - (eps / C) w[k])
-constexpr int CE_EX_MAX_C = 128;
-
-__device__ __forceinline__ void ce_ex_stage_w(const float* __restrict__ w, float* s_w, int C) {
-    for (int c = threadIdx.x; c < C; c += blockDim.x) s_w[c] = w != nullptr ? w[c] : 1.f;
-}
-
-__device__ __forceinline__ float ce_ex_pixel_loss(const float* p, int C, int t, const float* s_w, float eps) {
-    float mx = p[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(p[c] - mx);
-    const float lse = mx + logf(se);
-    float l = (1.f - eps) * s_w[t] * (lse - p[t]);
-    if (eps != 0.f) {
-        float sm = 0.f;
-        for (int c = 0; c < C; ++c) sm += s_w[c] * (lse - p[c]);
-        l += (eps / (float)C) * sm;
-    }
-    return l;
-}
-
-// o may alias p (every column is read before it is written); columns [C, ld_o) are zeroed
-__device__ __forceinline__ void ce_ex_pixel_grad(const float* p, float* o, int ld_o, int C, int t, const float* s_w, float eps,
-                                                 float wsum, float g) {
-    float mx = p[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(p[c] - mx);
-    const float inv = 1.f / se;
-    const float es = eps / (float)C, wt = (1.f - eps) * s_w[t];
-    const float a = wt + es * wsum;
-    for (int c = 0; c < C; ++c) o[c] = (expf(p[c] - mx) * inv * a - (c == t ? wt : 0.f) - es * s_w[c]) * g;
-    for (int c = C; c < ld_o; ++c) o[c] = 0.f;
-}
+// The pixel terms (CE_EX_MAX_C, ce_ex_stage_w, ce_ex_pixel_loss, ce_ex_pixel_grad) are in loss_rows.h: the other losses use them too.
 
 // part[b], part[nb + b], part[2 nb + b], part[3 nb + b] = the block's loss sum, divisor sum (w[t] over the valid pixels), valid
 // pixels, out-of-range targets.  loss_px (nullable): per-pixel loss, 0 at ignored pixels and NaN at out-of-range targets.
@@ -814,11 +745,6 @@ __device__ __forceinline__ unsigned lv_block_sum(unsigned v, unsigned* s_wave) {
     return tot;
 }
 
-__global__ __launch_bounds__(256) void k_lv_clear(unsigned* __restrict__ ctr, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) ctr[i] = 0u;
-}
-
 // grid (ceil(P / 1024), S): a work-group stays inside one segment.  ctr: G[S C] | V[S] | out-of-range targets.
 // cepart[b], cepart[nbe + b]: the work-group's cross-entropy sum and divisor sum (want_ce only).
 template <bool STAGED>
@@ -1213,191 +1139,6 @@ __global__ __launch_bounds__(256) void k_lv_bwd(const float* __restrict__ logits
                 }
             }
         }
-    }
-}
-
-// ---- exact Euclidean distance transform of a label batch (cvk_edt_squared / cvk_edt_signed; definitions in include/cvk.h) ------------
-// A pixel's category is its class, or void (-1) when its label is ignore_index or outside [0, C).  Two passes, everything per image:
-//   k_edt_cols  work-group = (image, 16 columns), their categories staged in LDS; thread = (column, channel), one walk down the column
-//               and one up.  Channel c < C: the vertical distance to the nearest pixel of class c in the column; channel C: to the
-//               nearest pixel of the column whose category differs from this pixel's (0xFFFF: none).  uint16 [N][H][W][C + 1].  ORs the
-//               image's class-presence word (and its void flag) with an integer atomic.
-//   k_edt_rows  work-group = one row (n, y): the row's column distances (transposed to [C + 1][W]) and categories sit in LDS; thread =
-//               x, and per channel the outward search of edt_row_search: x - k and x + k for k = 0, 1, ... until k^2 >= best.  Every
-//               x' with |x - x'| < k has been visited and every other one costs at least k^2, so the minimum is exact.  A class absent
-//               from the image is skipped (-1).  For the distance to another category the column term of x' is channel C where x' has
-//               this pixel's category and 0 elsewhere.  The integers of a 256-pixel tile are put in LDS in [x][c] order and stored as
-//               contiguous words: int32 (SIGNED = false) or phi with sign and correctly rounded root applied (SIGNED = true).
-// LDS of k_edt_cols: 16 H B (5.6 KiB at H = 360).  LDS of k_edt_rows: 2 W (C + 2) B of rows + 1 KiB x (C | 1) of output tile (12.6 + 13 KiB at W = 480, C = 12); a row that would not
-// fit 64 KiB keeps only the categories (2 W B) in LDS and searches the column distances in global memory.
-constexpr int EDT_MAX_C = 32;
-constexpr int EDT_MAX_H = 65534;                   // a vertical distance is at most H - 1 < 0xFFFF
-constexpr unsigned EDT_NONE = 0xFFFFu;
-constexpr unsigned EDT_INF = 0xFFFFFFFFu;
-constexpr int EDT_MAX_D2 = 1 << 24;                // (H - 1)^2 + (W - 1)^2 below this: every squared distance converts to fp32 exactly
-constexpr size_t EDT_LDS_LIMIT = 64 * 1024;
-
-__host__ __device__ __forceinline__ int edt_category(long t, int C, int ignore_index) {
-    return t >= 0 && t < C && t != (long)ignore_index ? (int)t : -1;
-}
-
-// The correctly rounded fp32 root of an integer below 2^24 (exact in fp32).  sqrtf is IEEE-rounded in this build (no fast-math flag);
-// __fsqrt_rn is not used: without OCML_BASIC_ROUNDED_OPERATIONS the toolchain defines it as the native approximation.
-__device__ __forceinline__ float edt_root(int d2) { return __builtin_sqrtf((float)d2); }
-
-// mask[2 n] = classes present in image n (bit c), mask[2 n + 1] = 1 when it has a void pixel; cleared before the launch.
-// Work-group = (image, strip of EDT_COL_TX columns): the strip's categories, int8 [H][EDT_COL_TX] (H <= 4096: at most 64 KiB), are staged in
-// LDS by all threads; then a thread owns one (column, channel) of the strip, channel fastest, and walks the column in LDS down and up;
-// the map is stored on the way down and read back (its own stores) and lowered on the way up.
-constexpr int EDT_COL_TX = 16, EDT_COL_BATCH = 8;
-
-__global__ __launch_bounds__(256) void k_edt_cols(const int64_t* __restrict__ lab, unsigned short* __restrict__ col,
-                                                 unsigned* __restrict__ mask, int strips, int H, int W, int C, int ignore_index) {
-    extern __shared__ signed char edt_cat[];
-    const int K = C + 1;
-    const int n = blockIdx.x / strips, x0 = (blockIdx.x - n * strips) * EDT_COL_TX;
-    const int64_t* L = lab + (size_t)n * H * W;
-    for (int i = threadIdx.x; i < H * EDT_COL_TX; i += 256) {
-        const int y = i / EDT_COL_TX, x = x0 + (i - y * EDT_COL_TX);
-        edt_cat[i] = (signed char)(x < W ? edt_category((long)L[(size_t)y * W + x], C, ignore_index) : -1);
-    }
-    __syncthreads();
-    const size_t os = (size_t)W * K;
-    for (int item = threadIdx.x; item < EDT_COL_TX * K; item += 256) {
-        const int xx = item / K, c = item - xx * K;
-        if (x0 + xx >= W) continue;
-        const signed char* s = edt_cat + xx;
-        unsigned short* o = col + ((size_t)n * H * W + x0 + xx) * K + c;
-        // Two walks with no data-dependent inner loop (lanes of a wave hold different classes): down, storing the distance to the nearest
-        // match above; then up in batches of EDT_COL_BATCH rows, whose stored values are fetched together before they are lowered.
-        if (c < C) {
-            int last = -1;
-            for (int y = 0; y < H; ++y) {
-                if (s[y * EDT_COL_TX] == c) last = y;
-                o[y * os] = (unsigned short)(last < 0 ? EDT_NONE : (unsigned)(y - last));
-            }
-            int next = -1;
-            for (int y1 = H; y1 > 0; y1 -= EDT_COL_BATCH) {
-                unsigned v[EDT_COL_BATCH];
-#pragma unroll
-                for (int j = 0; j < EDT_COL_BATCH; ++j) v[j] = y1 - 1 - j >= 0 ? (unsigned)o[(y1 - 1 - j) * os] : 0u;
-#pragma unroll
-                for (int j = 0; j < EDT_COL_BATCH; ++j) {
-                    const int y = y1 - 1 - j;
-                    if (y < 0) break;
-                    if (s[y * EDT_COL_TX] == c) next = y;
-                    if (next >= 0 && (unsigned)(next - y) < v[j]) o[y * os] = (unsigned short)(next - y);
-                }
-            }
-            if (last >= 0) atomicOr(&mask[2 * n], 1u << c);
-        } else {
-            bool any_void = false;
-            int prev = 0, start = 0;                       // the run of equal categories that holds y starts at `start`
-            for (int y = 0; y < H; ++y) {
-                const int k = s[y * EDT_COL_TX];
-                any_void |= k < 0;
-                if (y > 0 && k != prev) start = y;
-                prev = k;
-                o[y * os] = (unsigned short)(start > 0 ? (unsigned)(y - start + 1) : EDT_NONE);
-            }
-            int end = H - 1;                               // ... and ends at `end`
-            for (int y1 = H; y1 > 0; y1 -= EDT_COL_BATCH) {
-                unsigned v[EDT_COL_BATCH];
-#pragma unroll
-                for (int j = 0; j < EDT_COL_BATCH; ++j) v[j] = y1 - 1 - j >= 0 ? (unsigned)o[(y1 - 1 - j) * os] : 0u;
-#pragma unroll
-                for (int j = 0; j < EDT_COL_BATCH; ++j) {
-                    const int y = y1 - 1 - j;
-                    if (y < 0) break;
-                    const int k = s[y * EDT_COL_TX];
-                    if (y < H - 1 && k != prev) end = y;
-                    prev = k;
-                    if (end < H - 1 && (unsigned)(end + 1 - y) < v[j]) o[y * os] = (unsigned short)(end + 1 - y);
-                }
-            }
-            if (any_void) atomicOr(&mask[2 * n + 1], 1u);
-        }
-    }
-}
-
-// min over x' of (x - x')^2 + g(x')^2, g(x') = col[x' * cstride] (0xFFFF: no such pixel in that column); OTHER: g(x') = 0 where
-// cat[x'] != t.  -1 when no column has a finite term.  The one producer of the integers that both outputs are made of.
-template <bool OTHER>
-__device__ __forceinline__ int edt_row_search(const unsigned short* col, int cstride, const short* cat, int t, int x, int W) {
-    unsigned best = EDT_INF;
-    const int kmax = max(x, W - 1 - x);
-    for (int k = 0; k <= kmax; ++k) {
-        const unsigned k2 = (unsigned)k * (unsigned)k;
-        if (k2 >= best) break;
-        const int xl = x - k, xr = x + k;
-        if (xl >= 0) {
-            unsigned v = col[(size_t)xl * cstride];
-            if (OTHER && cat[xl] != t) v = 0u;
-            if (v != EDT_NONE) best = min(best, k2 + v * v);
-        }
-        if (k > 0 && xr < W) {
-            unsigned v = col[(size_t)xr * cstride];
-            if (OTHER && cat[xr] != t) v = 0u;
-            if (v != EDT_NONE) best = min(best, k2 + v * v);
-        }
-    }
-    return best == EDT_INF ? -1 : (int)best;
-}
-
-// grid N * H.  SIGNED: phi [M][C] floats; else to_class [M][C] and to_other [M] int32.
-template <bool STAGED, bool SIGNED>
-__global__ __launch_bounds__(256) void k_edt_rows(const int64_t* __restrict__ lab, const unsigned short* __restrict__ col,
-                                                 const unsigned* __restrict__ mask, int* __restrict__ to_class,
-                                                 int* __restrict__ to_other, float* __restrict__ phi, int H, int W, int C,
-                                                 int ignore_index) {
-    extern __shared__ unsigned char edt_lds[];
-    const int K = C + 1, pitch = C | 1;
-    const size_t row = blockIdx.x;
-    const int n = (int)(row / H);
-    short* s_cat = reinterpret_cast<short*>(edt_lds);
-    unsigned short* s_col = reinterpret_cast<unsigned short*>(edt_lds) + W;                // [K][W], STAGED only
-    const size_t rows_bytes = ((size_t)2 * W * (STAGED ? K + 1 : 1) + 3) & ~(size_t)3;
-    int* s_out = reinterpret_cast<int*>(edt_lds + rows_bytes);                             // [256][pitch]
-    const unsigned short* g = col + row * W * K;
-    for (int x = threadIdx.x; x < W; x += 256) s_cat[x] = (short)edt_category((long)lab[row * W + x], C, ignore_index);
-    if (STAGED)
-        for (int i = threadIdx.x; i < W * K; i += 256) {
-            const int x = i / K, c = i - x * K;
-            s_col[c * W + x] = g[i];
-        }
-    const unsigned present = mask[2 * n];
-    const bool several = __popc(present) + (int)(mask[2 * n + 1] & 1u) > 1;
-    __syncthreads();
-    for (int x0 = 0; x0 < W; x0 += 256) {
-        const int x = x0 + threadIdx.x;
-        int other = -1;
-        if (x < W) {
-            const int t = s_cat[x];
-            if (several)
-                other = STAGED ? edt_row_search<true>(s_col + C * W, 1, s_cat, t, x, W) : edt_row_search<true>(g + C, K, s_cat, t, x, W);
-            for (int c = 0; c < C; ++c) {
-                int d = -1;
-                if (((present >> c) & 1u) && !(SIGNED && c == t))
-                    d = STAGED ? edt_row_search<false>(s_col + c * W, 1, s_cat, t, x, W) : edt_row_search<false>(g + c, K, s_cat, t, x, W);
-                if (SIGNED) {
-                    float v;
-                    if (c == t) v = other < 0 ? 0.f : -(edt_root(other) - 1.f);
-                    else        v = d < 0 ? 0.f : edt_root(d);
-                    s_out[threadIdx.x * pitch + c] = __builtin_bit_cast(int, v);
-                } else {
-                    s_out[threadIdx.x * pitch + c] = d;
-                }
-            }
-            if (!SIGNED) to_other[row * W + x] = other;
-        }
-        __syncthreads();
-        const int words = min(256, W - x0) * C;
-        int* dst = (SIGNED ? reinterpret_cast<int*>(phi) : to_class) + (row * W + x0) * C;
-        for (int j = threadIdx.x; j < words; j += 256) {
-            const int px = j / C;
-            dst[j] = s_out[px * pitch + (j - px * C)];
-        }
-        __syncthreads();
     }
 }
 
@@ -2125,67 +1866,6 @@ __global__ __launch_bounds__(256) void k_kd_bwd_rows(const float* __restrict__ s
     }
 }
 
-// Class statistics of label masks: one workgroup per mask.  Every wave counts into its own LDS histogram (integer atomics:
-// exact, so the totals do not depend on the order); the folded per-mask counts go to the device counters with 64-bit integer
-// atomics: hist[c] += pixels of class c, hist[C + c] += the mask's counted pixels if c occurs in it, hist[2C] += labels outside
-// [0, C) that are not ignore_index.
-constexpr int HIST_THREADS = 1024, HIST_WAVES = HIST_THREADS / 64, HIST_MAX_C = 256;
-
-__global__ __launch_bounds__(HIST_THREADS) void k_class_hist(const void* __restrict__ masks, int mask_bytes, int64_t hw, int C,
-                                                             int ignore_index, unsigned long long* __restrict__ hist) {
-    __shared__ unsigned int h[HIST_WAVES * HIST_MAX_C];
-    __shared__ unsigned long long cnt[HIST_MAX_C];
-    __shared__ unsigned long long s_tot;
-    __shared__ unsigned int s_bad;
-    for (int i = threadIdx.x; i < HIST_WAVES * C; i += HIST_THREADS) h[i] = 0u;
-    if (threadIdx.x == 0) s_bad = 0u;
-    __syncthreads();
-    unsigned int* mine = h + (threadIdx.x >> 6) * C;
-    const size_t base = (size_t)blockIdx.x * hw;
-    unsigned int bad = 0u;
-    for (int64_t i = threadIdx.x; i < hw; i += HIST_THREADS) {
-        const long l = mask_bytes == 1 ? (long)static_cast<const uint8_t*>(masks)[base + i]
-                                       : (long)static_cast<const int64_t*>(masks)[base + i];
-        if (l == (long)ignore_index) continue;
-        if (l >= 0 && l < C) atomicAdd(&mine[l], 1u);
-        else ++bad;
-    }
-    if (bad) atomicAdd(&s_bad, bad);
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += HIST_THREADS) {
-        unsigned long long n = 0;
-        for (int k = 0; k < HIST_WAVES; ++k) n += h[k * C + c];
-        cnt[c] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long tot = 0;
-        for (int c = 0; c < C; ++c) tot += cnt[c];
-        s_tot = tot;
-        if (s_bad) atomicAdd(&hist[2 * C], (unsigned long long)s_bad);
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += HIST_THREADS) {
-        if (cnt[c]) {
-            atomicAdd(&hist[c], cnt[c]);
-            atomicAdd(&hist[C + c], s_tot);
-        }
-    }
-}
-
-__global__ void k_argmax(const float* __restrict__ logits, int ld, int64_t* __restrict__ out, int M, int C) {
-    for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
-        const float* p = logits + (size_t)m * ld;
-        float best = p[0];
-        int bi = 0;
-        for (int c = 1; c < C; ++c) {
-            const float v = p[c];
-            if (v > best || (v != v && best == best)) { best = v; bi = c; }  // first max; NaN wins like ATen
-        }
-        out[m] = bi;
-    }
-}
-
 // ---- multi-scale / flip test-time augmentation (cvk_tta_accumulate, cvk_tta_resize_input) ---------------------------------------
 // One launch per view folds that view's logits into the [M][C] probability accumulator: a workgroup owns CE_CHUNK consecutive
 // accumulator rows (a contiguous span of 256 C floats), one thread per pixel.  The accumulator side is staged through LDS exactly
@@ -2431,588 +2111,6 @@ __global__ __launch_bounds__(CE_CHUNK) void k_window_merge(const float* __restri
     }
 }
 
-__global__ __launch_bounds__(256) void k_confusion(const int64_t* __restrict__ pred, const int64_t* __restrict__ label,
-                                                  unsigned long long* __restrict__ hist, int M, int K, int ignore) {
-    extern __shared__ unsigned int h[];  // [3][K]
-    for (int i = threadIdx.x; i < 3 * K; i += blockDim.x) h[i] = 0;
-    __syncthreads();
-    for (long m = (long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long)gridDim.x * blockDim.x) {
-        const int64_t l = label[m], p = pred[m];  // compared as 64-bit values: 2^32 + c is no class and 2^32 + ignore not the ignore index
-        if (l == (int64_t)ignore) continue;
-        if (p >= 0 && p < K) {
-            atomicAdd(&h[K + p], 1u);
-            if (p == l) atomicAdd(&h[p], 1u);
-        }
-        if (l >= 0 && l < K) atomicAdd(&h[2 * K + l], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 3 * K; i += blockDim.x)
-        if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
-}
-
-// ---- boundary F1: per-image, per-class contour counts (cvk_boundary_counts, cvk_boundary_map; the rule is in include/cvk.h) ----------
-// A pixel of a map becomes one byte: its class (< BF_MAX_K), BF_OTHER for a non-void value that is no class (outside [0, K), or
-// ignore_index predicted where the label is not void: different from every class, no boundary of its own), BF_VOID for a void pixel or
-// a position outside the image (never different, no boundary).  Values are compared as 64-bit integers before they become a byte, so
-// 2^32 + c is no class, and nothing is ever indexed by a value that is not a class.
-constexpr int BF_MAX_K = 32, BF_MAX_R2 = 256, BF_MAX_R = 16;
-constexpr int BF_TH = 32, BF_TW = 64, BF_THREADS = 256;  // interior tile of a workgroup: 2048 pixels, 8 per thread
-constexpr int BF_STAGE_BATCH = 8;
-constexpr unsigned char BF_OTHER = 254, BF_VOID = 255, BF_NONE = 255;
-
-__device__ __forceinline__ unsigned char bf_code(int64_t x, int64_t void_src, int K, int ignore) {
-    if (void_src == (int64_t)ignore) return BF_VOID;
-    return (x >= 0 && x < K && x != (int64_t)ignore) ? (unsigned char)x : BF_OTHER;
-}
-
-// the boundary byte of a pixel with code v from its 4-neighbours' codes: v when v is a class and a non-void neighbour differs
-__device__ __forceinline__ unsigned char bf_boundary(unsigned char v, unsigned char up, unsigned char down, unsigned char left,
-                                                     unsigned char right) {
-    if (v >= BF_MAX_K) return BF_NONE;
-    const bool diff = (up != BF_VOID && up != v) || (down != BF_VOID && down != v) || (left != BF_VOID && left != v) ||
-                      (right != BF_VOID && right != v);
-    return diff ? v : BF_NONE;
-}
-
-// code of position (y, x) of image n, BF_VOID outside the image
-__device__ __forceinline__ unsigned char bf_code_at(const int64_t* __restrict__ map, const int64_t* __restrict__ void_from, int n, int y,
-                                                    int x, int H, int W, int K, int ignore) {
-    if (y < 0 || y >= H || x < 0 || x >= W) return BF_VOID;
-    const size_t i = ((size_t)n * H + y) * W + x;
-    return bf_code(map[i], void_from[i], K, ignore);
-}
-
-__global__ __launch_bounds__(256) void k_boundary_map(const int64_t* __restrict__ map, const int64_t* __restrict__ void_from,
-                                                     unsigned char* __restrict__ out, int N, int H, int W, int K, int ignore) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;     // the grid covers N * H * W < 2^31 with less than 256 to spare
-    if (m < N * H * W) {
-        const int x = m % W, r = m / W, y = r % H, n = r / H;
-        const unsigned char v = bf_code(map[m], void_from[m], K, ignore);
-        unsigned char b = BF_NONE;
-        if (v < BF_MAX_K)
-            b = bf_boundary(v, bf_code_at(map, void_from, n, y - 1, x, H, W, K, ignore), bf_code_at(map, void_from, n, y + 1, x, H, W, K, ignore),
-                            bf_code_at(map, void_from, n, y, x - 1, H, W, K, ignore), bf_code_at(map, void_from, n, y, x + 1, H, W, K, ignore));
-        out[m] = b;
-    }
-}
-
-// 0x80 in every byte of v that is zero, exactly (no carry runs from one byte into the next)
-__device__ __forceinline__ unsigned int bf_zero_bytes(unsigned int v) {
-    return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v | 0x7F7F7F7Fu);
-}
-
-// whether columns [x0, x1] of a boundary row (4-byte aligned, pitch a multiple of 4) hold byte c: aligned 32-bit LDS reads, four
-// positions per compare, the bytes of the first and last word outside the span masked off
-__device__ __forceinline__ bool bf_row_has(const unsigned char* row, int x0, int x1, unsigned char c) {
-    const unsigned int* w = reinterpret_cast<const unsigned int*>(row);
-    const unsigned int pat = 0x01010101u * c;
-    const int d0 = x0 >> 2, d1 = x1 >> 2;
-    for (int d = d0; d <= d1; ++d) {
-        unsigned int z = bf_zero_bytes(w[d] ^ pat);
-        if (d == d0) z &= 0xFFFFFFFFu << (8 * (x0 & 3));
-        if (d == d1) z &= 0xFFFFFFFFu >> (8 * (3 - (x1 & 3)));
-        if (z) return true;
-    }
-    return false;
-}
-
-// rows of the disc are searched nearest first, in up to BF_LEVELS bands of |dy|: 0..2, 3..5, 6..10, 11..16
-constexpr int BF_LEVELS = 4;
-__device__ __forceinline__ int bf_level_end(int lvl) { return lvl == 0 ? 2 : lvl == 1 ? 5 : lvl == 2 ? 10 : BF_MAX_R; }
-
-// One workgroup per BF_TH x BF_TW tile of one image (grid: tiles of an image x N, flattened).  With R = isqrt(r2):
-//   1. the codes of both maps for the tile plus a halo of R + 1 go to LDS (the only global reads);
-//   2. both boundary byte maps for the tile plus a halo of R are derived from them (bf_boundary, as k_boundary_map);
-//   3. the interior pixels that carry a boundary are counted (rows 0 / 2) and queued;
-//   4. the queue is served by all threads in turn: an entry searches the disc in the other map's boundary bytes row by row, nearest rows
-//      first, four positions per LDS read (bf_row_has), and leaves at the first hit (rows 1 / 3).  Positions outside the image are
-//      BF_NONE there, so an offset never leaves the image.  The rows come in bands; the entries a band leaves unmatched are queued again
-//      for the next one, so that the few entries that walk the whole disc fill whole waves instead of holding 63 finished lanes each.
-// Counters are 32-bit LDS atomics (at most 2048 per workgroup), flushed by 64-bit global atomics where non-zero: integer sums, exact in
-// any order.  LDS bytes: 2 (BF_TH + 2R + 2)(BF_TW + 2R + 2) codes + 2 (BF_TH + 2R) pitch boundary bytes, pitch = BF_TW + 2R rounded up
-// to 4 (cvk_boundary_counts sizes them), + two 8 KiB queues + tables: 29 KiB at R = 4, 42 KiB at R = 16.
-__global__ __launch_bounds__(BF_THREADS) void k_boundary_counts(const int64_t* __restrict__ pred, const int64_t* __restrict__ label,
-                                                               unsigned long long* __restrict__ counts, int H, int W, int K, int ignore,
-                                                               int r2, int R, int tiles_x, int tiles) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char bf_lds[];
-    __shared__ unsigned int s_cnt[4 * BF_MAX_K];
-    __shared__ unsigned short s_queue[2][2 * BF_TH * BF_TW];  // entry: interior pixel index | map << 11 (0: prediction, 1: label)
-    __shared__ int s_half[BF_MAX_R + 1];                      // s_half[|dy|] = isqrt(r2 - dy * dy)
-    __shared__ unsigned int s_nq[BF_LEVELS + 1];              // entries queued for each band
-    const int n = blockIdx.x / tiles, t = blockIdx.x - n * tiles;
-    const int ty0 = (t / tiles_x) * BF_TH, tx0 = (t % tiles_x) * BF_TW;
-    const int CH = BF_TH + 2 * R + 2, CW = BF_TW + 2 * R + 2, BH = BF_TH + 2 * R, BW = BF_TW + 2 * R, BP = (BW + 3) & ~3;
-    const int csize = (CH * CW + 3) & ~3;
-    unsigned char* cP = bf_lds;
-    unsigned char* cG = cP + csize;
-    unsigned char* bP = cG + csize;                           // 4-byte aligned, as every row of pitch BP is
-    unsigned char* bG = bP + BH * BP;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 4 * BF_MAX_K; i += BF_THREADS) s_cnt[i] = 0;
-    if (tid <= BF_LEVELS) s_nq[tid] = 0;
-    if (tid <= R) {
-        const int rem = r2 - tid * tid;
-        int w = 0;
-        while ((w + 1) * (w + 1) <= rem) ++w;
-        s_half[tid] = w;
-    }
-    // BF_STAGE_BATCH independent loads of each map are in flight per thread before the first is used (the loop is latency bound
-    // otherwise); a position outside the image reads nothing and takes the label ignore, which is BF_VOID in both maps
-    for (int base = 0; base < CH * CW; base += BF_THREADS * BF_STAGE_BATCH) {
-        int64_t l[BF_STAGE_BATCH], p[BF_STAGE_BATCH];
-#pragma unroll
-        for (int u = 0; u < BF_STAGE_BATCH; ++u) {
-            const int i = base + u * BF_THREADS + tid, cy = i / CW, cx = i - cy * CW;
-            const int y = ty0 - R - 1 + cy, x = tx0 - R - 1 + cx;
-            const bool in = i < CH * CW && y >= 0 && y < H && x >= 0 && x < W;
-            const size_t m = ((size_t)n * H + y) * W + x;
-            l[u] = in ? label[m] : (int64_t)ignore;
-            p[u] = in ? pred[m] : (int64_t)ignore;
-        }
-#pragma unroll
-        for (int u = 0; u < BF_STAGE_BATCH; ++u) {
-            const int i = base + u * BF_THREADS + tid;
-            if (i < CH * CW) {
-                cP[i] = bf_code(p[u], l[u], K, ignore);
-                cG[i] = bf_code(l[u], l[u], K, ignore);
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < BH * BP; i += BF_THREADS) {
-        const int by = i / BP, bx = i - by * BP;
-        unsigned char p = BF_NONE, g = BF_NONE;               // the pitch's padding columns hold no boundary
-        if (bx < BW) {
-            const int c = (by + 1) * CW + bx + 1;
-            p = bf_boundary(cP[c], cP[c - CW], cP[c + CW], cP[c - 1], cP[c + 1]);
-            g = bf_boundary(cG[c], cG[c - CW], cG[c + CW], cG[c - 1], cG[c + 1]);
-        }
-        bP[i] = p;
-        bG[i] = g;
-    }
-    __syncthreads();
-    for (int i = tid; i < BF_TH * BF_TW; i += BF_THREADS) {
-        const int b = ((i / BF_TW) + R) * BP + (i % BF_TW) + R;
-        const unsigned char p = bP[b], g = bG[b];
-        if (p != BF_NONE) {
-            atomicAdd(&s_cnt[p], 1u);
-            s_queue[0][atomicAdd(&s_nq[0], 1u)] = (unsigned short)i;
-        }
-        if (g != BF_NONE) {
-            atomicAdd(&s_cnt[2 * K + g], 1u);
-            s_queue[0][atomicAdd(&s_nq[0], 1u)] = (unsigned short)(i | (1 << 11));
-        }
-    }
-    __syncthreads();
-    for (int lvl = 0, a_lo = 0; lvl < BF_LEVELS; ++lvl) {     // uniform: every thread walks the same bands
-        const int a_hi = min(R, bf_level_end(lvl));
-        const bool more = a_hi < R;
-        const int nq = (int)s_nq[lvl];
-        const unsigned short* qin = s_queue[lvl & 1];
-        unsigned short* qout = s_queue[(lvl + 1) & 1];
-        for (int q = tid; q < nq; q += BF_THREADS) {
-            const int e = qin[q], which = e >> 11, i = e & (BF_TH * BF_TW - 1);
-            const int by = (i / BF_TW) + R, bx = (i % BF_TW) + R;
-            const unsigned char c = (which ? bG : bP)[by * BP + bx];
-            const unsigned char* other = which ? bP : bG;
-            bool hit = false;
-            for (int k = a_lo ? 2 * a_lo - 1 : 0; k <= 2 * a_hi && !hit; ++k) {
-                const int a = (k + 1) >> 1, dy = (k & 1) ? -a : a, w = s_half[a];
-                hit = bf_row_has(other + (by + dy) * BP, bx - w, bx + w, c);
-            }
-            if (hit) atomicAdd(&s_cnt[(which ? 3 : 1) * K + c], 1u);
-            else if (more) qout[atomicAdd(&s_nq[lvl + 1], 1u)] = (unsigned short)e;
-        }
-        __syncthreads();
-        if (!more || s_nq[lvl + 1] == 0) break;               // uniform: read after the barrier, written before it
-        a_lo = a_hi + 1;
-    }
-    for (int i = tid; i < 4 * K; i += BF_THREADS)
-        if (s_cnt[i]) atomicAdd(&counts[(size_t)n * 4 * K + i], (unsigned long long)s_cnt[i]);
-}
-
-// One AdamW element update (torch.optim.AdamW, decoupled weight decay).  Shared by k_adamw (scalars as kernel arguments) and the
-// range-table kernel: one expression list, so they cannot round differently.
-// coef scales the gradient on its way in (global-norm clipping: the record of cvk_grad_norm); an unclipped step passes 1.f, and
-// x * 1.f is x.
-// Returns the parameter value it stored, for the EMA that goes on with it in the register.
-__device__ __forceinline__ float adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                              float* __restrict__ v, int64_t i, float lr, float b1, float b2, float eps, float wd,
-                                              float bc1, float bc2_sqrt, float coef) {
-    const float gi = g[i] * coef;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
-    p[i] = pi;
-    return pi;
-}
-
-__global__ void k_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                        int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, 1.f);
-}
-
-// AdamW over a range table (cvk_adamw_step_ranges, cvk_adamw_step_ranges_dev): workgroup b serves the range whose block0 is the last one
-// <= b (a uniform binary search over the table) and strides over it with that range's workgroups.  Ranges outside [0, n) or with a record
-// index outside [0, nhyper) are skipped (cvk_adamw_plan_ranges refuses them on the host).  One kernel template, two compile-time choices:
-//   SRC: where the hyper records and the EMA's alpha come from.  AdamwArgSource: kernel arguments (eager).  AdamwDevSource: device memory
-//        the host rewrites between graph replays (uniform loads, once per thread, before the loop).
-//   EMA: the thread that has stored an element's new value moves the average towards it, ema += alpha * (p_new - ema), from the
-//        register: param is not read again, and elements outside every range are not touched in ema either.  Without it `ema` and
-//        alpha are never read and the loop is the plain update.
-// `clip` is the {total_norm, clip_coef} record of cvk_grad_norm, read once per thread, or null: coefficient 1.f.
-struct AdamwArgRecords {
-    cvk_adamw_hyper r[CVK_ADAMW_ARG_RECORDS];
-};
-
-struct AdamwArgSource {
-    AdamwArgRecords recs;
-    float a;
-    __device__ __forceinline__ const cvk_adamw_hyper* records() const { return recs.r; }
-    __device__ __forceinline__ float alpha() const { return a; }
-};
-
-struct AdamwDevSource {
-    const cvk_adamw_hyper* recs;
-    const float* a;
-    __device__ __forceinline__ const cvk_adamw_hyper* records() const { return recs; }
-    __device__ __forceinline__ float alpha() const { return *a; }
-};
-
-template <class SRC, bool EMA>
-__global__ void k_adamw_ranges(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                               float* __restrict__ ema, int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, const SRC src,
-                               int nhyper, const float* __restrict__ clip) {
-    const int b = blockIdx.x;
-    int lo = 0, hi = nr - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (rt[mid].block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    const int64_t off = rt[lo].offset, len = rt[lo].length;
-    const int hx = rt[lo].hyper, b0 = rt[lo].block0;
-    const int nb = (lo + 1 < nr ? rt[lo + 1].block0 : (int)gridDim.x) - b0;
-    if (off < 0 || len <= 0 || off + len > n || hx < 0 || hx >= nhyper || nb <= 0 || b < b0) return;
-    const cvk_adamw_hyper* __restrict__ hyper = src.records();
-    const float lr = hyper[hx].lr, b1 = hyper[hx].beta1, b2 = hyper[hx].beta2, eps = hyper[hx].eps, wd = hyper[hx].weight_decay;
-    const float bc1 = hyper[hx].bc1, bc2_sqrt = hyper[hx].bc2_sqrt;
-    const float coef = clip != nullptr ? clip[1] : 1.f;
-    float alpha = 0.f;
-    if constexpr (EMA) alpha = src.alpha();
-    for (int64_t i = off + (int64_t)(b - b0) * blockDim.x + threadIdx.x; i < off + len; i += (int64_t)nb * blockDim.x) {
-        const float pi = adamw_update(p, g, m, v, i, lr, b1, b2, eps, wd, bc1, bc2_sqrt, coef);
-        if constexpr (EMA) {
-            const float e = ema[i];
-            ema[i] = e + alpha * (pi - e);
-        }
-    }
-}
-
-// One momentum-SGD element update (torch.optim.SGD: coupled L2 weight decay, dampening, Nesterov), in fp32.  Shared by the eager and the
-// captured instantiation of k_sgd_ranges: one expression list, so they cannot round differently (the convention of adamw_update).
-// coef scales the gradient on its way in, as in adamw_update.  `mom` (momentum != 0 under MOM): the buffer is in use; `first` is torch's
-// `momentum_buffer is None`: the buffer becomes the (decayed) gradient itself, not (1 - dampening) * d.  Without `mom`, buf is neither
-// read nor written.  Returns the parameter value it stored, for the EMA that goes on with it in the register.
-__device__ __forceinline__ float sgd_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t i,
-                                            float lr, float momentum, float dampening, float wd, bool nesterov, bool first, bool mom,
-                                            float coef) {
-    const float pi = p[i];
-    float d = g[i] * coef;
-    d = d + wd * pi;
-    if (mom) {
-        const float b = first ? d : momentum * buf[i] + (1.f - dampening) * d;
-        buf[i] = b;
-        d = nesterov ? d + momentum * b : b;
-    }
-    const float pn = pi - lr * d;
-    p[i] = pn;
-    return pn;
-}
-
-// Momentum SGD over a range table (cvk_sgd_step_ranges, cvk_sgd_step_ranges_dev): the table, the workgroup-to-range search, the record
-// sources (a cvk_sgd_hyper has the size of a cvk_adamw_hyper and travels in the same slots), the clip record and the EMA tail are those of
-// k_adamw_ranges.  MOM false: no record uses a momentum buffer; `buf` is never read or written (3 passes over the range instead of 5).
-// Under MOM a record whose momentum is 0 still leaves its ranges of `buf` alone, as torch keeps no buffer for such a group.
-static_assert(sizeof(cvk_sgd_hyper) == sizeof(cvk_adamw_hyper), "cvk_sgd_hyper travels in the record slots of cvk_adamw_hyper");
-
-template <class SRC, bool EMA, bool MOM>
-__global__ void k_sgd_ranges(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, float* __restrict__ ema,
-                             int64_t n, const cvk_adamw_range* __restrict__ rt, int nr, const SRC src, int nhyper,
-                             const float* __restrict__ clip) {
-    const int b = blockIdx.x;
-    int lo = 0, hi = nr - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (rt[mid].block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    const int64_t off = rt[lo].offset, len = rt[lo].length;
-    const int hx = rt[lo].hyper, b0 = rt[lo].block0;
-    const int nb = (lo + 1 < nr ? rt[lo + 1].block0 : (int)gridDim.x) - b0;
-    if (off < 0 || len <= 0 || off + len > n || hx < 0 || hx >= nhyper || nb <= 0 || b < b0) return;
-    const cvk_sgd_hyper* __restrict__ hyper = reinterpret_cast<const cvk_sgd_hyper*>(src.records());
-    const float lr = hyper[hx].lr, momentum = hyper[hx].momentum, dampening = hyper[hx].dampening, wd = hyper[hx].weight_decay;
-    const bool nesterov = hyper[hx].nesterov != 0.f, first = hyper[hx].first != 0.f;
-    const bool mom = MOM && momentum != 0.f;
-    const float coef = clip != nullptr ? clip[1] : 1.f;
-    float alpha = 0.f;
-    if constexpr (EMA) alpha = src.alpha();
-    for (int64_t i = off + (int64_t)(b - b0) * blockDim.x + threadIdx.x; i < off + len; i += (int64_t)nb * blockDim.x) {
-        const float pi = sgd_update(p, g, buf, i, lr, momentum, dampening, wd, nesterov, first, mom, coef);
-        if constexpr (EMA) {
-            const float e = ema[i];
-            ema[i] = e + alpha * (pi - e);
-        }
-    }
-}
-
-// One row [loss, lr, beta1, ||gw||_2, ||gb||_2] of the per-iteration log, with `rec` (the {total_norm, clip_coef} record of cvk_grad_norm)
-// followed by its two floats, into ring[(*counter % capacity) * cols ..] (cols = 5 or 7), then ++*counter.
-// One workgroup of 256 threads: thread t sums the squares of elements t, t + 256, ... in fp64, then a fixed tree over LDS.
-constexpr int STEP_LOG_THREADS = 256;
-
-__device__ __forceinline__ double block_sum_sq_f64(const float* __restrict__ x, int n, double* red) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += STEP_LOG_THREADS) {
-        const double xi = (double)x[i];
-        s += xi * xi;
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = STEP_LOG_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();                                               // red is reused by the next reduction
-    return r;
-}
-
-__global__ __launch_bounds__(STEP_LOG_THREADS) void k_step_log(const float* __restrict__ loss, const cvk_adamw_hyper* __restrict__ hyper,
-                                                               const float* __restrict__ gw, int nw, const float* __restrict__ gb, int nb,
-                                                               const float* __restrict__ rec, float* __restrict__ ring, int capacity,
-                                                               int64_t* __restrict__ counter) {
-    __shared__ double red[STEP_LOG_THREADS];
-    const double sw = block_sum_sq_f64(gw, nw, red);
-    const double sb = block_sum_sq_f64(gb, nb, red);
-    if (threadIdx.x == 0) {
-        const int64_t c = *counter;
-        float* row = ring + (c % capacity) * (rec != nullptr ? 7 : 5);
-        row[0] = *loss;
-        row[1] = hyper->lr;
-        row[2] = hyper->beta1;
-        row[3] = (float)sqrt(sw);
-        row[4] = (float)sqrt(sb);
-        if (rec != nullptr) {
-            row[5] = rec[0];
-            row[6] = rec[1];
-        }
-        *counter = c + 1;
-    }
-}
-
-// ---- global-norm gradient clipping (cvk_grad_norm, cvk_grad_scale) -----------------------------------------------------------------
-// torch.nn.utils.clip_grad_norm_'s coefficient in fp32: clamp(max_norm / (total_norm + 1e-6), max=1).  `c > 1 ? 1 : c` keeps a NaN
-// (fminf would return 1).  One expression for the host entry point and the finish kernel (IEEE division on both sides).
-__host__ __device__ __forceinline__ float clip_coef_f32(float max_norm, float total_norm) {
-    const float c = max_norm / (total_norm + 1e-6f);
-    return c > 1.f ? 1.f : c;
-}
-
-constexpr int NORM_THREADS = 256;
-constexpr int NORM_UNROLL = 4;                  // independent 16-byte loads per lane and trip
-constexpr int NORM_MAX_BLOCKS = 2048;           // 8 workgroups per CU: a grid-stride streaming read
-
-// The workgroup's segment (uniform binary search over block0, as k_adamw_ranges) and its place among the segment's workgroups.
-// False when the table entry is unusable (cvk_grad_norm_plan refuses such a table on the host).
-__device__ __forceinline__ bool norm_segment_of(const cvk_norm_segment* __restrict__ st, int ns, int64_t n, int64_t* off, int64_t* len,
-                                                int* rank, int* nb) {
-    const int b = blockIdx.x;
-    int lo = 0, hi = ns - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (st[mid].block0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    *off = st[lo].offset;
-    *len = st[lo].length;
-    const int b0 = st[lo].block0;
-    *nb = (lo + 1 < ns ? st[lo + 1].block0 : (int)gridDim.x) - b0;
-    *rank = b - b0;
-    return *off >= 0 && *len > 0 && *off + *len <= n && *nb > 0 && b >= b0;
-}
-
-// A segment as [head scalars][16-byte vectors][tail scalars]: head = the elements before the first 16-byte boundary of g + off.
-__device__ __forceinline__ int64_t norm_head(const float* g, int64_t off, int64_t len) {
-    const int64_t h = (4 - (int64_t)((reinterpret_cast<uintptr_t>(g + off) >> 2) & 3)) & 3;
-    return h < len ? h : len;
-}
-
-// NaN-keeping maximum: once m is a NaN it stays one (torch.linalg.vector_norm(inf) of a buffer with a NaN is NaN).
-__device__ __forceinline__ double norm_max(double m, double x) { return (x > m || x != x) ? x : m; }
-
-template <bool INF>
-__device__ __forceinline__ double norm_acc(double a, float x) {
-    const double d = (double)x;
-    return INF ? norm_max(a, fabs(d)) : fma(d, d, a);
-}
-
-template <bool INF>
-__device__ __forceinline__ double norm_join(double a, double b) { return INF ? norm_max(a, b) : a + b; }
-
-// A fixed tree: xor-shuffles inside each wave, then the 4 wave results in order.  Every thread of the workgroup calls it.
-template <bool INF>
-__device__ __forceinline__ double norm_block_reduce(double a, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a = norm_join<INF>(a, __shfl_xor(a, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-    __syncthreads();
-    return norm_join<INF>(norm_join<INF>(red[0], red[1]), norm_join<INF>(red[2], red[3]));
-}
-
-template <bool INF>
-__global__ __launch_bounds__(NORM_THREADS) void k_grad_norm_partial(const float* __restrict__ g, int64_t n,
-                                                                    const cvk_norm_segment* __restrict__ st, int ns,
-                                                                    double* __restrict__ partials) {
-    __shared__ double red[NORM_THREADS / 64];
-    int64_t off, len;
-    int rank, nb;
-    const bool ok = norm_segment_of(st, ns, n, &off, &len, &rank, &nb);      // uniform
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    if (ok) {
-        const int64_t head = norm_head(g, off, len);
-        const int64_t nvec = (len - head) >> 2;
-        const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + off + head);
-        const int64_t tid = (int64_t)rank * NORM_THREADS + threadIdx.x, stride = (int64_t)nb * NORM_THREADS;
-        int64_t i = tid;
-        for (; i + (NORM_UNROLL - 1) * stride < nvec; i += NORM_UNROLL * stride) {
-            f32x4 x[NORM_UNROLL];
-#pragma unroll
-            for (int u = 0; u < NORM_UNROLL; ++u) x[u] = gv[i + u * stride];
-#pragma unroll
-            for (int u = 0; u < NORM_UNROLL; ++u) {
-                a0 = norm_acc<INF>(a0, x[u][0]);
-                a1 = norm_acc<INF>(a1, x[u][1]);
-                a2 = norm_acc<INF>(a2, x[u][2]);
-                a3 = norm_acc<INF>(a3, x[u][3]);
-            }
-        }
-        for (; i < nvec; i += stride) {
-            const f32x4 x = gv[i];
-            a0 = norm_acc<INF>(a0, x[0]);
-            a1 = norm_acc<INF>(a1, x[1]);
-            a2 = norm_acc<INF>(a2, x[2]);
-            a3 = norm_acc<INF>(a3, x[3]);
-        }
-        // the at most 3 + 3 elements around the vectors: the segment's first thread
-        if (tid == 0) {
-            for (int64_t j = 0; j < head; ++j) a0 = norm_acc<INF>(a0, g[off + j]);
-            for (int64_t j = head + 4 * nvec; j < len; ++j) a0 = norm_acc<INF>(a0, g[off + j]);
-        }
-    }
-    const double a = norm_join<INF>(norm_join<INF>(a0, a1), norm_join<INF>(a2, a3));
-    const double r = norm_block_reduce<INF>(a, red);
-    if (threadIdx.x == 0) partials[blockIdx.x] = r;                 // every workgroup writes its slot: the finish reads all of them
-}
-
-// One workgroup: thread t joins partials t, t + 256, ... in order, then the fixed tree; thread 0 writes {total_norm, clip_coef}.
-template <bool INF>
-__global__ __launch_bounds__(NORM_THREADS) void k_grad_norm_finish(const double* __restrict__ partials, int nblocks, float max_norm,
-                                                                   float* __restrict__ rec) {
-    __shared__ double red[NORM_THREADS / 64];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += NORM_THREADS) a = norm_join<INF>(a, partials[i]);
-    const double r = norm_block_reduce<INF>(a, red);
-    if (threadIdx.x == 0) {
-        const float total = INF ? (float)r : (float)sqrt(r);
-        rec[0] = total;
-        rec[1] = clip_coef_f32(max_norm, total);
-    }
-}
-
-// grad[i] *= clip_coef over the segment table (cvk_grad_scale).  A coefficient of exactly 1 leaves the buffer untouched.
-__global__ __launch_bounds__(NORM_THREADS) void k_grad_scale(float* __restrict__ g, int64_t n, const cvk_norm_segment* __restrict__ st,
-                                                             int ns, const float* __restrict__ rec) {
-    const float coef = rec[1];
-    if (coef == 1.f) return;
-    int64_t off, len;
-    int rank, nb;
-    if (!norm_segment_of(st, ns, n, &off, &len, &rank, &nb)) return;
-    const int64_t head = norm_head(g, off, len);
-    const int64_t nvec = (len - head) >> 2;
-    f32x4* __restrict__ gv = reinterpret_cast<f32x4*>(g + off + head);
-    const int64_t tid = (int64_t)rank * NORM_THREADS + threadIdx.x, stride = (int64_t)nb * NORM_THREADS;
-    for (int64_t i = tid; i < nvec; i += stride) {
-        f32x4 x = gv[i];
-        x[0] *= coef; x[1] *= coef; x[2] *= coef; x[3] *= coef;
-        gv[i] = x;
-    }
-    if (tid == 0) {
-        for (int64_t j = 0; j < head; ++j) g[off + j] *= coef;
-        for (int64_t j = head + 4 * nvec; j < len; ++j) g[off + j] *= coef;
-    }
-}
-
-// ---- gradient accumulation over micro-batches (cvk_grad_accumulate) ----------------------------------------------------------------
-// One element of the fold.  MODE 0: dst = src; 1: dst = dst + src; 2: dst = (dst + src) * scale.  One correctly rounded fp32 add, then
-// (mode 2) one separately rounded multiply: an add feeding a multiply has no fused form, and the file is built without fast-math, so
-// the result is bitwise `(d + s) * scale` of IEEE fp32 whatever the vector width.
-template <int MODE>
-__device__ __forceinline__ float acc_one(float d, float s, float scale) {
-    if (MODE == 0) return s;
-    if (MODE == 1) return d + s;
-    return (d + s) * scale;
-}
-
-// dst and src share the table (same offsets in both buffers) and both bases are 16-byte aligned (checked by the entry point), so the
-// head / vector / tail split of a segment is the same on both sides.  Elements outside the table are neither read nor written.
-template <int MODE>
-__global__ __launch_bounds__(NORM_THREADS) void k_grad_accumulate(float* __restrict__ dst, const float* __restrict__ src, int64_t n,
-                                                                  const cvk_norm_segment* __restrict__ st, int ns, float scale) {
-    int64_t off, len;
-    int rank, nb;
-    if (!norm_segment_of(st, ns, n, &off, &len, &rank, &nb)) return;
-    const int64_t head = norm_head(dst, off, len);
-    const int64_t nvec = (len - head) >> 2;
-    f32x4* __restrict__ dv = reinterpret_cast<f32x4*>(dst + off + head);
-    const f32x4* __restrict__ sv = reinterpret_cast<const f32x4*>(src + off + head);
-    const int64_t tid = (int64_t)rank * NORM_THREADS + threadIdx.x, stride = (int64_t)nb * NORM_THREADS;
-    int64_t i = tid;
-    for (; i + (NORM_UNROLL - 1) * stride < nvec; i += NORM_UNROLL * stride) {
-        f32x4 s[NORM_UNROLL], d[NORM_UNROLL];
-#pragma unroll
-        for (int u = 0; u < NORM_UNROLL; ++u) {
-            s[u] = sv[i + u * stride];
-            if (MODE != 0) d[u] = dv[i + u * stride];
-        }
-#pragma unroll
-        for (int u = 0; u < NORM_UNROLL; ++u) {
-            f32x4 r;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) r[k] = acc_one<MODE>(MODE != 0 ? d[u][k] : 0.f, s[u][k], scale);
-            dv[i + u * stride] = r;
-        }
-    }
-    for (; i < nvec; i += stride) {
-        const f32x4 s = sv[i];
-        f32x4 r;
-        if (MODE != 0) r = dv[i];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = acc_one<MODE>(MODE != 0 ? r[k] : 0.f, s[k], scale);
-        dv[i] = r;
-    }
-    if (tid == 0) {         // the at most 3 + 3 elements around the vectors: the segment's first thread
-        for (int64_t j = 0; j < head; ++j) dst[off + j] = acc_one<MODE>(MODE != 0 ? dst[off + j] : 0.f, src[off + j], scale);
-        for (int64_t j = head + 4 * nvec; j < len; ++j) dst[off + j] = acc_one<MODE>(MODE != 0 ? dst[off + j] : 0.f, src[off + j], scale);
-    }
-}
-
 // uint8 HWC (cv2 BGR order kept) -> float32 NHWC, 4 channels per pixel (3 valid + zero pad): (v/255 - mean[c]) / std[c]
 // = reference transforms.ToTensor + Normalize (transforms.py:485-538) with conf/settings.py:8-9 MEAN/STD passed in.
 __global__ void k_preprocess_u8(const uint8_t* __restrict__ src, float* __restrict__ dst, long npix, float m0, float m1,
@@ -3175,8 +2273,6 @@ __global__ void __launch_bounds__(256) k_augment_u8(AugArgs A) {
         default: aug_tile<4>(A, rec, s_in, s_h, s_lut, use_lut); break;
     }
 }
-
-#include "surface_dist.h"
 
 }  // namespace
 
@@ -3419,65 +2515,6 @@ extern "C" int cvk_lovasz_softmax_bwd(const float* logits, int ld, const int64_t
     CVK_LAUNCH_RETURN("cvk_lovasz_softmax_bwd");
 }
 
-static size_t edt_cols_bytes(int N, int H, int W, int C) { return ((size_t)2 * N * H * W * (C + 1) + 15) & ~(size_t)15; }
-
-static int edt_check_sizes(const char* who, int N, int H, int W, int C) {
-    CVK_CHECK_ARG(N > 0 && H > 0 && W > 0, "%s: sizes must be positive, got N %d, H %d, W %d", who, N, H, W);
-    CVK_CHECK_ARG(C >= 1 && C <= EDT_MAX_C, "%s: %d classes, the kernels serve 1 to %d", who, C, EDT_MAX_C);
-    CVK_CHECK_ARG(H <= EDT_MAX_H, "%s: H %d, a column distance is 16 bits wide (H <= %d)", who, H, EDT_MAX_H);
-    CVK_CHECK_ARG((int64_t)(H - 1) * (H - 1) + (int64_t)(W - 1) * (W - 1) < EDT_MAX_D2,
-                  "%s: image too large, (H - 1)^2 + (W - 1)^2 must stay below 2^24 for exact fp32 roots, got H %d, W %d", who, H, W);
-    CVK_CHECK_ARG((int64_t)N * H * W < 2147483648LL, "%s: 2^31 pixels or more", who);
-    return CVK_OK;
-}
-
-extern "C" int64_t cvk_edt_workspace_bytes(int N, int H, int W, int C) {
-    if (N <= 0 || H <= 0 || W <= 0 || C < 1 || C > EDT_MAX_C || H > EDT_MAX_H || (int64_t)N * H * W >= 2147483648LL ||
-        (int64_t)(H - 1) * (H - 1) + (int64_t)(W - 1) * (W - 1) >= EDT_MAX_D2)
-        return 0;
-    return (int64_t)(edt_cols_bytes(N, H, W, C) + 16 * (((size_t)8 * N + 15) / 16));
-}
-
-template <bool SIGNED>
-static void edt_launch(const int64_t* labels, int N, int H, int W, int C, int ignore_index, void* workspace, int* to_class, int* to_other,
-                       float* phi, hipStream_t s) {
-    unsigned short* col = static_cast<unsigned short*>(workspace);
-    unsigned* mask = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + edt_cols_bytes(N, H, W, C));
-    const int K = C + 1;
-    hipLaunchKernelGGL(k_lv_clear, dim3(cvk_cdiv(2 * (long)N, 256)), dim3(256), 0, s, mask, 2 * N);
-    const int strips = cvk_cdiv(W, EDT_COL_TX);
-    hipLaunchKernelGGL(k_edt_cols, dim3((unsigned)N * strips), dim3(256), (size_t)H * EDT_COL_TX, s, labels, col, mask, strips, H, W, C,
-                       ignore_index);
-    const size_t tile = (size_t)4 * 256 * (C | 1);
-    const size_t staged = (((size_t)2 * W * (K + 1) + 3) & ~(size_t)3) + tile, unstaged = (((size_t)2 * W + 3) & ~(size_t)3) + tile;
-    if (staged <= EDT_LDS_LIMIT)
-        hipLaunchKernelGGL((k_edt_rows<true, SIGNED>), dim3((unsigned)N * H), dim3(256), staged, s, labels, col, mask, to_class, to_other,
-                           phi, H, W, C, ignore_index);
-    else
-        hipLaunchKernelGGL((k_edt_rows<false, SIGNED>), dim3((unsigned)N * H), dim3(256), unstaged, s, labels, col, mask, to_class,
-                           to_other, phi, H, W, C, ignore_index);
-}
-
-extern "C" int cvk_edt_squared(const int64_t* labels, int N, int H, int W, int num_classes, int ignore_index, void* workspace,
-                               int32_t* to_class, int32_t* to_other, void* stream) {
-    CVK_CHECK_ARG(labels && workspace && to_class && to_other, "cvk_edt_squared: null pointer");
-    const int rc = edt_check_sizes("cvk_edt_squared", N, H, W, num_classes);
-    if (rc != CVK_OK) return rc;
-    CVK_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "cvk_edt_squared: the workspace must be 16-byte aligned");
-    edt_launch<false>(labels, N, H, W, num_classes, ignore_index, workspace, to_class, to_other, nullptr, (hipStream_t)stream);
-    CVK_LAUNCH_RETURN("cvk_edt_squared");
-}
-
-extern "C" int cvk_edt_signed(const int64_t* labels, int N, int H, int W, int num_classes, int ignore_index, void* workspace, float* phi,
-                              void* stream) {
-    CVK_CHECK_ARG(labels && workspace && phi, "cvk_edt_signed: null pointer");
-    const int rc = edt_check_sizes("cvk_edt_signed", N, H, W, num_classes);
-    if (rc != CVK_OK) return rc;
-    CVK_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "cvk_edt_signed: the workspace must be 16-byte aligned");
-    edt_launch<true>(labels, N, H, W, num_classes, ignore_index, workspace, nullptr, nullptr, phi, (hipStream_t)stream);
-    CVK_LAUNCH_RETURN("cvk_edt_signed");
-}
-
 extern "C" int cvk_boundary_loss_part_floats(int M, int C) {
     return M > 0 && C >= 1 && C <= EDT_MAX_C ? (BDL_PART_HEAD + C) * cvk_ce_blocks(M) : 0;
 }
@@ -3639,23 +2676,6 @@ extern "C" int cvk_kd_loss_bwd(const float* student, int ld_s, const float* teac
     CVK_LAUNCH_RETURN("cvk_kd_loss_bwd");
 }
 
-extern "C" int cvk_class_histogram(const void* masks, int mask_bytes, int N, int64_t HW, int num_classes, int ignore_index,
-                                   int64_t* hist, void* stream) {
-    CVK_CHECK_ARG(masks && hist, "cvk_class_histogram: null pointer");
-    CVK_CHECK_ARG((mask_bytes == 1 || mask_bytes == 8) && N > 0 && HW > 0 && num_classes > 0 && num_classes <= HIST_MAX_C,
-                  "cvk_class_histogram: bad arguments");
-    hipLaunchKernelGGL(k_class_hist, dim3(N), dim3(HIST_THREADS), 0, (hipStream_t)stream, masks, mask_bytes, HW, num_classes,
-                       ignore_index, (unsigned long long*)hist);
-    CVK_LAUNCH_RETURN("cvk_class_histogram");
-}
-
-extern "C" int cvk_argmax_channels(const float* logits, int ld, int64_t* out, int M, int C, void* stream) {
-    CVK_CHECK_ARG(logits && out && M > 0 && C > 0 && ld >= C, "cvk_argmax_channels: bad arguments");
-    const int blocks = cvk_cdiv(M, 256) < 8192 ? cvk_cdiv(M, 256) : 8192;
-    hipLaunchKernelGGL(k_argmax, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, ld, out, M, C);
-    CVK_LAUNCH_RETURN("cvk_argmax_channels");
-}
-
 template <bool IDENT>
 static bool tta_launch(int CP, int nb, size_t lds_bytes, hipStream_t s, const float* logits, int ld, int h, int w, float* acc, int64_t* pred,
                        int H, int W, int M, int C, int flip, int first, int last, float inv_k) {
@@ -3725,358 +2745,6 @@ extern "C" int cvk_window_merge(const float* logits, int ld, float* out, int64_t
     hipLaunchKernelGGL(k_window_merge, dim3(cvk_cdiv(M, CE_CHUNK)), dim3(CE_CHUNK), lds_bytes, (hipStream_t)stream, logits, ld, out, pred, M, C,
                        g);
     CVK_LAUNCH_RETURN("cvk_window_merge");
-}
-
-extern "C" int cvk_boundary_counts(const int64_t* pred, const int64_t* label, int64_t* counts, int N, int H, int W, int num_classes,
-                                   int ignore_index, int r2, void* stream) {
-    CVK_CHECK_ARG(pred && label && counts, "cvk_boundary_counts: null pointer");
-    CVK_CHECK_ARG(num_classes >= 1 && num_classes <= BF_MAX_K, "cvk_boundary_counts: %d classes, the kernel serves 1 to %d", num_classes,
-                  BF_MAX_K);
-    CVK_CHECK_ARG(r2 >= 0 && r2 <= BF_MAX_R2, "cvk_boundary_counts: squared tolerance %d outside 0..%d (16 pixels)", r2, BF_MAX_R2);
-    CVK_CHECK_ARG(N > 0 && H > 0 && W > 0, "cvk_boundary_counts: sizes must be positive, got N %d, H %d, W %d", N, H, W);
-    CVK_CHECK_ARG((int64_t)N * H * W < 2147483648LL, "cvk_boundary_counts: 2^31 pixels or more");
-    int R = 0;
-    while ((R + 1) * (R + 1) <= r2) ++R;
-    const int tiles_x = cvk_cdiv(W, BF_TW), tiles = tiles_x * cvk_cdiv(H, BF_TH);
-    const size_t codes = ((size_t)(BF_TH + 2 * R + 2) * (BF_TW + 2 * R + 2) + 3) & ~(size_t)3;
-    const size_t lds_bytes = 2 * codes + 2 * (size_t)(BF_TH + 2 * R) * ((BF_TW + 2 * R + 3) & ~3);
-    hipLaunchKernelGGL(k_boundary_counts, dim3((unsigned)tiles * (unsigned)N), dim3(BF_THREADS), lds_bytes, (hipStream_t)stream, pred, label,
-                       reinterpret_cast<unsigned long long*>(counts), H, W, num_classes, ignore_index, r2, R, tiles_x, tiles);
-    CVK_LAUNCH_RETURN("cvk_boundary_counts");
-}
-
-extern "C" int cvk_boundary_map(const int64_t* map, const int64_t* void_from, uint8_t* out_u8, int N, int H, int W, int num_classes,
-                                int ignore_index, void* stream) {
-    CVK_CHECK_ARG(map && out_u8, "cvk_boundary_map: null pointer");
-    CVK_CHECK_ARG(num_classes >= 1 && num_classes <= BF_MAX_K, "cvk_boundary_map: %d classes, the kernel serves 1 to %d", num_classes,
-                  BF_MAX_K);
-    CVK_CHECK_ARG(N > 0 && H > 0 && W > 0, "cvk_boundary_map: sizes must be positive, got N %d, H %d, W %d", N, H, W);
-    CVK_CHECK_ARG((int64_t)N * H * W < 2147483648LL, "cvk_boundary_map: 2^31 pixels or more");
-    hipLaunchKernelGGL(k_boundary_map, dim3(cvk_cdiv((long)N * H * W, 256)), dim3(256), 0, (hipStream_t)stream, map,
-                       void_from ? void_from : map, out_u8, N, H, W, num_classes, ignore_index);
-    CVK_LAUNCH_RETURN("cvk_boundary_map");
-}
-
-extern "C" int64_t cvk_surface_workspace_bytes(int N, int H, int W, int num_classes) {
-    if (cvk_edt_workspace_bytes(N, H, W, num_classes) == 0) return 0;
-    const SdLayout L = sd_layout(N, H, W, num_classes);
-    return (L.total - L.an) / 16 / 256 < 2147483648ULL ? (int64_t)L.total : 0;
-}
-
-extern "C" int cvk_surface_record_slots(void) { return SD_SLOTS; }
-
-extern "C" int cvk_surface_distances(const int64_t* pred, const int64_t* label, int N, int H, int W, int num_classes, int ignore_index,
-                                     int qnum, int qden, void* workspace, int32_t* d2, int64_t* record, void* stream) {
-    CVK_CHECK_ARG(pred && label && workspace && d2 && record, "cvk_surface_distances: null pointer");
-    const int rc = edt_check_sizes("cvk_surface_distances", N, H, W, num_classes);
-    if (rc != CVK_OK) return rc;
-    CVK_CHECK_ARG(cvk_surface_workspace_bytes(N, H, W, num_classes) > 0, "cvk_surface_distances: the workspace of N %d, %d classes is too large",
-                  N, num_classes);
-    CVK_CHECK_ARG(qden >= 1 && qden <= 10000 && qnum >= 0 && qnum <= qden,
-                  "cvk_surface_distances: percentile fraction %d / %d, need 0 <= qnum <= qden <= 10000", qnum, qden);
-    CVK_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "cvk_surface_distances: the workspace must be 16-byte aligned");
-    CVK_CHECK_ARG(((uintptr_t)d2 & 3u) == 0 && ((uintptr_t)record & 7u) == 0, "cvk_surface_distances: d2 or record misaligned");
-    hipStream_t s = (hipStream_t)stream;
-    const int C = num_classes;
-    const SdLayout L = sd_layout(N, H, W, C);
-    char* ws = static_cast<char*>(workspace);
-    unsigned short* col = reinterpret_cast<unsigned short*>(ws + L.col);
-    unsigned char* bmap = reinterpret_cast<unsigned char*>(ws + L.bmap);
-    int* sel = reinterpret_cast<int*>(ws + L.sel);
-    unsigned long long* an = reinterpret_cast<unsigned long long*>(ws + L.an);
-    unsigned long long* aq = reinterpret_cast<unsigned long long*>(ws + L.aq);
-    unsigned* present = reinterpret_cast<unsigned*>(ws + L.present);
-    unsigned* amax = reinterpret_cast<unsigned*>(ws + L.amax);
-    unsigned* hist1 = reinterpret_cast<unsigned*>(ws + L.hist1);
-    unsigned* hist2 = reinterpret_cast<unsigned*>(ws + L.hist2);
-    const size_t n16 = (L.total - L.an) / 16;
-    hipLaunchKernelGGL(k_sd_clear, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint4*>(ws + L.an), n16);
-    const dim3 gpx(cvk_cdiv((long)L.M, 256));
-    hipLaunchKernelGGL(k_boundary_map, gpx, dim3(256), 0, s, pred, label, bmap, N, H, W, C, ignore_index);
-    hipLaunchKernelGGL(k_boundary_map, gpx, dim3(256), 0, s, label, label, bmap + L.M, N, H, W, C, ignore_index);
-    const int strips = cvk_cdiv(W, EDT_COL_TX);
-    hipLaunchKernelGGL(k_sd_cols, dim3((unsigned)N * strips, 2), dim3(256), (size_t)H * EDT_COL_TX, s, bmap, col, present, strips, N, H, W, C);
-    const size_t bytes_b = (size_t)2 * ((W + 3) & ~3) + sizeof(unsigned) * 2 * C * SD_SMALL, staged = bytes_b + (size_t)4 * W * C;
-    if (staged + 1024 <= EDT_LDS_LIMIT)
-        hipLaunchKernelGGL(k_sd_rows<true>, dim3((unsigned)N * H), dim3(256), staged, s, bmap, col, present, d2, an, aq, amax, hist1, L.nb1,
-                           L.M, H, W, C);
-    else
-        hipLaunchKernelGGL(k_sd_rows<false>, dim3((unsigned)N * H), dim3(256), bytes_b, s, bmap, col, present, d2, an, aq, amax, hist1,
-                           L.nb1, L.M, H, W, C);
-    const dim3 gseg((unsigned)(L.S < (size_t)SD_MAX_SEG_GROUPS ? L.S : (size_t)SD_MAX_SEG_GROUPS));
-    hipLaunchKernelGGL(k_sd_pick, gseg, dim3(256), 0, s, an, hist1, L.nb1, sel, L.S, C, qnum, qden);
-    hipLaunchKernelGGL(k_sd_refine, dim3((unsigned)((2 * L.M + 255) / 256)), dim3(256), 0, s, d2, bmap, sel, hist2, L.M, H * W, C);
-    hipLaunchKernelGGL(k_sd_finish, gseg, dim3(256), 0, s, an, aq, amax, sel, hist2, reinterpret_cast<long long*>(record), L.S, C, qnum, qden);
-    CVK_LAUNCH_RETURN("cvk_surface_distances");
-}
-
-extern "C" int cvk_confusion_accumulate(const int64_t* pred, const int64_t* label, int64_t* hist, int M, int num_classes,
-                                        int ignore_index, void* stream) {
-    CVK_CHECK_ARG(pred && label && hist && M > 0 && num_classes > 0 && num_classes <= 4096, "cvk_confusion_accumulate: bad arguments");
-    const int blocks = cvk_cdiv(M, 1024) < 1024 ? cvk_cdiv(M, 1024) : 1024;
-    hipLaunchKernelGGL(k_confusion, dim3(blocks), dim3(256), 3 * num_classes * sizeof(unsigned int), (hipStream_t)stream, pred, label,
-                       (unsigned long long*)hist, M, num_classes, ignore_index);
-    CVK_LAUNCH_RETURN("cvk_confusion_accumulate");
-}
-
-// bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step), evaluated on the HOST (glibc powf) for both AdamW entry points: a
-// device powf need not round like the host's, and the captured update must be bitwise the eager one.
-static void adamw_bias_corrections(float beta1, float beta2, int step, float* bc1, float* bc2_sqrt) {
-    *bc1 = 1.f - powf(beta1, (float)step);
-    *bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
-}
-
-static int adamw_blocks(int64_t n) {
-    const int64_t b = (n + 255) / 256;
-    return (int)(b < 8192 ? b : 8192);
-}
-
-extern "C" int cvk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                              float beta2, float eps, float weight_decay, int step, void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, "cvk_adamw_step: bad arguments");
-    float bc1, bc2s;
-    adamw_bias_corrections(beta1, beta2, step, &bc1, &bc2s);
-    hipLaunchKernelGGL(k_adamw, dim3(adamw_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
-                       lr, beta1, beta2, eps, weight_decay, bc1, bc2s);
-    CVK_LAUNCH_RETURN("cvk_adamw_step");
-}
-
-extern "C" int cvk_adamw_hyper_fill(float lr, float beta1, float beta2, float eps, float weight_decay, int step, cvk_adamw_hyper* out) {
-    CVK_CHECK_ARG(out && step >= 1, "cvk_adamw_hyper_fill: bad arguments");
-    out->lr = lr;
-    out->beta1 = beta1;
-    out->beta2 = beta2;
-    out->eps = eps;
-    out->weight_decay = weight_decay;
-    adamw_bias_corrections(beta1, beta2, step, &out->bc1, &out->bc2_sqrt);
-    return CVK_OK;
-}
-
-// The planners' shared step: every entry's first workgroup (block0) and the total.  An entry of `length` elements gets one workgroup per
-// `per` elements, at most its share of the budget (one per `per` elements of the `total`, at most `cap`, shared in proportion to the
-// lengths), at least one.  Returns the workgroup count, or -1 as soon as it reaches 2^30.
-template <class ENTRY>
-static int64_t plan_block0(ENTRY* e, int count, int64_t total, int64_t per, int64_t cap) {
-    int64_t budget = (total + per - 1) / per;
-    if (budget > cap) budget = cap;
-    int64_t blocks = 0;
-    for (int r = 0; r < count; ++r) {
-        int64_t nb = (e[r].length + per - 1) / per;
-        const int64_t share = (int64_t)(((__int128)budget * e[r].length + total - 1) / total);
-        if (nb > share) nb = share;
-        if (nb < 1) nb = 1;
-        e[r].block0 = (int32_t)blocks;
-        blocks += nb;
-        if (blocks >= (1LL << 30)) return -1;
-    }
-    return blocks;
-}
-
-// Workgroups per range: as many as k_adamw would give the range's elements alone (one per 256, at most 8192 in all).
-extern "C" int cvk_adamw_plan_ranges(cvk_adamw_range* ranges, int nranges, int64_t n, int nhyper) {
-    CVK_CHECK_ARG(ranges && nranges > 0 && n > 0 && nhyper > 0, "cvk_adamw_plan_ranges: bad arguments");
-    int64_t total = 0;
-    for (int r = 0; r < nranges; ++r) {
-        const cvk_adamw_range& e = ranges[r];
-        CVK_CHECK_ARG(e.offset >= 0 && e.length > 0 && e.offset + e.length <= n, "cvk_adamw_plan_ranges: range %d [%lld, +%lld) outside the "
-                      "buffer of %lld elements", r, (long long)e.offset, (long long)e.length, (long long)n);
-        CVK_CHECK_ARG(e.hyper >= 0 && e.hyper < nhyper, "cvk_adamw_plan_ranges: range %d names record %d of %d", r, e.hyper, nhyper);
-        total += e.length;
-    }
-    const int64_t blocks = plan_block0(ranges, nranges, total, 256, 8192);
-    CVK_CHECK_ARG(blocks >= 0, "cvk_adamw_plan_ranges: too many workgroups");
-    return (int)blocks;
-}
-
-// One launch of the range kernel: SRC and EMA pick the instantiation, the argument list is the same for all four.
-template <class SRC>
-static void adamw_ranges_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
-                                const cvk_adamw_range* ranges, int nranges, int nblocks, const SRC& src, int nhyper, const float* record,
-                                void* stream) {
-    if (ema != nullptr)
-        hipLaunchKernelGGL((k_adamw_ranges<SRC, true>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
-                           ema, n, ranges, nranges, src, nhyper, record);
-    else
-        hipLaunchKernelGGL((k_adamw_ranges<SRC, false>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
-                           ema, n, ranges, nranges, src, nhyper, record);
-}
-
-extern "C" int cvk_adamw_step_ranges(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
-                                     const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                                     const float* record, float alpha, void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper, "cvk_adamw_step_ranges: null pointer");
-    CVK_CHECK_ARG(!ema || (alpha > 0.f && alpha <= 1.f), "cvk_adamw_step_ranges: alpha %g outside (0, 1]", (double)alpha);
-    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
-                  "cvk_adamw_step_ranges: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
-    AdamwArgSource src = {};
-    for (int i = 0; i < nhyper; ++i) src.recs.r[i] = hyper[i];
-    src.a = alpha;
-    adamw_ranges_launch(param, grad, exp_avg, exp_avg_sq, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
-    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges");
-}
-
-// alpha (DEVICE, one float) is what the kernel reads, rewritten by the host between graph replays; alpha_host is the value the host is
-// about to upload there (at a capture: the first one), checked here because the device value cannot be.
-extern "C" int cvk_adamw_step_ranges_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
-                                         const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_adamw_hyper* hyper, int nhyper,
-                                         const float* record, const float* alpha, float alpha_host, void* stream) {
-    CVK_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && ranges && hyper && (!ema || alpha), "cvk_adamw_step_ranges_dev: null pointer");
-    CVK_CHECK_ARG(!ema || (alpha_host > 0.f && alpha_host <= 1.f), "cvk_adamw_step_ranges_dev: alpha %g outside (0, 1]", (double)alpha_host);
-    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_adamw_step_ranges_dev: bad arguments");
-    const AdamwDevSource src = {hyper, alpha};
-    adamw_ranges_launch(param, grad, exp_avg, exp_avg_sq, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
-    CVK_LAUNCH_RETURN("cvk_adamw_step_ranges_dev");
-}
-
-// ---- momentum SGD over the same range table (torch.optim.SGD) ----------------------------------------------------------------------
-extern "C" int cvk_sgd_hyper_fill(float lr, float momentum, float dampening, float weight_decay, int nesterov, int first,
-                                  cvk_sgd_hyper* out) {
-    CVK_CHECK_ARG(out, "cvk_sgd_hyper_fill: null pointer");
-    CVK_CHECK_ARG(lr >= 0.f, "cvk_sgd_hyper_fill: lr %g must be >= 0", (double)lr);
-    CVK_CHECK_ARG(momentum >= 0.f, "cvk_sgd_hyper_fill: momentum %g must be >= 0", (double)momentum);
-    CVK_CHECK_ARG(weight_decay >= 0.f, "cvk_sgd_hyper_fill: weight_decay %g must be >= 0", (double)weight_decay);
-    CVK_CHECK_ARG(!nesterov || (momentum > 0.f && dampening == 0.f), "cvk_sgd_hyper_fill: nesterov needs a momentum > 0 and zero dampening "
-                  "(momentum %g, dampening %g)", (double)momentum, (double)dampening);
-    out->lr = lr;
-    out->momentum = momentum;
-    out->dampening = dampening;
-    out->weight_decay = weight_decay;
-    out->nesterov = nesterov ? 1.f : 0.f;
-    out->first = first ? 1.f : 0.f;
-    out->reserved = 0.f;
-    return CVK_OK;
-}
-
-// One launch of the SGD range kernel: SRC, EMA and MOM pick the instantiation, the argument list is the same for all eight.
-template <class SRC, bool MOM>
-static void sgd_ranges_launch(float* param, const float* grad, float* buf, float* ema, int64_t n, const cvk_adamw_range* ranges, int nranges,
-                              int nblocks, const SRC& src, int nhyper, const float* record, void* stream) {
-    if (ema != nullptr)
-        hipLaunchKernelGGL((k_sgd_ranges<SRC, true, MOM>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, buf, ema, n, ranges,
-                           nranges, src, nhyper, record);
-    else
-        hipLaunchKernelGGL((k_sgd_ranges<SRC, false, MOM>), dim3(nblocks), dim3(256), 0, (hipStream_t)stream, param, grad, buf, ema, n, ranges,
-                           nranges, src, nhyper, record);
-}
-
-extern "C" int cvk_sgd_step_ranges(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n,
-                                   const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_sgd_hyper* hyper, int nhyper,
-                                   const float* record, float alpha, void* stream) {
-    CVK_CHECK_ARG(param && grad && ranges && hyper, "cvk_sgd_step_ranges: null pointer");
-    CVK_CHECK_ARG(!ema || (alpha > 0.f && alpha <= 1.f), "cvk_sgd_step_ranges: alpha %g outside (0, 1]", (double)alpha);
-    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0 && nhyper <= CVK_ADAMW_ARG_RECORDS,
-                  "cvk_sgd_step_ranges: bad arguments (records: %d, at most %d)", nhyper, CVK_ADAMW_ARG_RECORDS);
-    AdamwArgSource src = {};
-    for (int i = 0; i < nhyper; ++i) {
-        CVK_CHECK_ARG(momentum_buf || hyper[i].momentum == 0.f, "cvk_sgd_step_ranges: null momentum buffer, but record %d has momentum %g", i,
-                      (double)hyper[i].momentum);
-        src.recs.r[i] = {hyper[i].lr, hyper[i].momentum, hyper[i].dampening, hyper[i].weight_decay, hyper[i].nesterov, hyper[i].first,
-                         hyper[i].reserved};                          // the 7 floats in their slots (static_assert above the kernel)
-    }
-    src.a = alpha;
-    if (momentum_buf != nullptr)
-        sgd_ranges_launch<AdamwArgSource, true>(param, grad, momentum_buf, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
-    else
-        sgd_ranges_launch<AdamwArgSource, false>(param, grad, momentum_buf, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
-    CVK_LAUNCH_RETURN("cvk_sgd_step_ranges");
-}
-
-// hyper and alpha as in cvk_adamw_step_ranges_dev.  The device records cannot be checked here: a null momentum_buf selects the kernel that
-// never touches a buffer, whatever momentum they carry (FlatSGD captures it only while every group's momentum is 0 and GraphedStep
-// refuses to replay after that changes).
-extern "C" int cvk_sgd_step_ranges_dev(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n,
-                                       const cvk_adamw_range* ranges, int nranges, int nblocks, const cvk_sgd_hyper* hyper, int nhyper,
-                                       const float* record, const float* alpha, float alpha_host, void* stream) {
-    CVK_CHECK_ARG(param && grad && ranges && hyper && (!ema || alpha), "cvk_sgd_step_ranges_dev: null pointer");
-    CVK_CHECK_ARG(!ema || (alpha_host > 0.f && alpha_host <= 1.f), "cvk_sgd_step_ranges_dev: alpha %g outside (0, 1]", (double)alpha_host);
-    CVK_CHECK_ARG(n > 0 && nranges > 0 && nblocks >= nranges && nhyper > 0, "cvk_sgd_step_ranges_dev: bad arguments");
-    const AdamwDevSource src = {reinterpret_cast<const cvk_adamw_hyper*>(hyper), alpha};
-    if (momentum_buf != nullptr)
-        sgd_ranges_launch<AdamwDevSource, true>(param, grad, momentum_buf, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
-    else
-        sgd_ranges_launch<AdamwDevSource, false>(param, grad, momentum_buf, ema, n, ranges, nranges, nblocks, src, nhyper, record, stream);
-    CVK_LAUNCH_RETURN("cvk_sgd_step_ranges_dev");
-}
-
-// record (the {total_norm, clip_coef} record of cvk_grad_norm) may be null: rows of 5 floats; with it, rows of 7.
-extern "C" int cvk_step_log(const float* loss, const cvk_adamw_hyper* hyper, const float* gw, int nw, const float* gb, int nb,
-                            const float* record, float* ring, int capacity, int64_t* counter, void* stream) {
-    CVK_CHECK_ARG(loss && hyper && gw && gb && ring && counter, "cvk_step_log: null pointer");
-    CVK_CHECK_ARG(nw > 0 && nb > 0 && capacity > 0, "cvk_step_log: bad arguments");
-    hipLaunchKernelGGL(k_step_log, dim3(1), dim3(STEP_LOG_THREADS), 0, (hipStream_t)stream, loss, hyper, gw, nw, gb, nb, record, ring,
-                       capacity, counter);
-    CVK_LAUNCH_RETURN("cvk_step_log");
-}
-
-extern "C" float cvk_clip_coef(float max_norm, float total_norm) { return clip_coef_f32(max_norm, total_norm); }
-
-// Workgroups per segment: one per NORM_THREADS * NORM_UNROLL 16-byte vectors, at most NORM_MAX_BLOCKS in all.
-extern "C" int cvk_grad_norm_plan(cvk_norm_segment* segments, int nsegments, int64_t n) {
-    CVK_CHECK_ARG(segments, "cvk_grad_norm_plan: null pointer");
-    CVK_CHECK_ARG(nsegments > 0 && n > 0, "cvk_grad_norm_plan: empty table or buffer (%d segments, %lld elements)", nsegments, (long long)n);
-    int64_t total = 0;
-    for (int r = 0; r < nsegments; ++r) {
-        const cvk_norm_segment& e = segments[r];
-        CVK_CHECK_ARG(e.offset >= 0 && e.length > 0 && e.length <= n && e.offset <= n - e.length, "cvk_grad_norm_plan: segment %d [%lld, "
-                      "+%lld) outside the buffer of %lld elements", r, (long long)e.offset, (long long)e.length, (long long)n);
-        total += e.length;
-    }
-    const int64_t blocks = plan_block0(segments, nsegments, total, (int64_t)NORM_THREADS * NORM_UNROLL * 4, NORM_MAX_BLOCKS);
-    CVK_CHECK_ARG(blocks >= 0, "cvk_grad_norm_plan: too many workgroups");
-    return (int)blocks;
-}
-
-extern "C" int cvk_grad_norm(const float* grad, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks, float norm_type,
-                             float max_norm, double* partials, float* record, void* stream) {
-    CVK_CHECK_ARG(grad && segments && partials && record, "cvk_grad_norm: null pointer");
-    CVK_CHECK_ARG(n > 0 && nsegments > 0 && nblocks >= nsegments, "cvk_grad_norm: empty table or buffer (%d segments, %d workgroups)",
-                  nsegments, nblocks);
-    const bool inf = norm_type == __builtin_inff();
-    CVK_CHECK_ARG(inf || norm_type == 2.f, "cvk_grad_norm: norm_type %g (2 and infinity are implemented)", (double)norm_type);
-    CVK_CHECK_ARG(max_norm >= 0.f, "cvk_grad_norm: max_norm %g is negative or not a number", (double)max_norm);
-    CVK_CHECK_ARG((((uintptr_t)grad) & 3u) == 0 && (((uintptr_t)partials) & 7u) == 0, "cvk_grad_norm: misaligned buffer");
-    if (inf) {
-        hipLaunchKernelGGL(k_grad_norm_partial<true>, dim3(nblocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, grad, n, segments, nsegments,
-                           partials);
-        hipLaunchKernelGGL(k_grad_norm_finish<true>, dim3(1), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const double*)partials, nblocks,
-                           max_norm, record);
-    } else {
-        hipLaunchKernelGGL(k_grad_norm_partial<false>, dim3(nblocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, grad, n, segments, nsegments,
-                           partials);
-        hipLaunchKernelGGL(k_grad_norm_finish<false>, dim3(1), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const double*)partials, nblocks,
-                           max_norm, record);
-    }
-    CVK_LAUNCH_RETURN("cvk_grad_norm");
-}
-
-extern "C" int cvk_grad_scale(float* grad, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks, const float* record,
-                              void* stream) {
-    CVK_CHECK_ARG(grad && segments && record, "cvk_grad_scale: null pointer");
-    CVK_CHECK_ARG(n > 0 && nsegments > 0 && nblocks >= nsegments, "cvk_grad_scale: empty table or buffer (%d segments, %d workgroups)",
-                  nsegments, nblocks);
-    CVK_CHECK_ARG((((uintptr_t)grad) & 3u) == 0, "cvk_grad_scale: misaligned buffer");
-    hipLaunchKernelGGL(k_grad_scale, dim3(nblocks), dim3(NORM_THREADS), 0, (hipStream_t)stream, grad, n, segments, nsegments, record);
-    CVK_LAUNCH_RETURN("cvk_grad_scale");
-}
-
-extern "C" int cvk_grad_accumulate(float* dst, const float* src, int64_t n, const cvk_norm_segment* segments, int nsegments, int nblocks,
-                                   int mode, float scale, void* stream) {
-    CVK_CHECK_ARG(dst && src && segments, "cvk_grad_accumulate: null pointer");
-    CVK_CHECK_ARG(dst != src, "cvk_grad_accumulate: dst and src are the same buffer");
-    CVK_CHECK_ARG(n > 0 && nsegments > 0 && nblocks >= nsegments, "cvk_grad_accumulate: empty table or buffer (%d segments, %d workgroups)",
-                  nsegments, nblocks);
-    CVK_CHECK_ARG(mode >= 0 && mode <= 2, "cvk_grad_accumulate: mode %d (0: copy, 1: add, 2: add and scale)", mode);
-    CVK_CHECK_ARG(scale - scale == 0.f, "cvk_grad_accumulate: scale %g is not finite", (double)scale);
-    CVK_CHECK_ARG((((uintptr_t)dst) & 15u) == 0 && (((uintptr_t)src) & 15u) == 0,
-                  "cvk_grad_accumulate: misaligned buffer (both bases must be 16-byte aligned)");
-    const dim3 grid(nblocks), block(NORM_THREADS);
-    if (mode == 0)
-        hipLaunchKernelGGL(k_grad_accumulate<0>, grid, block, 0, (hipStream_t)stream, dst, src, n, segments, nsegments, scale);
-    else if (mode == 1)
-        hipLaunchKernelGGL(k_grad_accumulate<1>, grid, block, 0, (hipStream_t)stream, dst, src, n, segments, nsegments, scale);
-    else
-        hipLaunchKernelGGL(k_grad_accumulate<2>, grid, block, 0, (hipStream_t)stream, dst, src, n, segments, nsegments, scale);
-    CVK_LAUNCH_RETURN("cvk_grad_accumulate");
 }
 
 // ---- library-wide pieces ---------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
+#pragma once
 // ---- surface distances: Hausdorff, its percentile and ASSD (cvk_surface_distances; the definitions are in include/cvk.h) ---------------
-// Included by loss_eval_optim.hip inside its namespace, after the distance transform (edt_row_search, EDT_*) and the boundary F1 kernels
-// (k_boundary_map, BF_*), whose contour rule and row search it shares.  M = N H W, segment s = (n, direction, class) = (2 n + dir) C + c,
+// Borrows the row search and the column walk's constants of the distance transform (edt.h: edt_row_search, EDT_*) and the contour rule
+// of the boundary F1 (boundary_f1.h: k_boundary_map, BF_*).  M = N H W, segment s = (n, direction, class) = (2 n + dir) C + c,
 // direction 0 = prediction -> label, 1 = label -> prediction.  Seven kernels, all on the caller's stream:
 //   k_sd_clear     zeroes the tail of the workspace: n and Q (uint64 [S] each), presence words [2 N], max [S], both histograms
 //                  (first level [S][4096 + wide bins], second level [S][2][4096])
@@ -24,6 +25,12 @@
 // LDS of k_sd_cols: 16 H B.  LDS of k_sd_rows: 2 W B of contour bytes + 512 C B of small-value counts (+ 4 W C B of column distances
 // when all of it fits 64 KiB: 0.9 + 6 + 22.5 KiB at W = 480, C = 12; else the search reads the column distances from global memory)
 // + 1 KiB of accumulators.
+#include "cvk_common.h"
+#include "edt.h"
+#include "boundary_f1.h"
+
+namespace {
+
 constexpr int SD_SLOTS = 8, SD_LOW_BITS = 12, SD_LOW_BINS = 1 << SD_LOW_BITS, SD_MAX_SEG_GROUPS = 1 << 20;
 constexpr int SD_SMALL = 64;                               // d2 below this is counted in LDS by k_sd_rows
 
@@ -335,4 +342,59 @@ __global__ __launch_bounds__(256) void k_sd_finish(const unsigned long long* __r
             o[7] = ev ? val[1] : -1;
         }
     }
+}
+
+}  // namespace
+
+extern "C" int64_t cvk_surface_workspace_bytes(int N, int H, int W, int num_classes) {
+    if (cvk_edt_workspace_bytes(N, H, W, num_classes) == 0) return 0;
+    const SdLayout L = sd_layout(N, H, W, num_classes);
+    return (L.total - L.an) / 16 / 256 < 2147483648ULL ? (int64_t)L.total : 0;
+}
+
+extern "C" int cvk_surface_record_slots(void) { return SD_SLOTS; }
+
+extern "C" int cvk_surface_distances(const int64_t* pred, const int64_t* label, int N, int H, int W, int num_classes, int ignore_index,
+                                     int qnum, int qden, void* workspace, int32_t* d2, int64_t* record, void* stream) {
+    CVK_CHECK_ARG(pred && label && workspace && d2 && record, "cvk_surface_distances: null pointer");
+    const int rc = edt_check_sizes("cvk_surface_distances", N, H, W, num_classes);
+    if (rc != CVK_OK) return rc;
+    CVK_CHECK_ARG(cvk_surface_workspace_bytes(N, H, W, num_classes) > 0, "cvk_surface_distances: the workspace of N %d, %d classes is too large",
+                  N, num_classes);
+    CVK_CHECK_ARG(qden >= 1 && qden <= 10000 && qnum >= 0 && qnum <= qden,
+                  "cvk_surface_distances: percentile fraction %d / %d, need 0 <= qnum <= qden <= 10000", qnum, qden);
+    CVK_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "cvk_surface_distances: the workspace must be 16-byte aligned");
+    CVK_CHECK_ARG(((uintptr_t)d2 & 3u) == 0 && ((uintptr_t)record & 7u) == 0, "cvk_surface_distances: d2 or record misaligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int C = num_classes;
+    const SdLayout L = sd_layout(N, H, W, C);
+    char* ws = static_cast<char*>(workspace);
+    unsigned short* col = reinterpret_cast<unsigned short*>(ws + L.col);
+    unsigned char* bmap = reinterpret_cast<unsigned char*>(ws + L.bmap);
+    int* sel = reinterpret_cast<int*>(ws + L.sel);
+    unsigned long long* an = reinterpret_cast<unsigned long long*>(ws + L.an);
+    unsigned long long* aq = reinterpret_cast<unsigned long long*>(ws + L.aq);
+    unsigned* present = reinterpret_cast<unsigned*>(ws + L.present);
+    unsigned* amax = reinterpret_cast<unsigned*>(ws + L.amax);
+    unsigned* hist1 = reinterpret_cast<unsigned*>(ws + L.hist1);
+    unsigned* hist2 = reinterpret_cast<unsigned*>(ws + L.hist2);
+    const size_t n16 = (L.total - L.an) / 16;
+    hipLaunchKernelGGL(k_sd_clear, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint4*>(ws + L.an), n16);
+    const dim3 gpx(cvk_cdiv((long)L.M, 256));
+    hipLaunchKernelGGL(k_boundary_map, gpx, dim3(256), 0, s, pred, label, bmap, N, H, W, C, ignore_index);
+    hipLaunchKernelGGL(k_boundary_map, gpx, dim3(256), 0, s, label, label, bmap + L.M, N, H, W, C, ignore_index);
+    const int strips = cvk_cdiv(W, EDT_COL_TX);
+    hipLaunchKernelGGL(k_sd_cols, dim3((unsigned)N * strips, 2), dim3(256), (size_t)H * EDT_COL_TX, s, bmap, col, present, strips, N, H, W, C);
+    const size_t bytes_b = (size_t)2 * ((W + 3) & ~3) + sizeof(unsigned) * 2 * C * SD_SMALL, staged = bytes_b + (size_t)4 * W * C;
+    if (staged + 1024 <= EDT_LDS_LIMIT)
+        hipLaunchKernelGGL(k_sd_rows<true>, dim3((unsigned)N * H), dim3(256), staged, s, bmap, col, present, d2, an, aq, amax, hist1, L.nb1,
+                           L.M, H, W, C);
+    else
+        hipLaunchKernelGGL(k_sd_rows<false>, dim3((unsigned)N * H), dim3(256), bytes_b, s, bmap, col, present, d2, an, aq, amax, hist1,
+                           L.nb1, L.M, H, W, C);
+    const dim3 gseg((unsigned)(L.S < (size_t)SD_MAX_SEG_GROUPS ? L.S : (size_t)SD_MAX_SEG_GROUPS));
+    hipLaunchKernelGGL(k_sd_pick, gseg, dim3(256), 0, s, an, hist1, L.nb1, sel, L.S, C, qnum, qden);
+    hipLaunchKernelGGL(k_sd_refine, dim3((unsigned)((2 * L.M + 255) / 256)), dim3(256), 0, s, d2, bmap, sel, hist2, L.M, H * W, C);
+    hipLaunchKernelGGL(k_sd_finish, gseg, dim3(256), 0, s, an, aq, amax, sel, hist2, reinterpret_cast<long long*>(record), L.S, C, qnum, qden);
+    CVK_LAUNCH_RETURN("cvk_surface_distances");
 }

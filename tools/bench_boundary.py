@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pytorch_camvid_amd as A  # noqa: E402
 from pytorch_camvid_amd import _lib  # noqa: E402
 
-TILE = (32, 64)                     # BF_TH x BF_TW of csrc/loss_eval_optim.hip
+TILE = (32, 64)                     # BF_TH x BF_TW of csrc/boundary_f1.h
 K, IGNORE = 12, 11
 
 
