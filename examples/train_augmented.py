@@ -35,14 +35,15 @@ def synthetic_camvid(n, b, seed):
         yield np.clip(frames, 0, 255).astype(np.uint8), masks
 
 
-def validate(net, batches, tta, window, boundary, surface=None):
-    """(accuracy, mIoU, the contour scores of one validation pass: boundary F1 and / or HD95 and ASSD, None without a meter)."""
-    if boundary is None and surface is None:
+def validate(net, batches, tta, window, boundary, surface=None, biou=None):
+    """(accuracy, mIoU, the contour scores of one validation pass: boundary F1, HD95 and ASSD, Boundary IoU and the trimap mIoU,
+    each with its meter; None without a meter)."""
+    if boundary is None and surface is None and biou is None:
         acc, _, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window)
         return acc, miou, None
     rep = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window,
-                              boundary=[m for m in (boundary, surface) if m is not None])
-    return rep["accuracy"], rep["miou"], {k: rep[k] for k in ("bf", "hd95", "assd") if k in rep}
+                              boundary=[m for m in (boundary, surface, biou) if m is not None])
+    return rep["accuracy"], rep["miou"], {k: rep[k] for k in ("bf", "hd95", "assd", "biou", "trimap_miou") if k in rep}
 
 
 def bf_text(scores, percentile=95):
@@ -51,6 +52,10 @@ def bf_text(scores, percentile=95):
     out = f"  BF {scores['bf']:.4f}" if "bf" in scores else ""
     if "hd95" in scores:
         out += f"  HD{percentile:g} {scores['hd95']:.2f} px  ASSD {scores['assd']:.2f} px"
+    if "biou" in scores:
+        out += f"  BIoU {scores['biou']:.4f}"
+    if "trimap_miou" in scores:
+        out += "  trimap mIoU " + " ".join(f"{v:.4f}" for v in scores["trimap_miou"])
     return out
 
 
@@ -121,8 +126,21 @@ def main():
                     help="also report HD95 and the average symmetric surface distance of the validation pass, in pixels (cvk.SurfaceDistanceMeter)")
     ap.add_argument("--hd-percentile", type=float, default=95.0, metavar="Q",
                     help="with --surface-distance: the percentile of the Hausdorff distance, 0..100 (default 95; 100 is the Hausdorff distance)")
+    ap.add_argument("--boundary-iou", action="store_true",
+                    help="also report Boundary IoU (Cheng et al., CVPR 2021) of the validation pass (cvk.BoundaryIoUMeter)")
+    ap.add_argument("--biou-ratio", type=float, default=0.02, metavar="X",
+                    help="with --boundary-iou: the dilation as a fraction of the image diagonal (default 2 %%)")
+    ap.add_argument("--trimap-widths", default=None, metavar="W,W,...",
+                    help="also report the mIoU inside bands of these widths around the label boundaries, e.g. 1,2,4,8,16 (up to 8 increasing "
+                    "widths in 1..254; cvk.BoundaryIoUMeter)")
     a = ap.parse_args()
-    tta = window = boundary = surface = None
+    tta = window = boundary = surface = biou = None
+    if a.boundary_iou or a.trimap_widths:
+        try:
+            widths = tuple(int(v) for v in a.trimap_widths.split(",")) if a.trimap_widths else ()
+            biou = cvk.BoundaryIoUMeter(num_classes=12, ignore_index=11, ratio=a.biou_ratio, trimap_widths=widths)
+        except ValueError as e:
+            ap.error(f"--biou-ratio / --trimap-widths: {e}")
     if a.surface_distance:
         try:
             surface = cvk.SurfaceDistanceMeter(num_classes=12, ignore_index=11, percentile=a.hd_percentile)
@@ -269,12 +287,12 @@ def main():
             print(f"  grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of {n.numel()} steps "
                   f"(max_norm {a.clip_grad_norm:g})")
         val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
-        acc, miou, bf = validate(net, val, tta, window, boundary, surface)
+        acc, miou, bf = validate(net, val, tta, window, boundary, surface, biou)
         print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}{bf_text(bf, a.hd_percentile)}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
                 val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)    # the same frames again
-                acc_e, miou_e, bf_e = validate(net, val, tta, window, boundary, surface)
+                acc_e, miou_e, bf_e = validate(net, val, tta, window, boundary, surface, biou)
             print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}{bf_text(bf_e, a.hd_percentile)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
 
 

@@ -732,6 +732,36 @@ int cvk_surface_record_slots(void);
 int cvk_surface_distances(const int64_t* pred, const int64_t* label, int N, int H, int W, int num_classes, int ignore_index, int qnum,
                           int qden, void* workspace, int32_t* d2, int64_t* record, void* stream);
 
+/* ---- chessboard depth, Boundary IoU (Cheng et al., CVPR 2021) and trimap counts (not in the reference) ---------------------------
+ * Codes.  A pixel of an int64 map X [N][H][W] becomes one byte: its class when X is in [0, num_classes) and not ignore_index, 254 for
+ * any other value, 255 (void) where void_from == ignore_index.  void_from (nullable: X's own) is the label map; a prediction takes the
+ * label's void, as in cvk_boundary_counts.  1 <= num_classes <= 32.
+ * Depth.  For a pixel z whose code is a class, depth0(z) is the smallest k >= 1 for which the (2k+1) x (2k+1) square around z, clipped
+ * to the image, holds a pixel whose code differs from z's: void and 254 are codes like any other here and bound the regions beside
+ * them (unlike the contour rule above, where void never differs).  A pixel whose code is no class has depth 0.  With the image border
+ * counted as outside, depth1(z) = min(depth0(z), 1 + min(x, W-1-x, y, H-1-y)).  The class-c mask eroded d times by a 3 x 3 square is
+ * {code = c and depth > d}, its band {code = c and depth <= d}: depth1 with a zero pad around the image (Cheng's), depth0 without.
+ * cvk_cheb_depth writes code_u8 and depth_u8 (DEVICE uint8 [N][H][W]): depth_u8 = min(depth0, max_depth + 1) for border == 0 and
+ * min(depth0, max_depth + 1, the border term) for border == 1; 1 <= max_depth <= 254 is the largest band any consumer compares
+ * against, and no search runs farther.  workspace: DEVICE, cvk_cheb_workspace_bytes(N, H, W) bytes (0: unsupported sizes: W > 32768 or
+ * N H W >= 2^31); it holds the row distances.  Two launches: rows, then columns (depth0 = min over y' of max(|y - y'|, g(x, y')), g the
+ * row distance where the code is z's and 0 elsewhere).
+ * cvk_boundary_iou_counts reads the codes and depth0 maps (border == 0, max_depth >= dilation and >= the last width) of the masked
+ * prediction (p) and the label (l) and ADDS into DEVICE int64 counts[N][6][num_classes] (the caller zeroes it), per image and class c:
+ *   row 0 bG = label pixels of class c with depth1 <= dilation,  row 1 bP = the same of the prediction,
+ *   row 2 bI = pixels where both maps have class c and both are within their band,
+ *   row 3 aG, row 4 aP = the areas of the two masks,  row 5 aI = the area of their intersection.
+ * trimap (nullable): DEVICE int64 [nw][num_classes][num_classes], ADDED into: a pixel whose label and prediction are classes adds 1 at
+ * [i][label][prediction] for the smallest i with depth0 of the label <= widths[i] (the image border is no boundary; deeper pixels add
+ * nothing).  widths: HOST int [nw], strictly increasing, each in 1..254, 1 <= nw <= 8, copied into the launch arguments.
+ * 1 <= dilation <= 254.  One launch, integer atomics only: two runs agree bit for bit.  No allocation, no host sync. */
+int64_t cvk_cheb_workspace_bytes(int N, int H, int W);
+int cvk_cheb_depth(const int64_t* map, const int64_t* void_from, uint8_t* code_u8, uint8_t* depth_u8, void* workspace, int N, int H,
+                   int W, int num_classes, int ignore_index, int max_depth, int border, void* stream);
+int cvk_boundary_iou_counts(const uint8_t* code_p, const uint8_t* depth_p, const uint8_t* code_l, const uint8_t* depth_l,
+                            int64_t* counts, int64_t* trimap, const int* widths, int nw, int N, int H, int W, int num_classes,
+                            int dilation, void* stream);
+
 /* ---- multi-scale / flip test-time augmentation: the merge of the views' logits (not in the reference) ------------------
  * Bilinear resampling here is torch's F.interpolate(mode="bilinear", align_corners=False) with the sample position taken from
  * integers: for destination index d of `out` samples over `in` source samples, num = max((2 d + 1) in - out, 0), lower source

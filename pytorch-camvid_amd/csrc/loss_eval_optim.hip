@@ -16,6 +16,7 @@
 #include "edt.h"
 #include "boundary_f1.h"
 #include "surface_dist.h"
+#include "boundary_iou.h"
 #include "eval_meters.h"
 #include "optim_flat.h"
 #include "grad_flat.h"

@@ -10,6 +10,9 @@ in losses.py; their public names and constants are importable from here as befor
   BoundaryMeter, label_boundaries, boundary_tolerance, boundary_scores
                     <- the boundary F1 measure (BF score, Csurka et al. BMVC 2013; not in the reference): per-image, per-class
                        contour counts from one launch, scores on the host
+  BoundaryIoUMeter, chessboard_depth, boundary_dilation, boundary_iou_scores, trimap_scores
+                    <- Boundary IoU (Cheng et al. CVPR 2021) and the trimap curve (not in the reference) on a device chessboard
+                       depth map: integer counts per image and class, scores on the host
 """
 import torch
 
@@ -362,6 +365,241 @@ class SurfaceDistanceMeter:
     def compute(self):
         """`surface_distance_scores` of `records()`."""
         return surface_distance_scores(self.records().numpy(), self.ignore_index, self.percentile)
+
+
+CHEB_MAX_DEPTH = 254             # include/cvk.h: depths, dilations and trimap widths of the chessboard depth map
+CHEB_MAX_WIDTHS = 8
+BIOU_ROWS = 6                    # include/cvk.h: bG, bP, bI, aG, aP, aI
+
+
+def boundary_dilation(H, W, ratio=0.02):
+    """The dilation of Boundary IoU (Cheng et al., CVPR 2021) for an H x W image, in pixels: max(1, round(ratio * diagonal)), in exact
+    rational arithmetic (`ratio` is read through its decimal string, as `boundary_tolerance` reads its tolerance): the largest d with
+    (2 d - 1)^2 <= 4 ratio^2 (H^2 + W^2), and at least 1.  An exact half rounds up, where Python's round() of the float product goes to
+    the even neighbour.  The default is 2 % of the diagonal: 360 x 480 -> 12, 720 x 960 -> 24."""
+    import math
+    from fractions import Fraction
+    try:
+        if isinstance(ratio, bool):
+            raise ValueError
+        q = Fraction(str(ratio))
+    except (ValueError, ZeroDivisionError):
+        raise ValueError(f"ratio must be a non-negative number. Got: {ratio!r}") from None
+    if q < 0:
+        raise ValueError(f"ratio must not be negative. Got: {ratio!r}")
+    d = max(1, (math.isqrt((4 * q * q * (int(H) * int(H) + int(W) * int(W))).__floor__()) + 1) // 2)
+    if d > CHEB_MAX_DEPTH:
+        raise ValueError(f"a ratio of {ratio!r} on {H} x {W} pixels is a dilation of {d}; the kernels serve at most {CHEB_MAX_DEPTH}")
+    return int(d)
+
+
+def _check_cheb_classes(who, num_classes):
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= 32:
+        raise ValueError(f"{who} serves 1 to 32 classes. Got: {num_classes}")
+    return num_classes
+
+
+def _check_depth(name, d):
+    if isinstance(d, bool) or not isinstance(d, int) or not 1 <= d <= CHEB_MAX_DEPTH:
+        raise ValueError(f"{name} must be an integer in 1..{CHEB_MAX_DEPTH}. Got: {d!r}")
+    return d
+
+
+class _ChebBuffers:
+    """The device buffers of cvk_cheb_depth / cvk_boundary_iou_counts, kept per (N, H, W, device): the workspace and the meter's four
+    byte maps (code and depth of the prediction, code and depth of the label)."""
+
+    _buffers = {}
+
+    @staticmethod
+    def get(lib, N, H, W, device, want_maps):
+        key = (N, H, W, str(device))
+        ent = _ChebBuffers._buffers.get(key)
+        if ent is None:
+            nbytes = lib.cvk_cheb_workspace_bytes(N, H, W)
+            if nbytes <= 0:
+                raise ValueError(f"the chessboard depth serves rows of up to 32768 pixels and fewer than 2^31 pixels, got N = {N}, "
+                                 f"H = {H}, W = {W}")
+            ent = _ChebBuffers._buffers[key] = [torch.empty(nbytes, device=device, dtype=torch.uint8), None]
+        if want_maps and ent[1] is None:
+            ent[1] = torch.empty((4, N, H, W), device=device, dtype=torch.uint8)
+        return ent
+
+
+def _cheb_call(lib, m, v, code, depth, ws, num_classes, ignore_index, max_depth, border):
+    N, H, W = m.shape
+    check(lib.cvk_cheb_depth(m.data_ptr(), None if v is None else v.data_ptr(), code.data_ptr(), depth.data_ptr(), ws.data_ptr(), N, H, W,
+                             num_classes, ignore_index, max_depth, 1 if border else 0, _stream(m)), "cvk_cheb_depth")
+
+
+def chessboard_depth(labels, num_classes=12, ignore_index=11, void_from=None, border=True, max_depth=254):
+    """(code, depth), uint8 [N,H,W] each, of the int64 map `labels` on the GPU (include/cvk.h, cvk_cheb_depth).  `code` is the pixel's
+    class, 254 for a value that is no class, 255 where `void_from` (the label map of a prediction; None: the map's own) is
+    `ignore_index`.  `depth` of a class pixel is how many 3 x 3 erosions of its class's mask it survives, plus one: the smallest k for
+    which the (2k+1)-square around it holds another code, void and 254 included; with `border` the image border counts as outside too
+    (Cheng's zero pad), without it the border bounds nothing.  Pixels deeper than `max_depth` hold `max_depth + 1`; a pixel that is no
+    class holds 0.  The class-c mask eroded d <= max_depth times is (code == c) & (depth > d).  No host sync."""
+    _check_boundary_maps("chessboard_depth", labels, labels if void_from is None else void_from)
+    _check_cheb_classes("chessboard_depth", num_classes)
+    _check_depth("max_depth", max_depth)
+    lib = _lib.load()
+    m = labels.contiguous()
+    v = None if void_from is None else void_from.contiguous()
+    N, H, W = m.shape
+    ws, _ = _ChebBuffers.get(lib, N, H, W, m.device, False)
+    code = torch.empty((N, H, W), device=m.device, dtype=torch.uint8)
+    depth = torch.empty((N, H, W), device=m.device, dtype=torch.uint8)
+    _cheb_call(lib, m, v, code, depth, ws, num_classes, int(ignore_index), max_depth, border)
+    return code, depth
+
+
+def boundary_iou_scores(counts, ignore_index=None):
+    """Boundary IoU (Cheng et al., CVPR 2021) from per-image, per-class counts [images, 6, K] (rows: bG, bP, bI the band pixels of the
+    label, of the masked prediction and of both; aG, aP, aI the same of the whole masks), in float64 on the host.  Returns
+      "biou": per class sum bI / (sum bG + sum bP - sum bI) over all images (pooled over the set, as the mIoU is), then the mean over
+          the classes with a non-zero denominator (NaN without one),
+      "biou_per_class": float64 [K], NaN where the denominator is 0 and at ignore_index,
+      "biou_image": the mean over the images with an evaluated class of the image's mean boundary IoU over its classes with
+          bG + bP > 0 (as the boundary F1 averages),
+      "min_iou_per_class": min(mask IoU, boundary IoU) of the pooled counts, the quantity Boundary AP / PQ use,
+      "images": how many images had an evaluated class."""
+    import numpy as np
+    c = np.asarray(counts, dtype=np.int64)
+    if c.ndim != 3 or c.shape[1] != BIOU_ROWS:
+        raise ValueError(f"expected counts of shape [images, {BIOU_ROWS}, K], got {list(c.shape)}")
+    K = c.shape[2]
+
+    def ratio(i, a, b):
+        den = (a + b - i).astype(np.float64)
+        return np.divide(i.astype(np.float64), den, out=np.full(den.shape, np.nan), where=den > 0)
+
+    pooled = c.sum(axis=0)
+    per_class = ratio(pooled[2], pooled[0], pooled[1])
+    mask_iou = ratio(pooled[5], pooled[3], pooled[4])
+    if ignore_index is not None and 0 <= ignore_index < K:
+        per_class[ignore_index] = mask_iou[ignore_index] = np.nan
+    ev = ~np.isnan(per_class)
+    per_image = ratio(c[:, 2], c[:, 0], c[:, 1])          # [images, K], NaN where bG + bP == 0 (the union is then 0 too)
+    if ignore_index is not None and 0 <= ignore_index < K:
+        per_image[:, ignore_index] = np.nan
+    evi = ~np.isnan(per_image)
+    ni = evi.sum(axis=1)
+    image = np.divide(np.where(evi, per_image, 0.0).sum(axis=1), ni, out=np.full(ni.shape, np.nan), where=ni > 0)
+    scored = ni > 0
+    return {"biou": float(per_class[ev].mean()) if ev.any() else float("nan"), "biou_per_class": per_class,
+            "biou_image": float(image[scored].mean()) if scored.any() else float("nan"),
+            "min_iou_per_class": np.where(np.isnan(per_class) | np.isnan(mask_iou), np.nan, np.fmin(per_class, mask_iou)),
+            "images": int(scored.sum())}
+
+
+def _check_widths(widths):
+    try:
+        ws = tuple(widths)
+    except TypeError:
+        raise ValueError(f"trimap_widths must be a sequence of integers. Got: {widths!r}") from None
+    if len(ws) > CHEB_MAX_WIDTHS:
+        raise ValueError(f"at most {CHEB_MAX_WIDTHS} trimap widths. Got: {len(ws)}")
+    for w in ws:
+        _check_depth("a trimap width", w)
+    if any(b <= a for a, b in zip(ws, ws[1:])):
+        raise ValueError(f"trimap widths must be strictly increasing. Got: {ws!r}")
+    return ws
+
+
+def trimap_scores(conf, widths, ignore_index=None):
+    """The trimap curve (Kohli et al.; DeepLab) from the bins of `BoundaryIoUMeter.trimap_counts()`, int64 [nw, K, K]: bin i holds the
+    confusion matrix [label, prediction] of the non-void pixels whose chessboard depth in the label map is above widths[i - 1] and at
+    most widths[i]; the band of width widths[i] is the running sum.  In float64 on the host, per width: "trimap_miou" the mean over
+    the classes other than ignore_index with a non-zero union of diag / (row sum + column sum - diag) (NaN without one),
+    "trimap_accuracy" trace / total (NaN for an empty band), "trimap_pixels" the band's total (int64), and "widths"."""
+    import numpy as np
+    ws = _check_widths(widths)
+    b = np.asarray(conf, dtype=np.int64)
+    if b.ndim != 3 or b.shape[0] != len(ws) or b.shape[1] != b.shape[2]:
+        raise ValueError(f"expected bins of shape [{len(ws)}, K, K], got {list(b.shape)}")
+    K = b.shape[1]
+    cum = np.cumsum(b, axis=0)
+    miou, acc = np.full(len(ws), np.nan), np.full(len(ws), np.nan)
+    pixels = cum.sum(axis=(1, 2)).astype(np.int64)
+    for i in range(len(ws)):
+        diag = np.diagonal(cum[i]).astype(np.float64)
+        union = cum[i].sum(axis=1) + cum[i].sum(axis=0) - np.diagonal(cum[i])
+        ev = union > 0
+        if ignore_index is not None and 0 <= ignore_index < K:
+            ev[ignore_index] = False
+        if ev.any():
+            miou[i] = (diag[ev] / union[ev]).mean()
+        if pixels[i] > 0:
+            acc[i] = diag.sum() / float(pixels[i])
+    return {"trimap_miou": miou, "trimap_accuracy": acc, "trimap_pixels": pixels, "widths": ws}
+
+
+class BoundaryIoUMeter:
+    """Boundary IoU (Cheng et al., CVPR 2021) and the trimap curve (mIoU inside bands of growing width around the label boundaries;
+    Kohli et al., DeepLab) of predictions against labels.  Both read one device map: the chessboard depth of every pixel inside its
+    own region (`chessboard_depth`), made by two launches per map; one more launch counts per image and class the band and mask
+    pixels of both maps and of their intersection, and per width the confusion matrix of the band (exact integers: two runs agree
+    bit for bit).  No host sync until `counts()` / `trimap_counts()` / `compute()`.  The dilation is `ratio` times the image diagonal
+    of each batch (`boundary_dilation`; Cheng's default 0.02), or `dilation` pixels; the band of a mask is what `dilation` 3 x 3
+    erosions with a zero pad remove.  `trimap_widths`: up to 8 strictly increasing widths in 1..254; the image border bounds no
+    trimap band.  Pixels whose label is `ignore_index` are void in both maps and bound the regions beside them."""
+
+    def __init__(self, num_classes=12, ignore_index=11, ratio=0.02, dilation=None, trimap_widths=()):
+        self.num_classes = _check_cheb_classes("BoundaryIoUMeter", num_classes)
+        self.ignore_index, self.ratio = int(ignore_index), ratio
+        self.dilation = None if dilation is None else _check_depth("dilation", dilation)
+        if dilation is None:
+            boundary_dilation(1, 1, ratio)                # a bad ratio fails here, not in the first batch
+        self.trimap_widths = _check_widths(trimap_widths)
+        import ctypes
+        self._widths = (ctypes.c_int * max(1, len(self.trimap_widths)))(*self.trimap_widths)
+        self.reset()
+
+    def reset(self):
+        self._parts, self._trimap = [], None
+
+    def update(self, pred, label):
+        _check_boundary_maps("BoundaryIoUMeter.update", pred, label)
+        lib = _lib.load()
+        N, H, W = pred.shape
+        K, nw = self.num_classes, len(self.trimap_widths)
+        d = self.dilation if self.dilation is not None else boundary_dilation(H, W, self.ratio)
+        max_depth = max((d,) + self.trimap_widths)
+        p = pred.contiguous(); l = label.contiguous()
+        ws, maps = _ChebBuffers.get(lib, N, H, W, p.device, True)
+        _cheb_call(lib, p, l, maps[0], maps[1], ws, K, self.ignore_index, max_depth, False)
+        _cheb_call(lib, l, None, maps[2], maps[3], ws, K, self.ignore_index, max_depth, False)
+        part = torch.zeros((N, BIOU_ROWS, K), device=p.device, dtype=torch.int64)
+        if nw and (self._trimap is None or self._trimap.device != p.device):
+            if self._trimap is not None:
+                raise ValueError("BoundaryIoUMeter.update: the batches of one meter must be on one device")
+            self._trimap = torch.zeros((nw, K, K), device=p.device, dtype=torch.int64)
+        check(lib.cvk_boundary_iou_counts(maps[0].data_ptr(), maps[1].data_ptr(), maps[2].data_ptr(), maps[3].data_ptr(), part.data_ptr(),
+                                          self._trimap.data_ptr() if nw else None, self._widths if nw else None, nw, N, H, W, K, d,
+                                          _stream(p)), "cvk_boundary_iou_counts")
+        self._parts.append(part)
+
+    def counts(self):
+        """int64 [images, 6, num_classes] on the host (rows bG, bP, bI, aG, aP, aI), in the order of the updates — one device->host
+        copy."""
+        if not self._parts:
+            return torch.zeros((0, BIOU_ROWS, self.num_classes), dtype=torch.int64)
+        return (self._parts[0] if len(self._parts) == 1 else torch.cat(self._parts)).cpu()
+
+    def trimap_counts(self):
+        """int64 [widths, num_classes, num_classes] on the host: per width the confusion matrix [label, prediction] of the pixels whose
+        depth in the label map falls into that width's bin (`trimap_scores` takes the running sum)."""
+        K = self.num_classes
+        if self._trimap is None:
+            return torch.zeros((len(self.trimap_widths), K, K), dtype=torch.int64)
+        return self._trimap.cpu()
+
+    def compute(self):
+        """`boundary_iou_scores` of `counts()`, and with widths `trimap_scores` of `trimap_counts()` too."""
+        out = boundary_iou_scores(self.counts().numpy(), self.ignore_index)
+        if self.trimap_widths:
+            out.update(trimap_scores(self.trimap_counts().numpy(), self.trimap_widths, self.ignore_index))
+        return out
 
 
 WEIGHT_METHODS = ("median_frequency", "enet")
@@ -727,7 +965,7 @@ class TestTimeAugmentation:
 
 def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None, contour_meters=()):
     """evaluate / evaluate_report with test-time augmentation: (meter, the per-batch losses of the loss view: empty without one).
-    `contour_meters` (BoundaryMeter, SurfaceDistanceMeter) see the predictions the ConfusionMeter sees."""
+    `contour_meters` (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter) see the predictions the ConfusionMeter sees."""
     meter, losses = None, []
 
     def keep_loss(masks, want):
@@ -789,12 +1027,12 @@ SURFACE_REPORT_KEYS = ("hd95", "hd", "assd", "hd95_per_class", "hd_per_class", "
 
 
 def _contour_meters(boundary):
-    """The meters behind evaluate_report's `boundary`: None, one meter, or a tuple / list with at most one meter of either kind."""
+    """The meters behind evaluate_report's `boundary`: None, one meter, or a tuple / list with at most one meter of each kind."""
     meters = list(boundary) if isinstance(boundary, (tuple, list)) else [] if boundary is None else [boundary]
     for m in meters:
-        if not isinstance(m, (BoundaryMeter, SurfaceDistanceMeter)):
+        if not isinstance(m, (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter)):
             raise ValueError("boundary must be a BoundaryMeter or None, or a SurfaceDistanceMeter, or a tuple or list of one of each. "
-                             f"Got: {type(m).__name__}")
+                             f"A BoundaryIoUMeter is taken the same way. Got: {type(m).__name__}")
     if len({type(m) for m in meters}) != len(meters):
         raise ValueError("boundary holds two meters of one kind: their scores would share the report's keys")
     return meters
@@ -803,7 +1041,11 @@ def _contour_meters(boundary):
 def _with_boundary(report, contour_meters):
     for m in contour_meters:
         scores = m.compute()
-        for k in SURFACE_REPORT_KEYS if isinstance(m, SurfaceDistanceMeter) else ("bf", "bf_per_class"):
+        if isinstance(m, BoundaryIoUMeter):
+            keys = ("biou", "biou_per_class") + (("trimap_miou",) if m.trimap_widths else ())
+        else:
+            keys = SURFACE_REPORT_KEYS if isinstance(m, SurfaceDistanceMeter) else ("bf", "bf_per_class")
+        for k in keys:
             report[k] = scores[k]
     return report
 
@@ -819,7 +1061,8 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
     (the boundary F1 measure) and "bf_per_class"; the meter keeps its counts for `boundary.compute()`.  `boundary` also takes a
     SurfaceDistanceMeter, or a tuple or list with one meter of either kind: a SurfaceDistanceMeter is reset and fed the same way, and
     the report gains "hd95", "hd", "assd" and their "_per_class" arrays; the meter's `compute()` has the rest (unmatched classes,
-    images)."""
+    images).  A BoundaryIoUMeter is a third kind, alone or beside one of each of the others: the report gains "biou" and
+    "biou_per_class", and "trimap_miou" when the meter has trimap widths."""
     _check_tta_window("evaluate_report", tta, window)
     contour_meters = _contour_meters(boundary)
     loss_fn = loss_fn or CrossEntropyLoss()
