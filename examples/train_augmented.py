@@ -10,6 +10,8 @@ package); random.seed makes the augmentation decisions of the reference's Compos
   python examples/train_augmented.py --graphed --optimizer sgd -lr 0.05 --clip-grad-norm 1.0    # the same with momentum SGD (cvk.FlatSGD)
   python examples/train_augmented.py --graphed --ema-decay 0.999 --ema-warmup   # weight EMA inside the captured step, validated too
   python examples/train_augmented.py --net segnet --teacher unet --teacher-weights unet.pth --graphed   # distil the UNet into SegNet
+  python examples/train_augmented.py --crop 360,480 --scale-range 0.5,2.0 --window-crop 360,480   # train on random scaled crops
+        # (transforms.crop_transforms: rescale, class-balanced crop, pad with void), validate the full frames in sliding windows
 """
 import argparse
 import os
@@ -133,6 +135,13 @@ def main():
     ap.add_argument("--trimap-widths", default=None, metavar="W,W,...",
                     help="also report the mIoU inside bands of these widths around the label boundaries, e.g. 1,2,4,8,16 (up to 8 increasing "
                     "widths in 1..254; cvk.BoundaryIoUMeter)")
+    ap.add_argument("--crop", default=None, metavar="H,W",
+                    help="train on random scaled crops of this size, e.g. 360,480 (transforms.crop_transforms: random rescale, a crop chosen "
+                    "on the device by the cat_max_ratio rule, pad with the ignore label), and validate the full 720x960 frames; with "
+                    "--window-crop in sliding windows")
+    ap.add_argument("--scale-range", default="0.5,2.0", metavar="A,B", help="with --crop: the range the rescale ratio is drawn from")
+    ap.add_argument("--cat-max-ratio", type=float, default=0.75, metavar="R",
+                    help="with --crop: a candidate crop is taken when its largest class holds less than R of its labelled pixels (1: the first)")
     a = ap.parse_args()
     tta = window = boundary = surface = biou = None
     if a.boundary_iou or a.trimap_widths:
@@ -230,6 +239,14 @@ def main():
         teacher.eval().requires_grad_(False)
         kd = cvk.DistillationLoss(1.0, a.kd_weight, a.kd_temperature, weight=weight, distill_ignored=a.kd_ignored)
     train_tf, valid_tf = transforms.train_transforms(), transforms.valid_transforms()
+    if a.crop:
+        try:
+            train_tf = transforms.crop_transforms(crop_size=tuple(int(v) for v in a.crop.split(",")),
+                                                  ratio_range=tuple(float(v) for v in a.scale_range.split(",")), cat_max_ratio=a.cat_max_ratio)
+        except ValueError as e:
+            ap.error(f"--crop / --scale-range / --cat-max-ratio: {e}")
+        # the full frames, not resized: the network sees them whole, or with --window-crop in windows of the training size
+        valid_tf = transforms.Compose([transforms.ToTensor(), transforms.Normalize(transforms.CAMVID_MEAN, transforms.CAMVID_STD)])
     step = None
     for epoch in range(1, a.epochs + 1):
         net.train()
@@ -272,6 +289,9 @@ def main():
         torch.cuda.synchronize()
         dt = time.time() - t0
         print(f"epoch {epoch}: loss {loss.item():.4f}  {a.b * a.iters / dt:.1f} img/s (incl. host data synthesis)")
+        if a.crop:                                                  # the device table of the last batch: candidate, offy, offx, passed
+            sel = train_tf.last_selection.cpu()
+            print(f"  crops {a.crop}: last batch took candidates {sel[:, 0].tolist()}, {int(sel[:, 3].sum())} of {len(sel)} by the ratio rule")
         if kd is not None:                                          # device views of the last step's record
             kd_h, kd_k = kd.last_terms.tolist()
             print(f"  distillation: H {kd_h:.4f}  K {kd_k:.4f}  arg-max agreement with the teacher {kd.last_agreement.item():.4f}  "

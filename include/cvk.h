@@ -835,6 +835,46 @@ int cvk_augment_u8(const uint8_t* frames, const void* masks, int mask_bytes, int
                    const cvk_augment_record* records, const float* mean3, const float* std3, float* out, int64_t* out_masks,
                    uint8_t* out_u8, void* stream);
 
+/* ---- crop training on device: random rescale, class-balanced crop, pad, blur, LUT, flip (mmseg's RandomResize + RandomCrop +
+ * Pad; the reference's own RandomScale, transforms.py:63-127, is the one-candidate case with negative offsets) --------------
+ * Per sample n the frame is rescaled to a VIRTUAL Hr x Wr image that never reaches memory: cv2 INTER_LINEAR as in cvk_augment_u8
+ * (f = (d + 0.5) * s - 0.5 in double, clamped at both edges, fp32 blend, rounded half-up) and INTER_NEAREST for the mask
+ * (min(floor(d * s), n - 1) in double), with the steps s = sy, sx of the record (source pixels per resized pixel; Hs / Hr for a
+ * cv2 dsize, 1 / fx for a cv2 factor).  Then the optional Gaussian of ksize taps (REFLECT_101 at the borders of the RESIZED image)
+ * and the optional LUT, both as in cvk_augment_u8.  Pixel (y, x) of the hc x wc output shows resized pixel (y + offy, x + offx);
+ * offsets are signed and whatever falls outside the resized image is pad: mask pad_label, uint8 0, float 0.0 in all four channels
+ * (pad_normalized == 0) or black normalised, (0 - mean) / std (pad_normalized != 0).  flip mirrors the whole wc-wide canvas, pad
+ * included.
+ * A record carries ncand (1..11; clamped to that range) candidate offsets.  cvk_crop_select counts, per candidate, the resized
+ * labels inside (window ∩ resized image) per value; labels equal to ignore_index or outside [0, 256) are not counted.  Candidates
+ * 0 .. ncand - 2 are tested in order; one passes iff more than one value has a non-zero count and
+ * (double)max_count / (double)sum_count < cat_max_ratio; the first that passes is chosen, else candidate ncand - 1 (mmseg's
+ * RandomCrop loop).  counts: DEVICE uint32 [N][11][256], cleared by the call, then the counts of candidates 0 .. ncand - 1;
+ * selection: DEVICE int32 [N][4] = {candidate, offy, offx, passed}.  Integer atomics only: both tables are exact.  Three launches.
+ * cvk_crop_augment_u8 reads the selection rows on the device and writes out float32 [N,hc,wc,4] (cvk_preprocess_u8's expression,
+ * fourth channel 0), out_masks int64 [N,hc,wc] and out_u8 (nullable) uint8 [N,hc,wc,3].  One launch.  mean3 / std3 are HOST
+ * pointers.  Neither call allocates or synchronises.  hc * wc < 2^31.
+ * sizeof(cvk_crop_record) == 416 (cvk_crop_record_bytes()): every field sits at a multiple of its own size, no implicit padding. */
+typedef struct cvk_crop_record {
+    double  sy, sx;              /*   0: source pixels per resized pixel */
+    int32_t Hr, Wr;              /*  16: size of the resized image, each >= 1 */
+    int32_t ncand;               /*  24: candidates in use, 1..11; the last one is the unconditional fallback */
+    int32_t offy[11];            /*  28 */
+    int32_t offx[11];            /*  72 */
+    float   taps[9];             /* 116: taps[0 .. ksize-1] */
+    uint8_t flip;                /* 152: != 0: mirror left-right */
+    uint8_t use_lut;             /* 153: != 0: apply lut */
+    uint8_t ksize;               /* 154: 3, 5, 7 or 9; anything else: no blur */
+    uint8_t reserved[5];         /* 155 */
+    uint8_t lut[256];            /* 160 */
+} cvk_crop_record;
+int cvk_crop_record_bytes(void);
+int cvk_crop_select(const void* masks, int mask_bytes, int N, int Hs, int Ws, int hc, int wc, const cvk_crop_record* records,
+                    int ignore_index, double cat_max_ratio, uint32_t* counts, int32_t* selection, void* stream);
+int cvk_crop_augment_u8(const uint8_t* frames, const void* masks, int mask_bytes, int N, int Hs, int Ws, int hc, int wc,
+                        const cvk_crop_record* records, const int32_t* selection, const float* mean3, const float* std3,
+                        int64_t pad_label, int pad_normalized, float* out, int64_t* out_masks, uint8_t* out_u8, void* stream);
+
 /* ---- fused AdamW over a flat fp32 buffer (torch.optim.AdamW: train.py:100,133) -------------------------------- */
 int cvk_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);

@@ -239,6 +239,10 @@ SIGNATURES = {
     "cvk_augment_record_bytes": (c_int, []),
     "cvk_augment_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(ctypes.c_float),
                                ctypes.POINTER(ctypes.c_float), c_vp, c_vp, c_vp, c_vp]),
+    "cvk_crop_record_bytes": (c_int, []),
+    "cvk_crop_select": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, ctypes.c_double, c_vp, c_vp, c_vp]),
+    "cvk_crop_augment_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, ctypes.POINTER(ctypes.c_float),
+                                    ctypes.POINTER(ctypes.c_float), c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "cvk_bf16s_rows_pad": (c_int, [c_int]),
     "cvk_bf16s_stat_partials": (c_int, [c_int, c_int, c_int]),
     "cvk_bf16s_stat_partials_c": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -296,6 +300,12 @@ _lock = threading.Lock()
 class AugmentRecord(ctypes.Structure):  # include/cvk.h cvk_augment_record (its size: cvk_augment_record_bytes())
     _fields_ = [("flip", ctypes.c_int32), ("ksize", ctypes.c_int32), ("use_lut", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("taps", ctypes.c_float * 12), ("lut", ctypes.c_uint8 * 256)]
+
+
+class CropRecord(ctypes.Structure):     # include/cvk.h cvk_crop_record (its size: cvk_crop_record_bytes())
+    _fields_ = [("sy", ctypes.c_double), ("sx", ctypes.c_double), ("Hr", ctypes.c_int32), ("Wr", ctypes.c_int32), ("ncand", ctypes.c_int32),
+                ("offy", ctypes.c_int32 * 11), ("offx", ctypes.c_int32 * 11), ("taps", ctypes.c_float * 9), ("flip", ctypes.c_uint8),
+                ("use_lut", ctypes.c_uint8), ("ksize", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 5), ("lut", ctypes.c_uint8 * 256)]
 
 
 class AdamwHyper(ctypes.Structure):     # include/cvk.h cvk_adamw_hyper

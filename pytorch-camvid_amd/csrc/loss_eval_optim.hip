@@ -10,6 +10,7 @@
 //   eval_meters.h   class histogram, arg-max, confusion counts
 //   optim_flat.h    AdamW, momentum SGD, the per-iteration log row
 //   grad_flat.h     global-norm clipping and gradient accumulation
+//   crop_aug.h      crop training: class-balanced window selection, resize + crop + pad + blur + LUT + flip
 // A new subject gets a header of that kind, not lines here.
 #include "cvk_common.h"
 #include "loss_rows.h"
@@ -20,6 +21,7 @@
 #include "eval_meters.h"
 #include "optim_flat.h"
 #include "grad_flat.h"
+#include "crop_aug.h"
 
 namespace {
 
@@ -2149,27 +2151,7 @@ struct AugArgs {
     uint8_t* out_u8;
 };
 
-__device__ __forceinline__ int aug_reflect101(int x, int n) {
-    if ((unsigned)x < (unsigned)n) return x;
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;
-    x %= p;
-    if (x < 0) x += p;
-    return x < n ? x : p - x;
-}
-
-__device__ __forceinline__ float aug_round_u8(float v) { return fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f); }
-
-// cv2 INTER_LINEAR source coordinate: f = (d + 0.5) * scale - 0.5, i = floor(f), weight f - i; clamped at both edges
-__device__ __forceinline__ void aug_coord(int d, double scale, int n, int& i0, int& i1, float& a) {
-    const double f = (d + 0.5) * scale - 0.5;
-    int i = (int)floor(f);
-    a = (float)(f - i);
-    if (i < 0) { i = 0; a = 0.f; }
-    if (i >= n - 1) { i = n - 1; a = 0.f; }
-    i0 = i;
-    i1 = i + 1 < n ? i + 1 : n - 1;
-}
+// aug_reflect101, aug_round_u8 and aug_coord: crop_aug.h
 
 template <int R>
 __device__ __forceinline__ void aug_tile(const AugArgs& A, const cvk_augment_record* rec, float* s_in, float* s_h,

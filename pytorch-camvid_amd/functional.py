@@ -1151,7 +1151,10 @@ class DevicePrefetcher:
     With `transforms` (a `transforms.Compose`, e.g. `transforms.train_transforms()`) each batch's augmentation parameters are
     drawn while it is staged, in batch order, and go up with its frames (pinned records, same side stream); the frames then pass
     through `cvk_augment_u8` instead of `preprocess_uint8` (masks uint8 or int64; uint8 ones travel at 1 byte per pixel) and the
-    masks come back int64 at the transforms' output size.  `transforms` supplies its own Normalize mean / std."""
+    masks come back int64 at the transforms' output size.  `transforms` supplies its own Normalize mean / std.
+    A `transforms.CropCompose` (e.g. `transforms.crop_transforms()`) is served the same way: its records (`cvk_crop_record`) are
+    drawn while the batch is staged and go up from the pinned slot; `cvk_crop_select` and `cvk_crop_augment_u8` run on the
+    consumer's stream and the batch comes back at the crop size."""
 
     def __init__(self, batches, device="cuda", mean=CAMVID_MEAN, std=CAMVID_STD, transforms=None):
         self.it = iter(batches)
@@ -1192,10 +1195,15 @@ class DevicePrefetcher:
         pm = self._pinned(slot, 1, masks); pm.copy_(masks)
         pr = None
         if self.transforms is not None:
-            from .transforms import RECORD
+            from .transforms import RECORD, CROP_RECORD, CropCompose
             N = frames.shape[0]
-            pr = self._pinned(slot, 2, torch.empty(N * RECORD.itemsize, dtype=torch.uint8))
-            self.transforms.pack([self.transforms.draw() for _ in range(N)], out=pr.numpy().view(RECORD))
+            if isinstance(self.transforms, CropCompose):        # the draws need the source size; everything else is the same
+                pr = self._pinned(slot, 2, torch.empty(N * CROP_RECORD.itemsize, dtype=torch.uint8))
+                self.transforms.pack([self.transforms.draw(frames.shape[1], frames.shape[2]) for _ in range(N)],
+                                     out=pr.numpy().view(CROP_RECORD))
+            else:
+                pr = self._pinned(slot, 2, torch.empty(N * RECORD.itemsize, dtype=torch.uint8))
+                self.transforms.pack([self.transforms.draw() for _ in range(N)], out=pr.numpy().view(RECORD))
         with torch.cuda.stream(self.stream):
             gf = pf.to(self.dev, non_blocking=True)
             gm = pm.to(self.dev, non_blocking=True)
@@ -1217,8 +1225,10 @@ class DevicePrefetcher:
         gf.record_stream(cur); gm.record_stream(cur)
         self._stage()                                   # upload of the following batch overlaps the consumer's step
         if self.transforms is not None:
-            from .transforms import augment_u8
+            from .transforms import augment_u8, CropCompose
             gr.record_stream(cur)
             t = self.transforms
+            if isinstance(t, CropCompose):
+                return t.apply(gf, gm, gr)                      # cvk_crop_select + cvk_crop_augment_u8 on the consumer's stream
             return augment_u8(gf, gm, gr, t.out_hw(gf.shape[1], gf.shape[2]), t.mean, t.std)
         return preprocess_uint8(gf, self.mean, self.std), gm
