@@ -37,15 +37,16 @@ def synthetic_camvid(n, b, seed):
         yield np.clip(frames, 0, 255).astype(np.uint8), masks
 
 
-def validate(net, batches, tta, window, boundary, surface=None, biou=None):
+def validate(net, batches, tta, window, boundary, surface=None, biou=None, region=None):
     """(accuracy, mIoU, the contour scores of one validation pass: boundary F1, HD95 and ASSD, Boundary IoU and the trimap mIoU,
-    each with its meter; None without a meter)."""
-    if boundary is None and surface is None and biou is None:
+    fragmentation and the mIoU without small regions, each with its meter; None without a meter)."""
+    if boundary is None and surface is None and biou is None and region is None:
         acc, _, miou = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window)
         return acc, miou, None
     rep = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, tta=tta, window=window,
-                              boundary=[m for m in (boundary, surface, biou) if m is not None])
-    return rep["accuracy"], rep["miou"], {k: rep[k] for k in ("bf", "hd95", "assd", "biou", "trimap_miou") if k in rep}
+                              boundary=[m for m in (boundary, surface, biou, region) if m is not None])
+    return rep["accuracy"], rep["miou"], {k: rep[k] for k in ("bf", "hd95", "assd", "biou", "trimap_miou", "fragmentation", "miou_filtered")
+                                      if k in rep}
 
 
 def bf_text(scores, percentile=95):
@@ -58,6 +59,8 @@ def bf_text(scores, percentile=95):
         out += f"  BIoU {scores['biou']:.4f}"
     if "trimap_miou" in scores:
         out += "  trimap mIoU " + " ".join(f"{v:.4f}" for v in scores["trimap_miou"])
+    if "miou_filtered" in scores:
+        out += f"  mIoU without small regions {scores['miou_filtered']:.4f}  fragmentation {scores['fragmentation']:.2f}"
     return out
 
 
@@ -142,8 +145,17 @@ def main():
     ap.add_argument("--scale-range", default="0.5,2.0", metavar="A,B", help="with --crop: the range the rescale ratio is drawn from")
     ap.add_argument("--cat-max-ratio", type=float, default=0.75, metavar="R",
                     help="with --crop: a candidate crop is taken when its largest class holds less than R of its labelled pixels (1: the first)")
+    ap.add_argument("--min-region", type=int, default=None, metavar="A",
+                    help="also report the mIoU after regions of fewer than A pixels went to their neighbours' class, and the fragmentation "
+                    "(predicted regions over label regions; cvk.RegionMeter)")
+    ap.add_argument("--region-connectivity", type=int, default=4, choices=(4, 8), help="with --min-region: 4- or 8-connected regions")
     a = ap.parse_args()
-    tta = window = boundary = surface = biou = None
+    tta = window = boundary = surface = biou = region = None
+    if a.min_region is not None:
+        try:
+            region = cvk.RegionMeter(num_classes=12, ignore_index=11, min_area=a.min_region, connectivity=a.region_connectivity)
+        except ValueError as e:
+            ap.error(f"--min-region: {e}")
     if a.boundary_iou or a.trimap_widths:
         try:
             widths = tuple(int(v) for v in a.trimap_widths.split(",")) if a.trimap_widths else ()
@@ -307,12 +319,12 @@ def main():
             print(f"  grad norm max {n.max().item():.4e}  clipped {(n > a.clip_grad_norm).float().mean().item() * 100:.0f} % of {n.numel()} steps "
                   f"(max_norm {a.clip_grad_norm:g})")
         val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)
-        acc, miou, bf = validate(net, val, tta, window, boundary, surface, biou)
+        acc, miou, bf = validate(net, val, tta, window, boundary, surface, biou, region)
         print(f"  validation: accuracy {acc:.4f}  mIoU {miou:.4f}{bf_text(bf, a.hd_percentile)}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
                 val = cvk.DevicePrefetcher(synthetic_camvid(2, a.b, 1000), transforms=valid_tf)    # the same frames again
-                acc_e, miou_e, bf_e = validate(net, val, tta, window, boundary, surface, biou)
+                acc_e, miou_e, bf_e = validate(net, val, tta, window, boundary, surface, biou, region)
             print(f"  validation, EMA weights: accuracy {acc_e:.4f}  mIoU {miou_e:.4f}{bf_text(bf_e, a.hd_percentile)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
 
 

@@ -762,6 +762,35 @@ int cvk_boundary_iou_counts(const uint8_t* code_p, const uint8_t* depth_p, const
                             int64_t* counts, int64_t* trimap, const int* widths, int nw, int N, int H, int W, int num_classes,
                             int dilation, void* stream);
 
+/* ---- connected components of a class map and the removal of small regions (not in the reference) --------------------------------
+ * Codes.  A pixel of an int64 map X [N][H][W] has the code X when X is in [0, num_classes) and not ignore_index; every other value is
+ * void, one code.  1 <= num_classes <= 32, N H W < 2^31, connectivity 4 or 8.
+ * A component is a maximal set of pixels of one image with equal code, connected under `connectivity`; void pixels form components
+ * too.  cvk_cc_label writes, DEVICE int32 [N][H][W] each: labels = y' W + x' of the first pixel of the pixel's component in row-major
+ * order (so labels[p] <= index(p), with equality at exactly one pixel per component) and area = the size of the pixel's component, at
+ * every pixel.  Four launches: a union-find per 32 x 64 tile in LDS, a lock-free merge over the tile seams (atomicMin; no work-group
+ * waits for another), a flatten pass that counts areas by integer atomics, and the spread of the areas.  The result does not depend
+ * on the order of arrival.
+ * cvk_cc_filter reads map and the labels and area cvk_cc_label made of it under the same num_classes, ignore_index and connectivity
+ * and writes out (DEVICE int64 [N][H][W], not overlapping map).  A class component is small iff area < min_area (min_area >= 1; 1
+ * removes nothing); void components are never small.  mode 0 (fill): every pixel of a small component becomes fill_value.  mode 1
+ * (neighbour): votes[k] of a small component S = the number of ordered pairs (p, q), p in S, q a neighbour of p inside the image under
+ * `connectivity`, q of class k and q's component not small; S becomes the class with the most votes, the smallest such class on a
+ * tie, and stays as it is without any vote.  One round: small components do not vote.  Every other pixel keeps its value bit for bit.
+ * record (nullable): DEVICE int64 [N][num_classes][8], ADDED into (slot 2: raised to), the caller zeroes it; per image and class
+ *   [0] components  [1] pixels  [2] largest area  [3] small components  [4] their pixels  [5] small components that changed value
+ *   [6] pixels the class received from other classes  [7] small components without a vote (mode 1).
+ * cvk_cc_record_slots() = 8.  workspace: DEVICE, cvk_cc_workspace_bytes(N, H, W, num_classes) bytes (0: unsupported sizes), the same
+ * for both calls: parents int32 [M], code bytes [M], votes int32 [M][num_classes] indexed by a component's first pixel and touched
+ * only there.  It need not be initialised and carries nothing from one call to the next.  No allocation, no host sync. */
+int64_t cvk_cc_workspace_bytes(int N, int H, int W, int num_classes);
+int cvk_cc_record_slots(void);
+int cvk_cc_label(const int64_t* map, int32_t* labels, int32_t* area, int N, int H, int W, int num_classes, int ignore_index,
+                 int connectivity, void* workspace, void* stream);
+int cvk_cc_filter(const int64_t* map, const int32_t* labels, const int32_t* area, int64_t* out, int64_t* record, int N, int H, int W,
+                  int num_classes, int ignore_index, int connectivity, int min_area, int mode, int64_t fill_value, void* workspace,
+                  void* stream);
+
 /* ---- multi-scale / flip test-time augmentation: the merge of the views' logits (not in the reference) ------------------
  * Bilinear resampling here is torch's F.interpolate(mode="bilinear", align_corners=False) with the sample position taken from
  * integers: for destination index d of `out` samples over `in` source samples, num = max((2 d + 1) in - out, 0), lower source

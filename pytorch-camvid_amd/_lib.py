@@ -232,6 +232,10 @@ SIGNATURES = {
     "cvk_cheb_workspace_bytes": (ctypes.c_int64, [c_int, c_int, c_int]),
     "cvk_cheb_depth": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "cvk_boundary_iou_counts": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "cvk_cc_workspace_bytes": (ctypes.c_int64, [c_int, c_int, c_int, c_int]),
+    "cvk_cc_record_slots": (c_int, []),
+    "cvk_cc_label": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "cvk_cc_filter": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp]),
     "cvk_tta_accumulate": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_vp]),
     "cvk_tta_resize_input": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "cvk_window_merge": (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),

@@ -11,6 +11,7 @@
 //   optim_flat.h    AdamW, momentum SGD, the per-iteration log row
 //   grad_flat.h     global-norm clipping and gradient accumulation
 //   crop_aug.h      crop training: class-balanced window selection, resize + crop + pad + blur + LUT + flip
+//   components.h    connected components of a class map (union-find over tiles) and the removal of small regions
 // A new subject gets a header of that kind, not lines here.
 #include "cvk_common.h"
 #include "loss_rows.h"
@@ -22,6 +23,7 @@
 #include "optim_flat.h"
 #include "grad_flat.h"
 #include "crop_aug.h"
+#include "components.h"
 
 namespace {
 

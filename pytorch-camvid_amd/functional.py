@@ -13,6 +13,9 @@ in losses.py; their public names and constants are importable from here as befor
   BoundaryIoUMeter, chessboard_depth, boundary_dilation, boundary_iou_scores, trimap_scores
                     <- Boundary IoU (Cheng et al. CVPR 2021) and the trimap curve (not in the reference) on a device chessboard
                        depth map: integer counts per image and class, scores on the host
+  connected_components, remove_small_regions, RegionFilter, RegionMeter, region_scores
+                    <- connected components of a class map (canonical labels and areas from a union-find over tiles) and the
+                       removal of small regions (not in the reference); fragmentation and the mIoU after despeckling
 """
 import torch
 
@@ -602,6 +605,203 @@ class BoundaryIoUMeter:
         return out
 
 
+CC_RECORD_SLOTS = 8              # include/cvk.h: components, pixels, largest, small, small pixels, changed, received, isolated
+CC_MODES = ("fill", "neighbor")
+
+
+def _check_region_options(who, num_classes, connectivity, mode="neighbor", min_area=1):
+    _check_cheb_classes(who, num_classes)
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"{who}: connectivity must be 4 or 8. Got: {connectivity!r}")
+    if mode not in CC_MODES:
+        raise ValueError(f"{who}: mode must be one of {CC_MODES}. Got: {mode!r}")
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 1:
+        raise ValueError(f"{who}: min_area must be an integer of at least 1. Got: {min_area!r}")
+
+
+def _check_region_map(who, m):
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.int64 or m.dim() not in (2, 3) or m.numel() == 0:
+        raise ValueError(f"{who}: expected an int64 tensor [N, H, W] or [H, W]")
+    if m.numel() >= 2 ** 31:
+        raise ValueError(f"{who}: {m.numel()} pixels, the kernels serve fewer than 2^31")
+    if not m.is_cuda:
+        raise ValueError(f"{who}: expected a tensor on a GPU (no CPU fallback)")
+    return (m if m.dim() == 3 else m.unsqueeze(0)).contiguous()
+
+
+class _RegionBuffers:
+    """The device buffers of cvk_cc_label / cvk_cc_filter, kept per (N, H, W, classes, device): the workspace, and two pairs of
+    (labels, area) for the callers that keep the maps to themselves (the filter and the meter)."""
+
+    _buffers = {}
+
+    @staticmethod
+    def get(lib, N, H, W, C, device):
+        key = (N, H, W, C, str(device))
+        ent = _RegionBuffers._buffers.get(key)
+        if ent is None:
+            nbytes = lib.cvk_cc_workspace_bytes(N, H, W, C)
+            if nbytes <= 0:
+                raise ValueError(f"connected components serve 1 to 32 classes and fewer than 2^31 pixels, got N = {N}, H = {H}, W = {W}, "
+                                 f"{C} classes")
+            ent = _RegionBuffers._buffers[key] = {"ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
+                                                  "maps": torch.empty((2, 2, N, H, W), device=device, dtype=torch.int32)}
+        return ent
+
+
+def _cc_label(lib, m, labels, area, ws, num_classes, ignore_index, connectivity):
+    N, H, W = m.shape
+    check(lib.cvk_cc_label(m.data_ptr(), labels.data_ptr(), area.data_ptr(), N, H, W, num_classes, ignore_index, connectivity,
+                           ws.data_ptr(), _stream(m)), "cvk_cc_label")
+
+
+def _cc_filter(lib, m, labels, area, out, record, ws, num_classes, ignore_index, connectivity, min_area, mode, fill_value):
+    N, H, W = m.shape
+    check(lib.cvk_cc_filter(m.data_ptr(), labels.data_ptr(), area.data_ptr(), out.data_ptr(), None if record is None else record.data_ptr(),
+                            N, H, W, num_classes, ignore_index, connectivity, min(min_area, 2 ** 31 - 1), CC_MODES.index(mode),
+                            int(fill_value), ws.data_ptr(), _stream(m)), "cvk_cc_filter")
+
+
+def connected_components(labels, num_classes=12, ignore_index=11, connectivity=4):
+    """(labels, area), int32 [N,H,W] each ([H,W] for an [H,W] map), of the int64 class map `labels` on the GPU (include/cvk.h,
+    cvk_cc_label).  A pixel's code is its value when that is a class other than `ignore_index`, and void, one code, for anything else;
+    a component is a maximal set of equal codes of one image connected under `connectivity` (4 or 8), void components included.
+    `labels` of a pixel is y * W + x of the first pixel of its component in row-major order, `area` the component's size, at every
+    pixel.  Exact and canonical: nothing depends on the order in which the device works.  The two maps are buffers kept per shape and
+    device and are overwritten by the next call of the same shape.  No host sync."""
+    _check_region_options("connected_components", num_classes, connectivity)
+    m = _check_region_map("connected_components", labels)
+    lib = _lib.load()
+    N, H, W = m.shape
+    ent = _RegionBuffers.get(lib, N, H, W, num_classes, m.device)
+    if "public" not in ent:
+        ent["public"] = torch.empty((2, N, H, W), device=m.device, dtype=torch.int32)
+    lab, area = ent["public"][0], ent["public"][1]
+    _cc_label(lib, m, lab, area, ent["ws"], num_classes, int(ignore_index), connectivity)
+    return (lab, area) if labels.dim() == 3 else (lab[0], area[0])
+
+
+class RegionFilter:
+    """Removes the regions of a class map that are smaller than `min_area` pixels: `rf(pred)` returns a new int64 map of the shape of
+    `pred` ([N,H,W] or [H,W]), e.g. `cls = rf(cvk.predict(net, img, window=sw))`.  A region is a component of `connected_components`
+    whose code is a class; void is never removed.  mode "fill": its pixels become `fill_value` (default: `ignore_index`).  mode
+    "neighbor": it becomes the class most of its neighbouring pixels have, counting pairs (pixel of the region, neighbour under the same
+    connectivity) whose neighbour is a class pixel of a region that is not small itself; ties go to the smallest class, a region
+    without any such neighbour stays as it is.  One round, so the result does not depend on any order; `min_area=1` returns the input's
+    values.  `last_record` is a view of the device record int64 [N, num_classes, 8] of the last call: components, pixels, largest area,
+    small components, their pixels, small components changed, pixels received from other classes, small components without a vote.
+    Five to seven launches, no host sync."""
+
+    def __init__(self, min_area, num_classes=12, ignore_index=11, connectivity=4, mode="neighbor", fill_value=None):
+        _check_region_options("RegionFilter", num_classes, connectivity, mode, min_area)
+        self.min_area, self.num_classes, self.ignore_index = min_area, num_classes, int(ignore_index)
+        self.connectivity, self.mode = connectivity, mode
+        if fill_value is not None and mode != "fill":
+            raise ValueError('RegionFilter: fill_value belongs to mode="fill"')
+        if fill_value is not None and (isinstance(fill_value, bool) or not isinstance(fill_value, int) or not -2 ** 63 <= fill_value < 2 ** 63):
+            raise ValueError(f"RegionFilter: fill_value must be an int64 value. Got: {fill_value!r}")
+        self.fill_value = self.ignore_index if fill_value is None else fill_value
+        self._record = None
+
+    @property
+    def last_record(self):
+        if self._record is None:
+            raise RuntimeError("RegionFilter.last_record: the filter has not been called yet")
+        return self._record
+
+    def _run(self, m, pair):
+        """the filtered map and the record of the contiguous [N,H,W] map `m`; `pair` chooses the (labels, area) buffers"""
+        lib = _lib.load()
+        N, H, W = m.shape
+        ent = _RegionBuffers.get(lib, N, H, W, self.num_classes, m.device)
+        lab, area = ent["maps"][pair][0], ent["maps"][pair][1]
+        _cc_label(lib, m, lab, area, ent["ws"], self.num_classes, self.ignore_index, self.connectivity)
+        out = torch.empty_like(m)
+        record = torch.zeros((N, self.num_classes, CC_RECORD_SLOTS), device=m.device, dtype=torch.int64)
+        _cc_filter(lib, m, lab, area, out, record, ent["ws"], self.num_classes, self.ignore_index, self.connectivity, self.min_area,
+                   self.mode, self.fill_value)
+        return out, record
+
+    def __call__(self, pred):
+        m = _check_region_map("RegionFilter", pred)
+        out, self._record = self._run(m, 0)
+        return out if pred.dim() == 3 else out[0]
+
+
+def remove_small_regions(pred, min_area, num_classes=12, ignore_index=11, connectivity=4, mode="neighbor", fill_value=None):
+    """`RegionFilter(min_area, ...)(pred)`: the int64 map `pred` without its class regions of fewer than `min_area` pixels."""
+    return RegionFilter(min_area, num_classes, ignore_index, connectivity, mode, fill_value)(pred)
+
+
+def region_scores(records_pred, records_label, hist, ignore_index=None):
+    """The scores of `RegionMeter` from its sums, in float64 on the host: `records_pred` / `records_label` int64 [K, 8] pooled over the
+    images, `hist` int64 [3, K] the confusion counts of the filtered prediction (intersection, prediction, label)."""
+    import numpy as np
+    rp, rl, h = (np.asarray(a, dtype=np.int64) for a in (records_pred, records_label, hist))
+    K = rp.shape[0]
+    frag = np.divide(rp[:, 0].astype(np.float64), rl[:, 0], out=np.full(K, np.nan), where=rl[:, 0] > 0)
+    union = (h[1] + h[2] - h[0]).astype(np.float64)
+    iou = np.divide(h[0].astype(np.float64), union, out=np.full(K, np.nan), where=union > 0)
+    if ignore_index is not None and 0 <= ignore_index < K:
+        frag[ignore_index] = iou[ignore_index] = np.nan
+    ev, evi = ~np.isnan(frag), ~np.isnan(iou)
+    return {"regions_pred": rp[:, 0].copy(), "regions_label": rl[:, 0].copy(), "small_regions_pred": rp[:, 3].copy(),
+            "fragmentation_per_class": frag, "fragmentation": float(frag[ev].mean()) if ev.any() else float("nan"),
+            "iou_filtered": iou, "miou_filtered": float(iou[evi].mean()) if evi.any() else float("nan")}
+
+
+class RegionMeter:
+    """Fragmentation of predictions against labels, and the mIoU after despeckling.  `update(pred, label)` labels the components of
+    both maps, filters the prediction as `RegionFilter(min_area, ..., mode)` does (the labels take no part in that, as at deployment;
+    void is the prediction's own `ignore_index` pixels) and adds the filtered prediction's confusion counts against the label and both
+    maps' records, all on the device.  `compute()` (one device->host copy) returns "regions_pred", "regions_label",
+    "small_regions_pred" (int64 per class, pooled over the images; the prediction's are those before the filter),
+    "fragmentation_per_class" (predicted regions over label regions; NaN for a class without a label region and at `ignore_index`),
+    "fragmentation" (its mean over the classes that occur), "iou_filtered", "miou_filtered" and "images"."""
+
+    def __init__(self, num_classes=12, ignore_index=11, min_area=64, connectivity=4, mode="neighbor"):
+        self._filter = RegionFilter(min_area, num_classes, ignore_index, connectivity, mode)
+        self._count = RegionFilter(1, num_classes, ignore_index, connectivity, "fill")       # removes nothing: the label's record
+        self.num_classes, self.ignore_index, self.min_area = num_classes, int(ignore_index), min_area
+        self.connectivity, self.mode = connectivity, mode
+        self.reset()
+
+    def reset(self):
+        self._sums, self.images = None, 0
+
+    def update(self, pred, label):
+        _check_boundary_maps("RegionMeter.update", pred, label)
+        if pred.numel() >= 2 ** 31:
+            raise ValueError(f"RegionMeter.update: {pred.numel()} pixels, the kernels serve fewer than 2^31")
+        lib = _lib.load()
+        p, l = pred.contiguous(), label.contiguous()
+        K = self.num_classes
+        if self._sums is None:
+            self._sums = torch.zeros(2 * K * CC_RECORD_SLOTS + 3 * K, device=p.device, dtype=torch.int64)
+        elif self._sums.device != p.device:
+            raise ValueError("RegionMeter.update: the batches of one meter must be on one device")
+        filtered, rec_p = self._filter._run(p, 0)
+        _, rec_l = self._count._run(l, 1)
+        rec = self._sums[:2 * K * CC_RECORD_SLOTS].view(2, K, CC_RECORD_SLOTS)
+        rec[0] += rec_p.sum(0)
+        rec[1] += rec_l.sum(0)
+        hist = self._sums[2 * K * CC_RECORD_SLOTS:]
+        check(lib.cvk_confusion_accumulate(filtered.data_ptr(), l.data_ptr(), hist.data_ptr(), filtered.numel(), K, self.ignore_index,
+                                           _stream(p)), "cvk_confusion_accumulate")
+        self.images += p.shape[0]
+
+    def compute(self):
+        K = self.num_classes
+        if self._sums is None:
+            s = torch.zeros(2 * K * CC_RECORD_SLOTS + 3 * K, dtype=torch.int64).numpy()
+        else:
+            s = self._sums.cpu().numpy()
+        rec = s[:2 * K * CC_RECORD_SLOTS].reshape(2, K, CC_RECORD_SLOTS)
+        out = region_scores(rec[0], rec[1], s[2 * K * CC_RECORD_SLOTS:].reshape(3, K), self.ignore_index)
+        out["images"] = self.images
+        return out
+
+
 WEIGHT_METHODS = ("median_frequency", "enet")
 
 
@@ -965,7 +1165,7 @@ class TestTimeAugmentation:
 
 def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None, contour_meters=()):
     """evaluate / evaluate_report with test-time augmentation: (meter, the per-batch losses of the loss view: empty without one).
-    `contour_meters` (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter) see the predictions the ConfusionMeter sees."""
+    `contour_meters` (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter, RegionMeter) see the predictions the ConfusionMeter sees."""
     meter, losses = None, []
 
     def keep_loss(masks, want):
@@ -1030,9 +1230,9 @@ def _contour_meters(boundary):
     """The meters behind evaluate_report's `boundary`: None, one meter, or a tuple / list with at most one meter of each kind."""
     meters = list(boundary) if isinstance(boundary, (tuple, list)) else [] if boundary is None else [boundary]
     for m in meters:
-        if not isinstance(m, (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter)):
+        if not isinstance(m, (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter, RegionMeter)):
             raise ValueError("boundary must be a BoundaryMeter or None, or a SurfaceDistanceMeter, or a tuple or list of one of each. "
-                             f"A BoundaryIoUMeter is taken the same way. Got: {type(m).__name__}")
+                             f"A BoundaryIoUMeter and a RegionMeter are taken the same way. Got: {type(m).__name__}")
     if len({type(m) for m in meters}) != len(meters):
         raise ValueError("boundary holds two meters of one kind: their scores would share the report's keys")
     return meters
@@ -1041,7 +1241,9 @@ def _contour_meters(boundary):
 def _with_boundary(report, contour_meters):
     for m in contour_meters:
         scores = m.compute()
-        if isinstance(m, BoundaryIoUMeter):
+        if isinstance(m, RegionMeter):
+            keys = ("fragmentation", "miou_filtered", "regions_pred")
+        elif isinstance(m, BoundaryIoUMeter):
             keys = ("biou", "biou_per_class") + (("trimap_miou",) if m.trimap_widths else ())
         else:
             keys = SURFACE_REPORT_KEYS if isinstance(m, SurfaceDistanceMeter) else ("bf", "bf_per_class")
@@ -1062,7 +1264,8 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
     SurfaceDistanceMeter, or a tuple or list with one meter of either kind: a SurfaceDistanceMeter is reset and fed the same way, and
     the report gains "hd95", "hd", "assd" and their "_per_class" arrays; the meter's `compute()` has the rest (unmatched classes,
     images).  A BoundaryIoUMeter is a third kind, alone or beside one of each of the others: the report gains "biou" and
-    "biou_per_class", and "trimap_miou" when the meter has trimap widths."""
+    "biou_per_class", and "trimap_miou" when the meter has trimap widths.  A RegionMeter is a fourth kind: the report gains
+    "fragmentation", "miou_filtered" and "regions_pred"."""
     _check_tta_window("evaluate_report", tta, window)
     contour_meters = _contour_meters(boundary)
     loss_fn = loss_fn or CrossEntropyLoss()
