@@ -133,6 +133,12 @@ def main():
                     help="also report the mIoU after regions of fewer than A pixels went to their neighbours' class, and the fragmentation "
                     "(predicted regions over label regions; cvk.RegionMeter)")
     ap.add_argument("--region-connectivity", type=int, default=4, choices=(4, 8), help="with --min-region: 4- or 8-connected regions")
+    ap.add_argument("--crf", action="store_true",
+                    help="also validate with a local-window mean-field CRF on top of the predictions (cvk.LocalCRF; the guide image is the "
+                    "network's own input) and print the mIoU with and without it; with --tta-* / --window-crop it refines their result")
+    ap.add_argument("--crf-iterations", type=int, default=5, help="with --crf: mean-field iterations")
+    ap.add_argument("--crf-radius", type=int, default=3, help="with --crf: the window is (2 radius + 1)^2 pixels, radius in 1..5")
+    ap.add_argument("--crf-dilation", type=int, default=1, help="with --crf: the step between the window's pixels, 1..4")
     a = ap.parse_args()
     tta = window = boundary = surface = biou = region = None
     if a.min_region is not None:
@@ -171,6 +177,13 @@ def main():
         except ValueError as e:
             ap.error(f"--tta-scales: {e}")
         window = None                   # the views are evaluated in windows: evaluate() takes tta= or window=, not both
+    crf = None
+    if a.crf:
+        try:
+            crf = cvk.LocalCRF(iterations=a.crf_iterations, radius=a.crf_radius, dilation=a.crf_dilation,
+                               inner=tta if tta is not None else window)
+        except ValueError as e:
+            ap.error(f"--crf-iterations / --crf-radius / --crf-dilation: {e}")
     a.flat_adamw = a.flat_adamw or a.graphed
     if (a.ema_decay is not None or a.ema_warmup) and not a.flat_adamw:
         ap.error("--ema-decay / --ema-warmup need --flat-adamw or --graphed (the average lives in FlatAdamW's flat buffers)")
@@ -328,13 +341,20 @@ def main():
             frames = ((m.unsqueeze(-1) * torch.tensor([20, 15, 10], device=dev)) % 256).clamp(0, 255).to(torch.uint8)
             batches.append((cvk.preprocess_uint8(frames), m))
         acc, miou, bf = validate(net, batches, tta, window, boundary, surface, biou, region)
+        miou_crf = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=crf)[2] if crf is not None else None
         if rank == 0:
             print(f"          val acc {acc:.4f}  mIoU(11 classes) {miou:.4f}{bf_text(bf, a.hd_percentile)}")
+            if crf is not None:
+                print(f"          with the CRF refinement mIoU {miou_crf:.4f}, without {miou:.4f}  ({crf.iterations} iterations, radius "
+                      f"{crf.radius}, dilation {crf.dilation})")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
                 acc_e, miou_e, bf_e = validate(net, batches, tta, window, boundary, surface, biou, region)
+                miou_crf_e = cvk.evaluate(net, batches, num_classes=12, ignore_index=11, tta=crf)[2] if crf is not None else None
             if rank == 0:
                 print(f"          EMA acc {acc_e:.4f}  mIoU(11 classes) {miou_e:.4f}{bf_text(bf_e, a.hd_percentile)}  ({opt.ema_updates} updates, decay {a.ema_decay:g})")
+                if crf is not None:
+                    print(f"          EMA with the CRF refinement mIoU {miou_crf_e:.4f}, without {miou_e:.4f}")
     if rank == 0:
         torch.save(net.state_dict(), "/tmp/cvk_synthetic.pth")             # train.py:232-240; loads into the reference too
         if a.ema_decay is not None:

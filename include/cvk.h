@@ -837,6 +837,48 @@ int cvk_tta_resize_input(const float* src, int64_t sN, int64_t sC, int64_t sH, i
 int cvk_window_merge(const float* logits, int ld, float* out, int64_t* pred, int N, int H, int W, int C, int hc, int wc, int sy, int sx,
                      int iy, int ix, void* stream);
 
+/* ---- local-window mean-field CRF refinement of a prediction (Teichmann & Cipolla's ConvCRF form with a dilation; not in the
+ * reference; the fully connected permutohedral CRF is NOT provided) -------------------------------------------------------------
+ * Inputs.  U [N][H][W][C], the unary: logits, or probabilities (unary_is_prob != 0), which enter as U_c := log(max(U_c, FLT_MIN)).
+ * A guide image I [N][3][H][W], I_k(p) = fma(a_k, x_k(p), b_k) in fp32, where x is the network's float input of any strides (in
+ * elements, as cvk_import_nchw) and a_k = 255 std_k, b_k = 255 mean_k undo the normalisation on load (grey levels of 0..255); or,
+ * with guide_u8 != 0, dense uint8 frames [N][H][W][3] taken as they are (the strides and a, b are ignored).  guide_a, guide_b: HOST
+ * float [3] each (may be NULL with guide_u8), copied into the launch arguments.  Integers radius r in
+ * 1..5, dilation d in 1..4, and T >= 1 iterations, one call each.
+ * Offsets.  O = {(d i, d j) : -r <= i, j <= r} \ {(0, 0)}, walked in row-major order of (i, j); a neighbour p + o outside the image
+ * contributes nothing, to no sum.
+ * Kernels.  Appearance ka(p, o) = ga[o] * exp(cb * |I(p) - I(p + o)|^2), smoothness ks(p, o) = gs[o], with the tables
+ * ga[o] = float32(exp(-|o|^2 / (2 theta_alpha^2))), gs[o] = float32(exp(-|o|^2 / (2 theta_gamma^2))) (|o|^2 = d^2 (i^2 + j^2), in
+ * pixels) and cb = float32(-1 / (2 theta_beta^2)) made by the HOST in double precision and rounded once (cvk.crf_coefficients returns
+ * exactly these); the tables are HOST float [(2r+1)^2] in row-major (i, j), the centre entry is never read, and they are copied into
+ * the launch arguments.  The kernel's only exponentials are the colour term and the softmax.
+ * Normalisation.  Each kernel by its own sum over the neighbours inside the image: na(p) = sum_o ka(p, o), ns(p) = sum_o ks(p, o);
+ * a zero sum gives a zero message (a 1 x 1 image has no neighbour and returns softmax(U)).
+ * Iteration.  Q_0 = softmax(U) (max-subtracted).  With Sa_c = sum_o ka(p, o) Q_t,c(p + o), Ss_c likewise,
+ *   m_c(p) = (wa / na(p)) Sa_c + (ws / ns(p)) Ss_c      (each quotient evaluated once per pixel, 0 where the sum is 0)
+ *   Q_{t+1}(p) = softmax_c(U_c(p) - sum_c' mu[c][c'] m_c'(p)),   mu = compat (DEVICE float [C][C]) or, when compat is NULL, -I
+ *   (Potts): then Q_{t+1} = softmax(U + m) and no C^2 product is evaluated.
+ * Every sum over o runs in the row-major order above in fp32, no atomics: two runs agree bit for bit, and a pixel's result does not
+ * depend on where it lies in the launch grid or on the other images of the batch.
+ * cvk_crf_step is ONE iteration, called T times on one stream: q_in and q_out are dense float [N][H][W][C], different buffers that
+ * swap roles from call to call.
+ *   first != 0: the call reads U in place of Q_t and takes the neighbours' softmax as it stages them (no Q_0 pass, no memset); q_in
+ *               is scratch then (required all the same: the path that does not stage writes Q_0 there), else q_in = Q_t.
+ *   last  != 0: q_out = probs = Q_T and pred (int64 [N][H][W], required then) = the first-maximum channel of exactly the values
+ *               stored (a NaN wins, as in cvk_argmax_channels).  first and last together: T = 1.
+ * Where the tile of Q and I with its halo r d fits the LDS it is staged there, each thread producing several pixels d apart so that
+ * one read of a neighbour's C values feeds several outputs; where it does not, neighbours are read from global memory.  The two
+ * paths evaluate the same expressions in the same order.  cvk_crf_tile reports the tile (th x tw pixels per work-group) and which
+ * path (staged = 1 / 0) a (C, radius, dilation) takes; CVK_EINVAL outside the limits.
+ * Limits: 1 <= C <= 32, ld_u >= C, sizes up to 16384 per side, N * H * W * C < 2^31, wa, ws >= 0 and cb <= 0 finite.  Weights are
+ * recomputed from the staged image every iteration: nothing per (pixel, offset) is stored.  At most two launches (one on the staged
+ * path), no allocation, no host sync; the calls can be captured. */
+int cvk_crf_tile(int C, int radius, int dilation, int* th, int* tw, int* staged);
+int cvk_crf_step(const float* unary, int ld_u, int unary_is_prob, const float* q_in, float* q_out, int64_t* pred, const void* guide,
+                 int guide_u8, int64_t gN, int64_t gC, int64_t gH, int64_t gW, const float* guide_a, const float* guide_b,
+                 const float* ga, const float* gs, float cb, float wa, float ws, const float* compat, int N, int H, int W, int C,
+                 int radius, int dilation, int first, int last, void* stream);
+
 /* ---- input pipeline on device (transforms.ToTensor + Normalize: transforms.py:485-538, MEAN/STD conf/settings.py:8-9) ----
  * src uint8 [N,H,W,3] (channel order as decoded, i.e. cv2 BGR) -> dst float32 NHWC with ld = 4 (pad channel 0):
  * dst[c] = (src[c]/255 - mean3[c]) / std3[c].  mean3 / std3 are HOST pointers to 3 floats. */

@@ -12,6 +12,7 @@
 //   grad_flat.h     global-norm clipping and gradient accumulation
 //   crop_aug.h      crop training: class-balanced window selection, resize + crop + pad + blur + LUT + flip
 //   components.h    connected components of a class map (union-find over tiles) and the removal of small regions
+//   crf.h           local-window mean-field CRF refinement of a prediction (a register-blocked stencil over an LDS tile)
 // A new subject gets a header of that kind, not lines here.
 #include "cvk_common.h"
 #include "loss_rows.h"
@@ -24,6 +25,7 @@
 #include "grad_flat.h"
 #include "crop_aug.h"
 #include "components.h"
+#include "crf.h"
 
 namespace {
 

@@ -16,6 +16,9 @@ in losses.py; their public names and constants are importable from here as befor
   connected_components, remove_small_regions, RegionFilter, RegionMeter, region_scores
                     <- connected components of a class map (canonical labels and areas from a union-find over tiles) and the
                        removal of small regions (not in the reference); fragmentation and the mIoU after despeckling
+  LocalCRF, crf_refine, crf_coefficients, crf_tile
+                    <- local-window mean-field CRF refinement of a prediction under the network's own input as the guide image
+                       (ConvCRF's form with a dilation; not in the reference): one stencil launch per iteration
 """
 import torch
 
@@ -1161,6 +1164,202 @@ class TestTimeAugmentation:
     def __call__(self, net, images):
         """(probs float32 [N,C,H,W], pred int64 [N,H,W]) of one batch; see the class."""
         return self._merge(net, images)
+
+
+CRF_MAX_RADIUS, CRF_MAX_DILATION = 5, 4          # include/cvk.h: the window of cvk_crf_step
+
+
+def _crf_numbers(name, v, n, positive_from):
+    import math
+    try:
+        out = tuple(float(e) for e in v)
+    except (TypeError, ValueError):
+        out = ()
+    ok = len(out) == n and all(math.isfinite(e) for e in out) and out[0] >= 0.0 and all(e > 0.0 for e in out[positive_from:])
+    if not ok:
+        raise ValueError(f"{name} must be {n} finite numbers, a weight >= 0 followed by widths > 0. Got: {v!r}")
+    return out
+
+
+def _crf_window(radius, dilation):
+    for name, v, hi in (("radius", radius, CRF_MAX_RADIUS), ("dilation", dilation, CRF_MAX_DILATION)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise ValueError(f"{name} must be an integer in 1..{hi}. Got: {v!r}")
+    return radius, dilation
+
+
+def crf_coefficients(radius=3, dilation=1, appearance=(4.0, 8.0, 13.0), smoothness=(3.0, 3.0)):
+    """(ga, gs, cb, wa, ws): exactly the numbers cvk_crf_step gets.  ga, gs are float32 numpy arrays [2r+1, 2r+1] over the offsets
+    (d i, d j) in row-major (i, j): ga = float32(exp(-|o|^2 / (2 theta_alpha^2))), gs the same with theta_gamma; cb =
+    float32(-1 / (2 theta_beta^2)); wa, ws the two weights as float32.  Each is evaluated in double and rounded once.  The centre
+    entry of a table (offset (0, 0)) is never read."""
+    import numpy as np
+    r, d = _crf_window(radius, dilation)
+    wa, theta_alpha, theta_beta = _crf_numbers("appearance", appearance, 3, 1)
+    ws, theta_gamma = _crf_numbers("smoothness", smoothness, 2, 1)
+    i = np.arange(-r, r + 1, dtype=np.float64) * d
+    o2 = i[:, None] ** 2 + i[None, :] ** 2
+    ga = np.exp(-o2 / (2.0 * theta_alpha * theta_alpha)).astype(np.float32)
+    gs = np.exp(-o2 / (2.0 * theta_gamma * theta_gamma)).astype(np.float32)
+    cb = float(np.float32(-1.0 / (2.0 * theta_beta * theta_beta)))
+    if not (np.isfinite(np.float32(wa)) and np.isfinite(np.float32(ws)) and np.isfinite(cb)):
+        raise ValueError("appearance / smoothness leave float32's range")
+    return ga, gs, cb, float(np.float32(wa)), float(np.float32(ws))
+
+
+def crf_tile(num_classes, radius=3, dilation=1):
+    """(tile height, tile width, staged) of cvk_crf_step for a class count and a window: the pixels one work-group produces and
+    whether their neighbourhood is staged in LDS (True) or read from global memory (False).  No GPU needed."""
+    import ctypes
+    lib = _lib.load()
+    th, tw, st = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib.cvk_crf_tile(int(num_classes), int(radius), int(dilation), ctypes.byref(th), ctypes.byref(tw), ctypes.byref(st))
+    if rc != 0:
+        raise ValueError(lib.cvk_last_error_string().decode())
+    return th.value, tw.value, bool(st.value)
+
+
+class LocalCRF:
+    """Local-window mean-field CRF refinement of a prediction, on the device (cvk_crf_step; the definition is in include/cvk.h).
+
+      crf = LocalCRF(iterations=5, radius=3, dilation=1, appearance=(4.0, 8.0, 13.0), smoothness=(3.0, 3.0))
+      probs, pred = crf.refine(logits, images)     # logits [N,C,H,W], images the network's float input [N,3,H,W]
+      probs, pred = crf(net, images)               # eval-mode forward under no_grad, then the refinement
+
+    This is the ConvCRF form (Teichmann & Cipolla) with a dilation for reach: every pixel hears the (2 radius + 1)^2 - 1 pixels at
+    offsets (dilation i, dilation j) around it, not the whole image; the fully connected permutohedral CRF is not provided.
+    `appearance = (wa, theta_alpha in pixels, theta_beta in grey levels of 0..255)`, `smoothness = (ws, theta_gamma)`; the defaults
+    are DeepLab's dense-CRF values with theta_alpha scaled to a 7 x 7 window.  `compat` is None (Potts, mu = -I) or a float32 [C,C]
+    device tensor mu.  `mean` / `std` are the normalisation of the network's input, undone on load (I = 255 (std x + mean)), so the
+    guide is the network input itself, of any strides: no second image tensor exists.  uint8 frames [N,H,W,3] are taken as they are.
+
+    `inner` decides what `crf(net, images)` refines: None, the network's logits; a SlidingWindow, `inner.logits(net, images)`; a
+    TestTimeAugmentation, its mean probabilities (a probability unary enters as log(max(p, FLT_MIN))).
+
+    One launch per iteration, no atomics: two runs agree bitwise.  `probs` is float32 [N,C,H,W], a channels_last view of one of the
+    two buffers this object keeps per (N, C, H, W, device): the next call with that shape overwrites it (clone it to keep it).
+    `pred` is a fresh int64 [N,H,W], the first-maximum arg-max of `probs` (`torch.equal(pred, argmax_channels(probs))`).  Channels_last
+    logits are read in place, other layouts copied once.  At most 32 classes.  A LocalCRF has TestTimeAugmentation's return
+    contract: `evaluate`, `evaluate_report` and `predict` take it as `tta=`; "loss" is then `loss_fn` of the unrefined logits (with a
+    TestTimeAugmentation inside, of its loss view)."""
+
+    def __init__(self, iterations=5, radius=3, dilation=1, appearance=(4.0, 8.0, 13.0), smoothness=(3.0, 3.0), compat=None,
+                 mean=CAMVID_MEAN, std=CAMVID_STD, inner=None):
+        import ctypes
+        import math
+        import numpy as np
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+            raise ValueError(f"iterations must be an integer >= 1. Got: {iterations!r}")
+        self.iterations = iterations
+        self.radius, self.dilation = _crf_window(radius, dilation)
+        self.ga, self.gs, self.cb, self.wa, self.ws = crf_coefficients(radius, dilation, appearance, smoothness)
+        if compat is not None and (not isinstance(compat, torch.Tensor) or compat.dim() != 2 or compat.shape[0] != compat.shape[1]
+                                   or compat.dtype != torch.float32):
+            raise ValueError("compat must be None or a float32 tensor of shape [C, C]")
+        self.compat = None if compat is None else compat.detach().contiguous()
+        try:
+            mean, std = tuple(float(e) for e in mean), tuple(float(e) for e in std)
+        except (TypeError, ValueError):
+            mean = std = ()
+        if len(mean) != 3 or len(std) != 3 or not all(math.isfinite(e) for e in mean + std) or not all(e > 0.0 for e in std):
+            raise ValueError("mean and std must be three finite numbers each, std > 0")
+        if inner is not None and not isinstance(inner, (SlidingWindow, TestTimeAugmentation)):
+            raise ValueError(f"inner must be None, a SlidingWindow or a TestTimeAugmentation. Got: {inner!r}")
+        self.inner = inner
+        self.guide_scale = np.array([255.0 * s for s in std], dtype=np.float32)       # a_k, b_k of include/cvk.h, rounded once
+        self.guide_offset = np.array([255.0 * m for m in mean], dtype=np.float32)
+        taps = (2 * self.radius + 1) ** 2
+        self._ga = (ctypes.c_float * taps)(*self.ga.ravel().tolist())
+        self._gs = (ctypes.c_float * taps)(*self.gs.ravel().tolist())
+        self._a = (ctypes.c_float * 3)(*self.guide_scale.tolist())
+        self._b = (ctypes.c_float * 3)(*self.guide_offset.tolist())
+        self._buf = {}
+
+    def refine(self, unary, images, unary_is_prob=False):
+        """(probs float32 [N,C,H,W], pred int64 [N,H,W]) of a unary [N,C,H,W] (logits, or probabilities with `unary_is_prob`) under
+        the guide `images` (float32 [N,3,H,W] of any strides, or uint8 [N,H,W,3]); see the class."""
+        lib = _lib.load()
+        if not isinstance(unary, torch.Tensor) or unary.dim() != 4 or unary.dtype != torch.float32:
+            raise ValueError("expected a float32 unary of shape [N, C, H, W]")
+        if not unary.is_cuda:
+            raise RuntimeError("pytorch_camvid_amd.LocalCRF needs HIP tensors (no CPU fallback)")
+        N, C, H, W = unary.shape
+        if not 1 <= C <= 32:
+            raise ValueError(f"pytorch_camvid_amd.LocalCRF serves 1 to 32 classes, got C = {C}")
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.device != unary.device:
+            raise ValueError("expected the guide images as a 4-D tensor on the unary's device")
+        if images.dtype == torch.uint8:
+            if tuple(images.shape) != (N, H, W, 3):
+                raise ValueError(f"uint8 guide frames must be {[N, H, W, 3]}, got {list(images.shape)}")
+            guide, u8, strides = images.contiguous(), 1, (0, 0, 0, 0)
+        elif images.dtype == torch.float32:
+            if tuple(images.shape) != (N, 3, H, W):
+                raise ValueError(f"the float guide must be {[N, 3, H, W]}, got {list(images.shape)}")
+            guide, u8, strides = images.detach(), 0, tuple(images.stride())
+        else:
+            raise ValueError(f"the guide must be float32 [N,3,H,W] or uint8 [N,H,W,3], got {images.dtype}")
+        compat = self.compat
+        if compat is not None:
+            if tuple(compat.shape) != (C, C):
+                raise ValueError(f"compat is {list(compat.shape)}, the unary has {C} classes")
+            if compat.device != unary.device:
+                raise ValueError(f"compat is on {compat.device}, the unary on {unary.device}")
+        key = (N, C, H, W, unary.device)
+        bufs = self._buf.get(key)
+        if bufs is None:
+            bufs = self._buf[key] = (torch.empty((N, H, W, C), device=unary.device, dtype=torch.float32),
+                                     torch.empty((N, H, W, C), device=unary.device, dtype=torch.float32))
+        lg, ld = _as_nhwc(unary.detach())
+        if lg.data_ptr() in (bufs[0].data_ptr(), bufs[1].data_ptr()):
+            lg, ld = lg.clone(), C                            # an earlier result of this object as the unary: it would be overwritten
+        pred = torch.empty((N, H, W), device=unary.device, dtype=torch.int64)
+        T, s = self.iterations, _stream(unary)
+        for t in range(T):
+            q_out, q_in = bufs[t & 1], bufs[(t + 1) & 1]
+            check(lib.cvk_crf_step(lg.data_ptr(), ld, int(bool(unary_is_prob)), q_in.data_ptr(), q_out.data_ptr(),
+                                   pred.data_ptr() if t == T - 1 else None, guide.data_ptr(), u8, *strides, self._a, self._b, self._ga,
+                                   self._gs, self.cb, self.wa, self.ws, None if compat is None else compat.data_ptr(), N, H, W, C,
+                                   self.radius, self.dilation, int(t == 0), int(t == T - 1), s), "cvk_crf_step")
+        return bufs[(T - 1) & 1].permute(0, 3, 1, 2), pred
+
+    def loss_view(self, H, W):
+        """Index of the logits evaluate_report takes its loss from: the inner TestTimeAugmentation's own rule, else 0 (the unrefined
+        logits)."""
+        return self.inner.loss_view(H, W) if isinstance(self.inner, TestTimeAugmentation) else 0
+
+    def _merge(self, net, images, on_logits=None):
+        _check_images("LocalCRF", images)
+        if isinstance(self.inner, TestTimeAugmentation):
+            probs, _ = self.inner._merge(net, images, on_logits)
+            return self.refine(probs, images, unary_is_prob=True)
+        if isinstance(self.inner, SlidingWindow):
+            logits = self.inner.logits(net, images)
+        else:
+            was_training = net.training
+            net.eval()
+            try:
+                with torch.no_grad():
+                    logits = net(images)
+            finally:
+                net.train(was_training)
+            if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
+                raise ValueError("the network must return logits of shape [N, C, h, w]")
+            if logits.dtype != torch.float32 or not logits.is_cuda:
+                raise RuntimeError(f"expected float32 logits on a HIP device, got {logits.dtype} on {logits.device}")
+        if on_logits is not None:
+            on_logits(0, logits)
+        with torch.no_grad():
+            return self.refine(logits.detach(), images)
+
+    def __call__(self, net, images):
+        """(probs float32 [N,C,H,W], pred int64 [N,H,W]) of one batch; see the class."""
+        return self._merge(net, images)
+
+
+def crf_refine(logits, images, iterations=5, radius=3, dilation=1, appearance=(4.0, 8.0, 13.0), smoothness=(3.0, 3.0), compat=None,
+               mean=CAMVID_MEAN, std=CAMVID_STD, unary_is_prob=False):
+    """`LocalCRF(...).refine(logits, images, unary_is_prob)` in one call: (probs, pred), fresh buffers."""
+    return LocalCRF(iterations, radius, dilation, appearance, smoothness, compat, mean, std).refine(logits, images, unary_is_prob)
 
 
 def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None, contour_meters=()):
