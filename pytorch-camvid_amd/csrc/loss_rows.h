@@ -3,7 +3,8 @@
 // contiguous logits (a wave covers 64 * ld contiguous floats: fully used cache lines).  Here: the workgroup geometry (CE_*), the
 // 256-thread sum, the global <-> LDS movement of a chunk of pixel rows, and the weighted, label-smoothed pixel terms of
 // k_ce_fwd_ex / k_ce_bwd_ex that OHEM, Lovász, the boundary, focal + Dice and distillation losses reuse; the inference merges
-// borrow CE_CHUNK.  One kernel, k_lv_clear, because two subjects launch it (Lovász and the distance transform, edt.h).  No entry point.
+// borrow CE_CHUNK.  One kernel, k_lv_clear, because two subjects launch it (Lovász and the distance transform, edt.h).  One entry
+// point, cvk_ce_blocks: the number of workgroups of that geometry, which the launches of every loss take as their grid.
 #include "cvk_common.h"
 
 namespace {
@@ -103,3 +104,5 @@ __global__ __launch_bounds__(256) void k_lv_clear(unsigned* __restrict__ ctr, in
 }
 
 }  // namespace
+
+extern "C" int cvk_ce_blocks(int M) { return M > 0 ? cvk_cdiv(M, CE_ROWS_PER_BLOCK) : 0; }

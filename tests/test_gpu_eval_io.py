@@ -1,6 +1,6 @@
 """The kernels that bring an image in and turn logits into mIoU, called through the C ABI and compared with the numpy restatements
 of tests/eval_io_ref.py (which tests/test_eval_io_ref_cpu.py checks without a GPU): cvk_import_nchw, cvk_export_nchw, cvk_zero_frame
-(csrc/pointwise.hip), cvk_preprocess_u8 (csrc/loss_eval_optim.hip), cvk_argmax_channels, cvk_confusion_accumulate (csrc/eval_meters.h,
+(csrc/pointwise.hip), cvk_preprocess_u8 (csrc/ingest.h), cvk_argmax_channels, cvk_confusion_accumulate (csrc/eval_meters.h; both headers are
 compiled as part of loss_eval_optim.hip) and their Python wrappers preprocess_uint8, argmax_channels and ConfusionMeter.
 
 These operations move data or count integers, so every comparison is exact (bit patterns for the float passes); the one exception
