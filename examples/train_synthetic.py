@@ -35,6 +35,20 @@ def validate(net, batches, tta, window, boundary, surface=None, biou=None, regio
                                       if k in rep}
 
 
+def calibration_text(net, batches, fit):
+    """--calibration / --fit-temperature: ECE and NLL of the validation batches (cvk.CalibrationMeter through evaluate_report), and
+    with `fit` the temperature fitted on the same batches (cvk.TemperatureScaler) with the ECE after scaling."""
+    batches = list(batches)
+    before = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, boundary=cvk.CalibrationMeter(12, 11, 15))
+    out = f"calibration: ECE {before['ece']:.4f}  MCE {before['mce']:.4f}  NLL {before['nll']:.4f}  Brier {before['brier']:.4f}"
+    if fit:
+        scaler = cvk.TemperatureScaler(iterations=20, ignore_index=11).fit_network(net, batches)
+        after = cvk.evaluate_report(net, batches, num_classes=12, ignore_index=11, boundary=cvk.CalibrationMeter(12, 11, 15, temperature=scaler))
+        state = "converged" if scaler.converged else "at the bracket's end" if scaler.at_bound else "not converged"
+        out += f"\n{'':10s}temperature T {scaler.temperature:.4f} ({state}): ECE {before['ece']:.4f} -> {after['ece']:.4f}  NLL {before['nll']:.4f} -> {after['nll']:.4f}"
+    return out
+
+
 def bf_text(scores, percentile=95):
     if scores is None:
         return ""
@@ -133,6 +147,10 @@ def main():
                     help="also report the mIoU after regions of fewer than A pixels went to their neighbours' class, and the fragmentation "
                     "(predicted regions over label regions; cvk.RegionMeter)")
     ap.add_argument("--region-connectivity", type=int, default=4, choices=(4, 8), help="with --min-region: 4- or 8-connected regions")
+    ap.add_argument("--calibration", action="store_true",
+                    help="also report the expected calibration error, NLL and Brier score of the validation pass (cvk.CalibrationMeter)")
+    ap.add_argument("--fit-temperature", action="store_true",
+                    help="fit a temperature T on the validation batches (cvk.TemperatureScaler) and report T and the ECE before and after")
     ap.add_argument("--crf", action="store_true",
                     help="also validate with a local-window mean-field CRF on top of the predictions (cvk.LocalCRF; the guide image is the "
                     "network's own input) and print the mIoU with and without it; with --tta-* / --window-crop it refines their result")
@@ -347,6 +365,10 @@ def main():
             if crf is not None:
                 print(f"          with the CRF refinement mIoU {miou_crf:.4f}, without {miou:.4f}  ({crf.iterations} iterations, radius "
                       f"{crf.radius}, dilation {crf.dilation})")
+        if a.calibration or a.fit_temperature:
+            text = calibration_text(net, batches, a.fit_temperature)
+            if rank == 0:
+                print(f"          {text}")
         if a.ema_decay is not None:
             with opt.swap_ema():                                            # the averaged weights (BatchNorm statistics stay the live ones)
                 acc_e, miou_e, bf_e = validate(net, batches, tta, window, boundary, surface, biou, region)

@@ -879,6 +879,45 @@ int cvk_crf_step(const float* unary, int ld_u, int unary_is_prob, const float* q
                  const float* ga, const float* gs, float cb, float wa, float ws, const float* compat, int N, int H, int W, int C,
                  int radius, int dilation, int first, int last, void* stream);
 
+/* ---- calibration meter and temperature fit (Guo et al., "On Calibration of Modern Neural Networks", ICML 2017; not in the
+ * reference) ----
+ * logits: DEVICE float rows [M][ld] with C classes (NHWC), target: DEVICE int64 [M], tau: DEVICE float, the inverse temperature 1 / T
+ * (NULL: 1).  For a pixel with logits x and target t, in fp32:
+ *   z_c = tau x_c, m = max_c z_c, se = sum_c expf(z_c - m) in class order, pred = the first maximum of x (a NaN wins: exactly
+ *   cvk_argmax_channels), conf = 1 / se, the top-label probability (<= 1).
+ *   valid iff t != ignore_index and 0 <= t < C; an out-of-range target is counted in the record and otherwise skipped.
+ *   bin = clamp((int)ceilf(conf * (float)bins) - 1, 0, bins - 1): right-closed bins (b / bins, (b + 1) / bins].
+ *   q = (int64)floor(conf * 2^30): with C <= 128 it carries every bit of conf; sum conf = sum q / 2^30, exact in 64-bit integers.
+ *   nll = (m + logf(se)) - z_t;  brier = sum_c (p_c - [c == t])^2, p_c = expf(z_c - m) * conf.
+ * cvk_calib_accumulate ADDS the valid pixels of the call to
+ *   hist:   DEVICE int64 [C][bins][3], by predicted class and bin: {count, correct (pred == t), sum q}; 64-bit integer atomics;
+ *   record: DEVICE 32 bytes {int64 valid, int64 out of range, double sum nll, double sum brier}: the fp64 sums go through `part`
+ *           (DEVICE scratch of 4 * cvk_ce_blocks(M) doubles) and a one-workgroup finish in a fixed order; no float atomic: two
+ *           calls on the same input give the same bits.
+ * conf (DEVICE float [M]) and pred (DEVICE int64 [M]) are optional maps of EVERY pixel, written when non-NULL.  hist, target, part
+ * and record go together: all NULL writes the maps only (one of them is required then; `bins` is not read).
+ * Limits: 1 <= C <= 128, ld >= C, 1 <= bins <= 64, C * bins <= 2048 (the work-group's table: 48 KiB of LDS).  Two launches (one
+ * without tables), no allocation, no host sync.
+ *
+ * Temperature fit: NLL(tau) = mean over the valid pixels of (lse(tau x) - tau x_t) is convex in tau, with gradient
+ * g = mean(E_p[x] - x_t) and curvature h = mean(Var_p[x]), p = softmax(tau x), Var_p[x] = sum_c p_c (x_c - E_p[x])^2.
+ * state: DEVICE double[9] = {tau, lo, hi, G, H, L, n, k, -}: the sums of g, h and nll terms, the valid pixels and the row counter;
+ * the first 4 bytes of word 8 hold tau as a float, which is what cvk_calib_accumulate's `tau` can point at.  The caller initialises
+ * it: {tau0 (a float's value), 1/64, 64, 0, 0, 0, 0, 0} and (float)tau0.
+ * cvk_calib_newton_accumulate reads (float)state[0] and ADDS one batch's sums to G, H, L, n; a target that is ignore_index or out of
+ * range is skipped (the meter's record counts the latter) (`part` as above; pixel terms in fp32,
+ * sums in fp64, fixed order).  cvk_calib_newton_step (one thread, fp64) closes an iteration over any number of batches: with
+ * g = G / n, h = H / n: g < 0 sets lo = tau, g > 0 sets hi = tau; the candidate is tau - g / h when h > 1e-12; when it is not
+ * strictly inside (lo, hi), or h is too small, it is sqrt(lo * hi); the new tau is the candidate rounded to float once.  n == 0
+ * leaves tau alone.  It writes row k of log (DEVICE double [log_rows][8]): {tau used, n, NLL = L / n, g, h, tau next, lo, hi}
+ * (no row when k >= log_rows), zeroes the sums and increments k.  final_pass != 0: the row is written with tau next = tau and
+ * nothing else changes (the NLL of the fitted tau).  A fit is a chain of these calls on one stream: no host sync, no allocation. */
+int cvk_calib_accumulate(const float* logits, int ld, const int64_t* target, const float* tau, int64_t* hist, double* part, void* record,
+                         float* conf, int64_t* pred, int M, int C, int bins, int ignore_index, void* stream);
+int cvk_calib_newton_accumulate(const float* logits, int ld, const int64_t* target, double* state, double* part, int M, int C,
+                                int ignore_index, void* stream);
+int cvk_calib_newton_step(double* state, double* log, int log_rows, int final_pass, void* stream);
+
 /* ---- input pipeline on device (transforms.ToTensor + Normalize: transforms.py:485-538, MEAN/STD conf/settings.py:8-9) ----
  * src uint8 [N,H,W,3] (channel order as decoded, i.e. cv2 BGR) -> dst float32 NHWC with ld = 4 (pad channel 0):
  * dst[c] = (src[c]/255 - mean3[c]) / std3[c].  mean3 / std3 are HOST pointers to 3 floats. */

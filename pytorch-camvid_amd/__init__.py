@@ -17,7 +17,8 @@ from .functional import (ConfusionMeter, argmax_channels, evaluate,  # noqa: F40
                          boundary_tolerance, boundary_scores, SurfaceDistanceMeter, surface_distances, surface_distance_scores,
                          surface_percentile, BoundaryIoUMeter, chessboard_depth, boundary_dilation, boundary_iou_scores,
                          trimap_scores, connected_components, remove_small_regions, RegionFilter, RegionMeter, region_scores,
-                         LocalCRF, crf_refine, crf_coefficients, crf_tile)
+                         LocalCRF, crf_refine, crf_coefficients, crf_tile, CalibrationMeter, TemperatureScaler,
+                         calibration_scores, confidence_map)
 from .optim import FlatAdamW, FlatSGD, clip_grad_norm_, ema_alpha  # noqa: F401
 from .accumulate import GradAccumulator  # noqa: F401
 from . import ddp  # noqa: F401

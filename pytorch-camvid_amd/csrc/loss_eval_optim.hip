@@ -19,6 +19,7 @@
 //   loss_boundary.h  boundary loss over the signed distance maps of edt.h
 //   loss_seg.h       fused focal + soft-Dice loss
 //   loss_kd.h        knowledge-distillation loss (cross-entropy + temperature KL)
+//   calibration.h    calibration meter (ECE tables, NLL, Brier) and the Newton temperature fit
 //   infer_merge.h    the inference merges: test-time augmentation views and sliding windows
 //   ingest.h         uint8 frames to normalised NHWC; the fused train / val transform
 // A new subject gets a header of that kind, not lines here.
@@ -40,6 +41,7 @@
 #include "loss_boundary.h"
 #include "loss_seg.h"
 #include "loss_kd.h"
+#include "calibration.h"
 #include "infer_merge.h"
 #include "ingest.h"
 

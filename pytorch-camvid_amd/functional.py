@@ -19,6 +19,10 @@ in losses.py; their public names and constants are importable from here as befor
   LocalCRF, crf_refine, crf_coefficients, crf_tile
                     <- local-window mean-field CRF refinement of a prediction under the network's own input as the guide image
                        (ConvCRF's form with a dilation; not in the reference): one stencil launch per iteration
+  CalibrationMeter, calibration_scores, confidence_map, TemperatureScaler
+                    <- expected calibration error, reliability tables, NLL and Brier score of the top-label probability, and
+                       temperature scaling (Guo et al. ICML 2017; not in the reference): one pass over the logits per batch into
+                       integer tables, and a Newton fit of 1 / T that runs on the device without a host sync
 """
 import torch
 
@@ -1362,6 +1366,285 @@ def crf_refine(logits, images, iterations=5, radius=3, dilation=1, appearance=(4
     return LocalCRF(iterations, radius, dilation, appearance, smoothness, compat, mean, std).refine(logits, images, unary_is_prob)
 
 
+CALIB_MAX_CLASSES, CALIB_MAX_BINS, CALIB_MAX_CELLS = 128, 64, 2048     # include/cvk.h: the limits of cvk_calib_accumulate
+CALIB_Q_SCALE = float(1 << 30)                                         # hist[..., 2] holds sum floor(conf * 2^30)
+CALIB_LOG_COLUMNS = ("tau", "n", "nll", "g", "h", "tau_next", "lo", "hi")
+CALIB_TAU_BRACKET = (1.0 / 64.0, 64.0)
+CALIBRATION_REPORT_KEYS = ("ece", "mce", "nll", "brier")
+
+
+def _check_calib_logits(who, logits, label=None):
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or (label is not None and not label.is_cuda):
+        raise RuntimeError(f"pytorch_camvid_amd.{who} needs HIP tensors (no CPU fallback)")
+    if label is not None and label.device != logits.device:
+        raise ValueError(f"{who}: the logits are on {logits.device}, the label on {label.device}")
+    _check_calib_shapes(who, logits, label)
+
+
+def _check_calib_shapes(who, logits, label=None):
+    """dtype, rank, class count and label shape: everything about the tensors but where they live"""
+    if logits.dim() != 4:
+        raise ValueError("expected logits of shape [N, C, H, W]")
+    if logits.dtype != torch.float32:
+        raise ValueError(f"{who}: expected float32 logits, got {logits.dtype}")
+    N, C, H, W = logits.shape
+    if not 1 <= C <= CALIB_MAX_CLASSES:
+        raise ValueError(f"{who} serves 1 to {CALIB_MAX_CLASSES} classes, got C = {C}")
+    if N * H * W == 0:
+        raise ValueError(f"{who}: empty logits")
+    if label is not None:
+        if label.dtype != torch.int64:
+            raise ValueError(f"{who}: expected an int64 label, got {label.dtype}")
+        if tuple(label.shape) != (N, H, W):
+            raise ValueError(f"Expected label size {[N, H, W]}, got {list(label.shape)}")
+
+
+def _check_calib_classes(who, num_classes, bins=1):
+    if not isinstance(num_classes, int) or not 1 <= num_classes <= CALIB_MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes must be an integer in [1, {CALIB_MAX_CLASSES}], got {num_classes!r}")
+    if not isinstance(bins, int) or isinstance(bins, bool) or not 1 <= bins <= CALIB_MAX_BINS:
+        raise ValueError(f"{who}: bins must be an integer in [1, {CALIB_MAX_BINS}], got {bins!r}")
+    if num_classes * bins > CALIB_MAX_CELLS:
+        raise ValueError(f"{who}: num_classes * bins = {num_classes * bins} exceeds {CALIB_MAX_CELLS} (the work-group's table in LDS)")
+
+
+def _calib_tau(who, temperature, device):
+    """The device float the kernel reads as tau = 1 / T: None (tau = 1), a TemperatureScaler's live value, or a new tensor."""
+    if temperature is None:
+        return None
+    if isinstance(temperature, TemperatureScaler):
+        return temperature.tau
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0.0 < float(temperature) < float("inf"):
+        raise ValueError(f"{who}: temperature must be None, a positive finite number or a TemperatureScaler, got {temperature!r}")
+    return torch.full((), 1.0 / float(temperature), device=device, dtype=torch.float32)
+
+
+def calibration_scores(hist, record):
+    """The host arithmetic of CalibrationMeter.compute(): `hist` int64 [C][B][3] = {count, correct, sum floor(conf 2^30)} by predicted
+    class and bin, `record` the four words {valid, out of range, sum nll, sum brier} (an int64 tensor whose last two words are fp64 bit
+    patterns, as the meter keeps it, or a sequence of four numbers).  ECE = sum_b n_b / n |acc_b - conf_b| over Guo's right-closed
+    bins, MCE the maximum gap over the non-empty bins; "ece_per_class" is the same sum within the pixels PREDICTED as a class.  With no
+    valid pixel every score is NaN."""
+    import numpy as np
+    h = np.asarray(hist.cpu() if isinstance(hist, torch.Tensor) else hist).astype(np.int64)
+    if h.ndim != 3 or h.shape[2] != 3:
+        raise ValueError(f"calibration_scores: hist must be [C][B][3], got {list(h.shape)}")
+    if isinstance(record, torch.Tensor):
+        r = record.cpu()
+        sums = r[2:4].view(torch.float64) if r.dtype == torch.int64 else r[2:4].double()
+        valid, bad, s_nll, s_brier = int(r[0]), int(r[1]), float(sums[0]), float(sums[1])
+    else:
+        valid, bad, s_nll, s_brier = int(record[0]), int(record[1]), float(record[2]), float(record[3])
+
+    def gaps(t):                                  # t: [..., B, 3] -> per-bin count, accuracy, confidence, |acc - conf| (NaN where empty)
+        cnt = t[..., 0].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            acc = t[..., 1] / cnt
+            conf = t[..., 2] / CALIB_Q_SCALE / cnt
+        return cnt, acc, conf, np.abs(acc - conf)
+
+    top = h.sum(axis=0)
+    cnt, acc, conf, gap = gaps(top)
+    n = float(cnt.sum())
+    nan = float("nan")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ece = float(np.nansum(cnt * gap) / n) if n > 0 else nan
+        ccnt, _, _, cgap = gaps(h)
+        per_n = ccnt.sum(axis=1)
+        ece_c = np.where(per_n > 0, np.nansum(ccnt * cgap, axis=1) / per_n, np.nan)
+    return {"ece": ece, "mce": float(np.nanmax(gap)) if n > 0 else nan,
+            "nll": s_nll / valid if valid > 0 else nan, "brier": s_brier / valid if valid > 0 else nan,
+            "accuracy": float(top[:, 1].sum() / n) if n > 0 else nan,
+            "mean_confidence": float(top[:, 2].sum() / CALIB_Q_SCALE / n) if n > 0 else nan,
+            "bins": {"count": top[:, 0].copy(), "accuracy": acc, "confidence": conf},
+            "ece_per_class": ece_c, "count_per_class": per_n.astype(np.int64), "valid": valid, "out_of_range": bad}
+
+
+class CalibrationMeter:
+    """Expected calibration error and reliability tables of the top-label probability (Guo et al., ICML 2017), accumulated on the
+    device in one pass over the logits per batch (cvk_calib_accumulate; the definitions are in include/cvk.h):
+
+      meter = CalibrationMeter(num_classes=12, ignore_index=11, bins=15, temperature=None)
+      meter.update(logits, masks)          # float32 [N,C,H,W] (channels_last is read in place), int64 [N,H,W]
+      meter.compute()                      # one device->host copy: "ece", "mce", "nll", "brier", "accuracy", "mean_confidence",
+                                           # "bins" (count / accuracy / confidence per bin), "ece_per_class", "count_per_class"
+                                           # (by predicted class), "valid", "out_of_range"
+
+    `temperature` is None, a float T (the probabilities are softmax(logits / T)), or a TemperatureScaler, whose device value is read at
+    every update without a sync.  `hist` (int64 [C][bins][3]) and `record` (int64 [4]: valid, out of range, and the fp64 bit patterns
+    of sum nll and sum brier) are the device tensors; every word of `hist` is an integer sum, so the tables do not depend on the order
+    of the pixels or of the updates.  Limits: 1 <= C <= 128, 1 <= bins <= 64, C * bins <= 2048."""
+
+    def __init__(self, num_classes=12, ignore_index=11, bins=15, temperature=None, device="cuda"):
+        _check_calib_classes("CalibrationMeter", num_classes, bins)
+        self.num_classes, self.ignore_index, self.bins = num_classes, int(ignore_index), bins
+        self.temperature = temperature
+        self._tau = _calib_tau("CalibrationMeter", temperature, device)
+        self.hist = torch.zeros((num_classes, bins, 3), device=device, dtype=torch.int64)
+        self.record = torch.zeros(4, device=device, dtype=torch.int64)
+        self._part = None
+
+    def reset(self):
+        self.hist.zero_()
+        self.record.zero_()
+
+    def update(self, logits, label, conf=None, pred=None):
+        """Adds one batch.  `conf` (float32 [N,H,W]) and `pred` (int64 [N,H,W]), when given, receive the maps of every pixel."""
+        _check_calib_logits("CalibrationMeter", logits, label)
+        N, C, H, W = logits.shape
+        if C != self.num_classes:
+            raise ValueError(f"CalibrationMeter: the meter has {self.num_classes} classes, the logits {C}")
+        for name, m, dt in (("conf", conf, torch.float32), ("pred", pred, torch.int64)):
+            if m is not None and (m.dtype != dt or tuple(m.shape) != (N, H, W) or not m.is_contiguous() or m.device != logits.device):
+                raise ValueError(f"CalibrationMeter: {name} must be a contiguous {dt} tensor of shape {[N, H, W]} on the logits' device")
+        tau = self._tau
+        if logits.device != self.hist.device or (tau is not None and tau.device != logits.device):
+            raise ValueError(f"CalibrationMeter: the logits are on {logits.device}, the meter's tables on {self.hist.device}"
+                             + (f", its temperature on {tau.device}" if tau is not None else ""))
+        lib = _lib.load()
+        lg, ld = _as_nhwc(logits.detach())
+        lab = label.contiguous()
+        M = N * H * W
+        need = 4 * lib.cvk_ce_blocks(M)
+        if self._part is None or self._part.numel() < need or self._part.device != logits.device:
+            self._part = torch.empty(need, device=logits.device, dtype=torch.float64)
+        check(lib.cvk_calib_accumulate(lg.data_ptr(), ld, lab.data_ptr(), tau.data_ptr() if tau is not None else None,
+                                       self.hist.data_ptr(), self._part.data_ptr(), self.record.data_ptr(),
+                                       conf.data_ptr() if conf is not None else None, pred.data_ptr() if pred is not None else None,
+                                       M, C, self.bins, self.ignore_index, _stream(logits)), "cvk_calib_accumulate")
+
+    def compute(self):
+        both = torch.cat([self.record, self.hist.reshape(-1)]).cpu()                 # one device->host copy
+        return calibration_scores(both[4:].reshape(self.num_classes, self.bins, 3), both[:4])
+
+
+def confidence_map(logits, temperature=None):
+    """(conf float32 [N,H,W], pred int64 [N,H,W]): the top-label probability of softmax(logits / T) and its class (the first maximum,
+    as argmax_channels), from the meter's kernel without its tables: one launch.  The input of confidence-thresholded
+    pseudo-labelling.  `temperature` as in CalibrationMeter."""
+    _check_calib_logits("confidence_map", logits)
+    lib = _lib.load()
+    N, C, H, W = logits.shape
+    tau = _calib_tau("confidence_map", temperature, logits.device)
+    if tau is not None and tau.device != logits.device:
+        raise ValueError(f"confidence_map: the logits are on {logits.device}, the temperature on {tau.device}")
+    lg, ld = _as_nhwc(logits.detach())
+    conf = torch.empty((N, H, W), device=logits.device, dtype=torch.float32)
+    pred = torch.empty((N, H, W), device=logits.device, dtype=torch.int64)
+    check(lib.cvk_calib_accumulate(lg.data_ptr(), ld, None, tau.data_ptr() if tau is not None else None, None, None, None,
+                                   conf.data_ptr(), pred.data_ptr(), N * H * W, C, 1, 0, _stream(logits)), "cvk_calib_accumulate")
+    return conf, pred
+
+
+class TemperatureScaler:
+    """Temperature scaling (Guo et al., ICML 2017): one scalar T fitted by minimising the NLL of softmax(logits / T) on held-out
+    batches.  The fit is a bracketed Newton iteration on tau = 1 / T that runs on the device as a fixed chain of launches
+    (cvk_calib_newton_accumulate per batch, cvk_calib_newton_step per iteration) with no host sync:
+
+      scaler = TemperatureScaler(iterations=20, init=1.0, ignore_index=11)
+      scaler.fit(logits_list, labels_list)        # stored float32 [N,C,H,W] / int64 [N,H,W] tensors; or
+      scaler.fit_network(net, batches)            # an eval-mode forward per batch, logits kept
+      scaler.temperature                          # host float T (one copy);  scaler.tau: 0-dim device view of 1 / T
+      scaler(logits)                              # logits * tau, layout preserved
+      scaler.log()                                # float64 [iterations + 1, 8]: tau, n, nll, g, h, tau_next, lo, hi per iteration
+
+    tau is kept inside [1/64, 64].  `converged`: the last row's Newton step would move tau by less than 1e-5 of its value;
+    `at_bound`: the fit ran into an end of the bracket (the NLL has no minimum inside it: a perfectly separable set, say)."""
+
+    def __init__(self, iterations=20, init=1.0, ignore_index=11, device="cuda"):
+        if not isinstance(iterations, int) or isinstance(iterations, bool) or not 1 <= iterations <= 1000:
+            raise ValueError(f"TemperatureScaler: iterations must be an integer in [1, 1000], got {iterations!r}")
+        if isinstance(init, bool) or not isinstance(init, (int, float)) or not 1.0 / 64.0 <= 1.0 / float(init or float("nan")) <= 64.0:
+            raise ValueError(f"TemperatureScaler: the initial temperature must lie in [1/64, 64], got {init!r}")
+        self.iterations, self.init, self.ignore_index = iterations, float(init), int(ignore_index)
+        self._state = torch.zeros(9, device=device, dtype=torch.float64)
+        self._log = torch.zeros((iterations + 1, len(CALIB_LOG_COLUMNS)), device=device, dtype=torch.float64)
+        self._part = None
+        self._reset_state()
+
+    def _reset_state(self):
+        tau0 = float(torch.tensor(1.0 / self.init, dtype=torch.float32))
+        host = torch.tensor([tau0, CALIB_TAU_BRACKET[0], CALIB_TAU_BRACKET[1], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float64)
+        host[8:9].view(torch.float32)[0] = tau0
+        self._state.copy_(host)                 # one host-to-device copy; the kernels own the state from here
+        self._log.zero_()
+
+    @property
+    def tau(self):
+        """0-dim float32 device view of the fitted inverse temperature; the step kernel writes it"""
+        return self._state[8:9].view(torch.float32)[0]
+
+    @property
+    def temperature(self):
+        return 1.0 / float(self.tau)
+
+    def log(self):
+        return self._log.clone()
+
+    def _last(self):
+        return [float(v) for v in self._log[self.iterations].cpu()]
+
+    @property
+    def at_bound(self):
+        tau, _, _, _, _, _, lo, hi = self._last()
+        return bool((hi == CALIB_TAU_BRACKET[1] and tau >= hi * (1.0 - 1e-3)) or (lo == CALIB_TAU_BRACKET[0] and tau <= lo * (1.0 + 1e-3)))
+
+    @property
+    def converged(self):
+        tau, n, _, g, h, _, _, _ = self._last()
+        return bool(n > 0 and not self.at_bound and h > 1e-12 and abs(g / h) <= 1e-5 * tau)
+
+    def fit(self, logits_list, labels_list):
+        """Fits on stored batches: every iteration walks every batch, then steps; a last pass leaves the NLL of the fitted tau in the
+        log's last row.  Labels that are `ignore_index` or outside [0, C) are skipped (a CalibrationMeter counts the latter as
+        "out_of_range"; the fit does not report them).  Returns self."""
+        if isinstance(logits_list, torch.Tensor):
+            logits_list, labels_list = [logits_list], [labels_list]
+        logits_list, labels_list = list(logits_list), list(labels_list)
+        if not logits_list or len(logits_list) != len(labels_list):
+            raise ValueError("TemperatureScaler.fit: expected as many label tensors as logits tensors, and at least one")
+        lib = _lib.load()
+        calls = []
+        for logits, label in zip(logits_list, labels_list):
+            _check_calib_logits("TemperatureScaler", logits, label)
+            if logits.device != self._state.device:
+                raise ValueError(f"TemperatureScaler: the logits are on {logits.device}, the scaler on {self._state.device}")
+            lg, ld = _as_nhwc(logits.detach())
+            calls.append((lg, ld, label.contiguous(), lg.shape[0] * lg.shape[1] * lg.shape[2], logits.shape[1]))
+        need = 4 * max(lib.cvk_ce_blocks(c[3]) for c in calls)
+        if self._part is None or self._part.numel() < need:
+            self._part = torch.empty(need, device=self._state.device, dtype=torch.float64)
+        self._reset_state()
+        stream = _stream(logits_list[0])
+        state, log, part = self._state.data_ptr(), self._log.data_ptr(), self._part.data_ptr()
+        for it in range(self.iterations + 1):
+            for lg, ld, lab, M, C in calls:
+                check(lib.cvk_calib_newton_accumulate(lg.data_ptr(), ld, lab.data_ptr(), state, part, M, C, self.ignore_index, stream),
+                      "cvk_calib_newton_accumulate")
+            check(lib.cvk_calib_newton_step(state, log, self.iterations + 1, int(it == self.iterations), stream), "cvk_calib_newton_step")
+        return self
+
+    def fit_network(self, net, batches, window=None):
+        """Runs `net` once over `batches` ((images, masks) on the GPU) in eval mode under no_grad, keeps the logits and fits on them.
+        Memory: the kept logits, 4 C M bytes per batch (C classes, M = N H W pixels; 66 MB at 8 x 12 x 360 x 480).  With `window` (a
+        SlidingWindow) the logits are the windows' merged ones.  `net.training` is restored."""
+        _check_window(window)
+        was_training = net.training
+        net.eval()
+        kept, masks_kept = [], []
+        try:
+            with torch.no_grad():
+                for images, masks in batches:
+                    kept.append(net(images) if window is None else window(net, images)[0])
+                    masks_kept.append(masks)
+        finally:
+            net.train(was_training)
+        return self.fit(kept, masks_kept)
+
+    def __call__(self, logits):
+        return logits * self.tau
+
+
 def _evaluate_tta(net, batches, num_classes, ignore_index, tta, loss_fn=None, contour_meters=()):
     """evaluate / evaluate_report with test-time augmentation: (meter, the per-batch losses of the loss view: empty without one).
     `contour_meters` (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter, RegionMeter) see the predictions the ConfusionMeter sees."""
@@ -1429,9 +1712,10 @@ def _contour_meters(boundary):
     """The meters behind evaluate_report's `boundary`: None, one meter, or a tuple / list with at most one meter of each kind."""
     meters = list(boundary) if isinstance(boundary, (tuple, list)) else [] if boundary is None else [boundary]
     for m in meters:
-        if not isinstance(m, (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter, RegionMeter)):
+        if not isinstance(m, (BoundaryMeter, SurfaceDistanceMeter, BoundaryIoUMeter, RegionMeter, CalibrationMeter)):
             raise ValueError("boundary must be a BoundaryMeter or None, or a SurfaceDistanceMeter, or a tuple or list of one of each. "
-                             f"A BoundaryIoUMeter and a RegionMeter are taken the same way. Got: {type(m).__name__}")
+                             "A BoundaryIoUMeter, a RegionMeter and a CalibrationMeter are taken the same way. "
+                             f"Got: {type(m).__name__}")
     if len({type(m) for m in meters}) != len(meters):
         raise ValueError("boundary holds two meters of one kind: their scores would share the report's keys")
     return meters
@@ -1440,7 +1724,9 @@ def _contour_meters(boundary):
 def _with_boundary(report, contour_meters):
     for m in contour_meters:
         scores = m.compute()
-        if isinstance(m, RegionMeter):
+        if isinstance(m, CalibrationMeter):
+            keys = CALIBRATION_REPORT_KEYS
+        elif isinstance(m, RegionMeter):
             keys = ("fragmentation", "miou_filtered", "regions_pred")
         elif isinstance(m, BoundaryIoUMeter):
             keys = ("biou", "biou_per_class") + (("trimap_miou",) if m.trimap_widths else ())
@@ -1464,9 +1750,14 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
     the report gains "hd95", "hd", "assd" and their "_per_class" arrays; the meter's `compute()` has the rest (unmatched classes,
     images).  A BoundaryIoUMeter is a third kind, alone or beside one of each of the others: the report gains "biou" and
     "biou_per_class", and "trimap_miou" when the meter has trimap widths.  A RegionMeter is a fourth kind: the report gains
-    "fragmentation", "miou_filtered" and "regions_pred"."""
+    "fragmentation", "miou_filtered" and "regions_pred".  A CalibrationMeter is a fifth kind: it is fed the logits `loss_fn` sees
+    (with `window`, the merged ones) and the masks, and the report gains "ece", "mce", "nll" and "brier"; with `tta` it raises
+    ValueError (the calibration of merged views is not provided)."""
     _check_tta_window("evaluate_report", tta, window)
     contour_meters = _contour_meters(boundary)
+    if tta is not None and any(isinstance(m, CalibrationMeter) for m in contour_meters):
+        raise ValueError("evaluate_report(): a CalibrationMeter with tta= is not provided: the merged views have probabilities but no "
+                         "logits to calibrate; pass window= or neither")
     loss_fn = loss_fn or CrossEntropyLoss()
     for m in contour_meters:
         m.reset()
@@ -1500,7 +1791,7 @@ def evaluate_report(net, batches, num_classes=12, ignore_index=11, loss_fn=None,
             n += 1
             meter.update(pred, masks)
             for m in contour_meters:
-                m.update(pred, masks)
+                m.update(logits if isinstance(m, CalibrationMeter) else pred, masks)
     net.train(was_training)
     if meter is None:
         raise ValueError("evaluate_report(): no batches")
