@@ -11,14 +11,14 @@ from .losses import (CrossEntropyLoss, cross_entropy, last_ce_status, Segmentati
                      LovaszSoftmaxLoss, lovasz_softmax,
                      BoundaryLoss, boundary_loss, squared_distance_maps, signed_distance_maps,
                      DistillationLoss, distillation_loss, distillation_scales)
-from .functional import (ConfusionMeter, argmax_channels, evaluate,  # noqa: F401
-                         evaluate_report, predict, preprocess_uint8, DevicePrefetcher, TestTimeAugmentation, SlidingWindow,
-                         ClassFrequencyMeter, class_weights, weights_from_counts, BoundaryMeter, label_boundaries,
-                         boundary_tolerance, boundary_scores, SurfaceDistanceMeter, surface_distances, surface_distance_scores,
-                         surface_percentile, BoundaryIoUMeter, chessboard_depth, boundary_dilation, boundary_iou_scores,
-                         trimap_scores, connected_components, remove_small_regions, RegionFilter, RegionMeter, region_scores,
-                         LocalCRF, crf_refine, crf_coefficients, crf_tile, CalibrationMeter, TemperatureScaler,
-                         calibration_scores, confidence_map)
+from .inference import (argmax_channels, preprocess_uint8, DevicePrefetcher, TestTimeAugmentation, SlidingWindow,  # noqa: F401
+                        LocalCRF, crf_refine, crf_coefficients, crf_tile)
+from .meters import (ConfusionMeter, ClassFrequencyMeter, class_weights, weights_from_counts, BoundaryMeter, label_boundaries,  # noqa: F401
+                     boundary_tolerance, boundary_scores, SurfaceDistanceMeter, surface_distances, surface_distance_scores,
+                     surface_percentile, BoundaryIoUMeter, chessboard_depth, boundary_dilation, boundary_iou_scores,
+                     trimap_scores, connected_components, remove_small_regions, RegionFilter, RegionMeter, region_scores,
+                     CalibrationMeter, TemperatureScaler, calibration_scores, confidence_map)
+from .functional import evaluate, evaluate_report, predict  # noqa: F401
 from .optim import FlatAdamW, FlatSGD, clip_grad_norm_, ema_alpha  # noqa: F401
 from .accumulate import GradAccumulator  # noqa: F401
 from . import ddp  # noqa: F401

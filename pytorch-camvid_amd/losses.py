@@ -1,4 +1,4 @@
-"""The losses of the hot path as autograd nodes on HIP tensors (the meters and the inference drivers are in functional.py).
+"""The losses of the hot path as autograd nodes on HIP tensors (the meters are in meters.py, the inference drivers in inference.py).
 
   CrossEntropyLoss, cross_entropy
                     <- nn.CrossEntropyLoss() of reference train.py:105 (mean over N*H*W, no ignored class); also torch's

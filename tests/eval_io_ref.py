@@ -1,6 +1,6 @@
 """Plain numpy restatements of the image-ingest and evaluation entry points, written from their definitions for the tests
 (include/cvk.h: cvk_import_nchw, cvk_export_nchw, cvk_zero_frame, cvk_preprocess_u8, cvk_argmax_channels, cvk_confusion_accumulate;
-functional.py: ConfusionMeter.compute / precision_recall), and the seeded inputs the CPU and the GPU tests share.  Nothing here
+meters.py: ConfusionMeter.compute / precision_recall), and the seeded inputs the CPU and the GPU tests share.  Nothing here
 touches a GPU or imports the package.
 
   import       dst[n][y][x][c] = src[n][c][y][x] for c < C, +0.0 for C <= c < ld          pure data movement: any dtype, so the

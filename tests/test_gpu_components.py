@@ -176,7 +176,7 @@ def test_vote_slots_past_2_31_elements():
         rec = rf.last_record[0].cpu()
         assert rec[0].tolist() == [1, H * W - 2, H * W - 2, 0, 0, 0, 2, 0]
         assert rec[1].tolist() == [1, 1, 1, 1, 1, 1, 0, 0] and rec[31].tolist() == [1, 1, 1, 1, 1, 1, 0, 0] and not rec[2:31].any()
-    A.functional._RegionBuffers._buffers.clear()            # 9.5 GB of workspace: not kept for the rest of the session
+    A.meters._workspaces.clear()                            # 9.5 GB of workspace: not kept for the rest of the session
 
 
 def test_region_meter_against_the_restatement():
