@@ -47,15 +47,16 @@ passes back to back (each with its cvk_grad_accumulate launch), then the tail ab
 are `torch.stack(micro_losses).mean()`, computed on the device inside the graph; the log gets one row per update and the scheduler
 steps once per replay.  The accumulator's identity, `steps` and `mean` are baked in.  Not together with allow_grad_sync=True.
 """
+import ctypes
+
 import torch
 
 from . import _lib, engine
 from ._lib import check
 from .optim import ema_alpha as _ema_alpha
 
-HYPER_FLOATS = 7                         # include/cvk.h cvk_adamw_hyper: lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt; cvk_sgd_hyper has
-                                         # the same size with lr and momentum in floats 0 and 1
-HYPER_BYTES = 4 * HYPER_FLOATS
+HYPER_BYTES = ctypes.sizeof(_lib.AdamwHyper)   # include/cvk.h cvk_adamw_hyper: all floats; cvk_sgd_hyper has the same size with lr and
+HYPER_FLOATS = HYPER_BYTES // 4                # momentum in floats 0 and 1
 HYPER_SLOTS = 32                         # pinned staging records: the host may run this many replays ahead of the GPU before it waits
 
 

@@ -139,7 +139,7 @@ class _CrossEntropy(torch.autograd.Function):
         return d.permute(0, 3, 1, 2), None, None, None
 
 
-REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}      # include/cvk.h CVK_REDUCTION_*
+REDUCTIONS = {k: _lib.DEFINES["CVK_REDUCTION_" + k.upper()] for k in ("none", "mean", "sum")}
 
 
 class _CrossEntropyEx(torch.autograd.Function):
@@ -221,7 +221,7 @@ def cross_entropy(logits, target, weight=None, ignore_index=-100, reduction="mea
     return _ce(logits, target, weight, 1.0, ignore_index, reduction, label_smoothing)
 
 
-DICE_AVERAGES = {"present": 0, "all": 1}           # include/cvk.h CVK_DICE_*
+DICE_AVERAGES = {k: _lib.DEFINES["CVK_DICE_" + k.upper()] for k in ("present", "all")}
 SEG_RECORD_HEAD = 7                                # loss | valid | out of range | sum w[t] | F | D | K, then dice_c, a_c, b_c
 
 
@@ -461,10 +461,10 @@ def ohem_cross_entropy(logits, target, thresh, min_kept, weight=None, ignore_ind
     return _OhemCrossEntropy.apply(logits, target, weight, (lam, min_kept, ignore_index, 1.0))
 
 
-LOVASZ_CLASSES = {"present": 0, "all": 1}          # include/cvk.h CVK_LOVASZ_*
+LOVASZ_CLASSES = {k: _lib.DEFINES["CVK_LOVASZ_" + k.upper()] for k in ("present", "all")}
 LOVASZ_RECORD_HEAD = 8                             # loss | V | out of range | J | H | evaluated pairs | counted segments | sum w[t]
 LOVASZ_CLASS_SLOTS = 128                           # L_c at [8 + c], G_c at [8 + 128 + c]
-LOVASZ_SORT_TILE = 2048                            # include/cvk.h CVK_LOVASZ_SORT_TILE: elements a sort work-group covers
+LOVASZ_SORT_TILE = _lib.DEFINES["CVK_LOVASZ_SORT_TILE"]   # elements a sort work-group covers
 
 
 def _check_lovasz_options(lovasz, ce, classes, per_image, weight):

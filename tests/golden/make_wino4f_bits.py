@@ -16,6 +16,9 @@ import sys
 import numpy as np
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from pytorch_camvid_amd._lib import bind    # noqa: E402  argument types from include/cvk.h: the given build must match it in these four
+
 SHAPE = dict(N=2, H=24, W=44, Cin=64, Cout=64)      # 11 column groups per row (ragged against the 128-group tiles), 2 x 24 rows
 
 
@@ -41,12 +44,7 @@ def run(lib):
     dev = torch.device("cuda:0")
     x, w, b = (t.to(dev) for t in inputs())
     st = torch.cuda.current_stream().cuda_stream
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    lib.cvk_wino4f_weight_floats.restype = ctypes.c_size_t
-    lib.cvk_wino4f_weight_floats.argtypes = [ci, ci]
-    lib.cvk_wino4f_weight_transform.argtypes = [vp, vp, ci, ci, ci, vp]
-    lib.cvk_wino4f_stat_partials.argtypes = [ci, ci, ci]
-    lib.cvk_conv3x3_wino4f.argtypes = [vp] * 6 + [ci] * 7 + [vp]
+    bind(lib, names=["cvk_wino4f_weight_floats", "cvk_wino4f_weight_transform", "cvk_wino4f_stat_partials", "cvk_conv3x3_wino4f"])
     out = {}
     for tag, dgrad in (("fwd", 0), ("dgrad", 1)):
         Uf = torch.empty(lib.cvk_wino4f_weight_floats(s["Cout"], s["Cin"]), device=dev)

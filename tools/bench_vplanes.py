@@ -33,8 +33,7 @@ def main():
     base = None         # optional: an older build of the library (raw handle), e.g. scratch/baselib/libcvk_r6base.so = the kernels before round 6
     if len(sys.argv) > 1:
         import ctypes
-        base = ctypes.CDLL(os.path.abspath(sys.argv[1]))
-        base.cvk_conv3x3_wino4f.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 7 + [ctypes.c_void_p]
+        base = _lib.bind(ctypes.CDLL(os.path.abspath(sys.argv[1])), names=["cvk_conv3x3_wino4f"])
     s = torch.cuda.current_stream().cuda_stream
     tf = tv = tw_old = tw_new = 0.0
     for name, ci, co, H, W in LAYERS:
