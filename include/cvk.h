@@ -135,7 +135,8 @@ int cvk_conv3x3_w2d(const float* x, const float* U, const float* bias, float* y,
 /* the three passes of cvk_conv3x3_w2d, callable (and timed) one by one.  V float[36][Tpad][Cin] + 512 bytes of slack,
  * Tpad = cvk_w2d_tpad(T), rows beyond T zero; Mo float[f][36][T][Cout] with f = cvk_w2d_ksplit(T, Cin, Cout) K-range planes
  * (the tiles of the last partial round of workgroups are split in K; the output pass adds the planes in a fixed order and
- * therefore takes Cin as well) */
+ * therefore takes Cin as well).  cvk_w2d_output writes the columns [0, Cout) of every pixel of y and leaves the pad columns
+ * [Cout, ldy) as they were. */
 int cvk_w2d_ksplit(int T, int Cin, int Cout);
 int cvk_w2d_input_transform(const float* x, float* V, int N, int H, int W, int Cin, void* stream);
 int cvk_w2d_gemm(const float* V, const float* U, float* Mo, int T, int Cin, int Cout, void* stream);

@@ -1495,7 +1495,12 @@ extern "C" int cvk_w2d_output(const float* Mo, const float* bias, float* y, floa
 extern "C" int cvk_conv3x3_w2d(const float* x, const float* U, const float* bias, float* y, float* stats, float* counts,
                                int N, int H, int W, int Cin, int Cout, int ldy, void* workspace, size_t workspace_bytes,
                                void* stream) {
-    CVK_CHECK_ARG(workspace && N > 0 && H > 0 && W > 0, "cvk_conv3x3_w2d: bad arguments");
+    // every rejection of the three passes, before the first of them runs (and before the workspace query, which answers 0 for Cin < 32)
+    CVK_CHECK_ARG(x && U && y && workspace && N > 0 && H > 0 && W > 0, "cvk_conv3x3_w2d: bad arguments");
+    CVK_CHECK_ARG(Cin >= 32 && Cin % 32 == 0 && Cout >= 64 && Cout % 4 == 0 && ldy >= Cout && ldy % 4 == 0,
+                  "cvk_conv3x3_w2d: needs Cin %% 32 == 0, Cout %% 4 == 0, Cout >= 64, ldy >= Cout, ldy %% 4 == 0 (got Cin %d, Cout %d, ldy %d)", Cin, Cout, ldy);
+    CVK_CHECK_ARG((stats == nullptr) == (counts == nullptr), "cvk_conv3x3_w2d: stats and counts go together");
+    CVK_CHECK_ARG(cvk_aligned16(x) && cvk_aligned16(U) && cvk_aligned16(y), "cvk_conv3x3_w2d: pointers must be 16-byte aligned");
     CVK_CHECK_ARG(cvk_aligned16(workspace) && workspace_bytes >= cvk_conv3x3_w2d_workspace_bytes(N, H, W, Cin, Cout),
                   "cvk_conv3x3_w2d: workspace too small or misaligned");
     const int T = w2_tiles(4, N, H, W);
@@ -1534,6 +1539,7 @@ extern "C" int cvk_conv3x3_wgrad_w2d(const float* x, const float* dy, float* dw,
     CVK_CHECK_ARG(dy && dw && workspace, "cvk_conv3x3_wgrad_w2d: null pointer");
     CVK_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cin <= Cin_pad && Cin_pad % 4 == 0 && Cout > 0 && Cout % 4 == 0 && ld_dy >= Cout && ld_dy % 4 == 0,
                   "cvk_conv3x3_wgrad_w2d: bad shape (channel counts must be multiples of 4)");
+    CVK_CHECK_ARG(cvk_aligned16(x) && cvk_aligned16(dy), "cvk_conv3x3_wgrad_w2d: pointers must be 16-byte aligned");      // before the first pass runs
     CVK_CHECK_ARG(cvk_aligned16(workspace) && workspace_bytes >= cvk_conv3x3_wgrad_w2d_workspace_bytes(N, H, W, Cin_pad, Cout),
                   "cvk_conv3x3_wgrad_w2d: workspace too small or misaligned");
     const int T = w2_tiles(4, N, H, W), Tpad = w2_tpad(T);
